@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the MI355X-native BWAS hot path (driver contract in the task statement).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline figure only: set-up, W untimed steps, exactly K timed steps, the JSON line.  `--full`
+adds everything else the benchmark measures (device-side launch profile and rooflines, the fused one-hot leg, concurrent
+instances, expand_1M, the sharded queue, the network-in-the-loop legs, CPU baselines, the expand workload's write
+ceiling).  `--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (float32 /
+float64, <= 64 MB in all); the inputs are seeded, so two builds can be compared output for output.
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (the driver) or
 directly — bench.py then re-executes itself under torch.distributed.run, one rank per GPU (rank r pinned to GPU r, the
@@ -13,11 +19,11 @@ Workloads:
                      device-resident engine.  One step = one full BWAS iteration: pop 20 000 by (cost, push order) ->
                      expand 240 000 children (+is_solved, hash, node fields) -> heuristic -> cost -> CLOSED dedup ->
                      push.  `value` is measured with the built-in hash-derived heuristic 10+5*u01(hash) (SURVEY §8d
-                     "engine-only") over episodes of W untimed + K timed iterations on fresh test-set scrambles, repeated
-                     until >= 0.25 s were timed.  The same JSON line carries: `roofline` (dominant launch + every launch
-                     against the same roofline, timed by device-side stamps inside the replayed hipGraph over one more
-                     episode of the timed shape), `roofline_iteration` (SURVEY §8(d) bytes x batch / ms_per_step),
-                     `engine_onehot_f32` (the same iteration with the fp32 one-hot rows fused into the expansion launch),
+                     "engine-only") over one episode of W untimed + K timed iterations on a test-set scramble; beside it
+                     `roofline_iteration` (SURVEY §8(d) bytes x batch / ms_per_step).  With --full the same JSON line
+                     carries: `roofline` (dominant launch + every launch against the same roofline, timed by device-side
+                     stamps inside the replayed hipGraph over one more episode of the timed shape), `engine_onehot_f32`
+                     (the same iteration with the fp32 one-hot rows fused into the expansion launch),
                      `expand_1M` (BASELINE configs[1]: the gather kernel on 1M states, fp32 and bf16 one-hot rows, each
                      with its HBM roofline), `end_to_end_nnet` (the 14.7M-parameter ResNet heuristic in the loop: fp32 parity mode, bf16 on the
                      library / on the hand-written layer kernel, reference order; synthetic weights — the reference's
@@ -47,13 +53,41 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (≈6.3 TB/s achievable)
-MIN_TIMED_S = 0.25     # the astar legs repeat their K-step region on fresh scrambles until this much time was timed
+MIN_TIMED_S = 0.25     # the --full astar legs repeat their K-step region on fresh scrambles until this much time was timed
 STATE_DIM = {"cube3": 54, "puzzle15": 16, "puzzle24": 25, "puzzle35": 36, "puzzle48": 49}
 
 
 def synth_states(n: int, d: int, seed: int = 0) -> np.ndarray:
     rng = np.random.default_rng(seed)
     return rng.permuted(np.tile(np.arange(d, dtype=np.uint8), (n, 1)), axis=1)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def sample_rows(x, max_rows: int):
+    """The rows of `x` a dump keeps: all of them, or a fixed seeded sample (in row order) when there are more."""
+    if x.shape[0] <= max_rows:
+        return x
+    idx = np.sort(np.random.default_rng(0).choice(x.shape[0], max_rows, replace=False))
+    return x[torch.from_numpy(idx).to(x.device)] if torch.is_tensor(x) else x[idx]
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """`--dump-outputs`: every array as <out_dir>/<name>.npy, float64 where float32 would not hold the values exactly."""
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach().cpu()
+            a = (a.float() if a.dtype in (torch.bfloat16, torch.float16) else a).numpy()
+        a = np.asarray(a)
+        conv[name] = a.astype(np.float64 if a.dtype in (np.float64, np.int64, np.uint64, np.int32, np.uint32) else np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: outputs to dump take %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 _BACKEND = "nccl"
@@ -179,7 +213,7 @@ def run_selftest(args, world, rank):
     units = reduce_ranks(float(args.steps * (rank + 1)), world, "sum")
     return {"value": units / wall, "ms_per_step": wall / args.steps * 1e3,
             "config": {"workload": "selftest (no GPU work)", "parallelism": "x%d" % world},
-            "per_rank_value": gather_ranks(float(rank), world)}
+            "per_rank_value": gather_ranks(float(rank), world), "outputs": {"units": np.array([units])}}
 
 
 # --------------------------------------------------------------------------------------------------
@@ -205,11 +239,12 @@ def engine_bytes(env: str, B: int, onehot_bytes: int):
     }
 
 
-def run_astar_leg(args, world, rank, onehot_dtype, min_timed_s, profile_iters):
+def run_astar_leg(args, world, rank, onehot_dtype, min_timed_s, profile_iters, keep_outputs=False):
     """Episodes of [reset on a fresh scramble, W untimed iterations, K timed iterations], repeated until min_timed_s of
-    timed region accumulated (a batch-20 000 iteration is ~0.1 ms: K alone would be a few milliseconds).  A real cube3
+    timed region accumulated (min_timed_s = 0: exactly one episode, the headline's K timed steps).  A real cube3
     search lasts a few hundred iterations (results/cube3: <= 6.1e7 nodes), so episodes — not one endless search — are
-    the workload.  Every timed region is bracketed by barrier + synchronize on all ranks."""
+    the workload.  Every timed region is bracketed by barrier + synchronize on all ranks.  keep_outputs: the result
+    carries what the last timed iteration computed (its children, the search's counters) under "outputs"."""
     from deepcubea_amd import _lib
     from deepcubea_amd.search_methods.engine import BwasEngine
     B, w = args.batch_size, args.weight
@@ -225,6 +260,15 @@ def run_astar_leg(args, world, rank, onehot_dtype, min_timed_s, profile_iters):
     graph = not args.no_graph
     total_t, total_exp, total_gen, local_exp, episodes, dev_ms = 0.0, 0.0, 0.0, 0.0, 0, 0.0
     st1 = None
+    if min_timed_s <= 0:
+        # a single timed episode: one untimed episode of the same shape first, so that the hipGraph chunks of the timed
+        # window (one per dca_engine_plan_chunk shape) are captured there and not inside the timed region
+        root = test_root(rank, args.env)
+        eng.reset(root)
+        if sem == _lib.SEM_PY:
+            eng.root_commit(_lib.heuristic_builtin(hid, torch.from_numpy(root[None].copy()).cuda()))
+        eng.run_builtin(hid, warm, use_graph=graph)
+        eng.run_builtin(hid, args.steps, use_graph=graph)
     while True:
         root = test_root(rank + world * episodes, args.env)
         eng.reset(root)
@@ -257,6 +301,12 @@ def run_astar_leg(args, world, rank, onehot_dtype, min_timed_s, profile_iters):
            "timed_s": total_t, "device_ms_per_step": dev_ms / (episodes * args.steps), "local_value": local_exp / total_t,
            "open_size_end": st1["open_size"], "closed_size_end": st1["closed_size"],
            "nodes_generated_timed_rank0": total_gen}
+    if keep_outputs:
+        ch = eng.last_children().cpu().numpy()  # (a view of the engine's node pool: copied before anything reuses it)
+        res["outputs"] = {"children": sample_rows(ch, (48 << 20) // (4 * ch.shape[1])),
+                          "search_counters": np.array([st1[k] for k in ("iterations", "nodes_generated", "nodes_expanded",
+                                                                        "open_size", "closed_size", "pool_size")],
+                                                      dtype=np.float64)}
     if profile_iters > 0:
         # One more episode of exactly the timed shape — fresh scramble, the same W untimed iterations, then the K iterations
         # that the timed regions cover (rebase iterations included) — replayed one at a time with the device-side stamps
@@ -280,11 +330,13 @@ def run_astar_leg(args, world, rank, onehot_dtype, min_timed_s, profile_iters):
 def run_astar(args, world, rank):
     B, w = args.batch_size, args.weight
     A = 12 if args.env == "cube3" else 4
-    leg = run_astar_leg(args, world, rank, None, MIN_TIMED_S, args.profile_iters)
+    leg = run_astar_leg(args, world, rank, None, 0.0, args.profile_iters if args.full else 0,
+                        keep_outputs=bool(args.dump_outputs))
     per_rank = gather_ranks(leg["local_value"], world)
     res = {
         "value": leg["value"],
         "ms_per_step": leg["ms_per_step"],
+        "outputs": leg.get("outputs"),
         "config": {"workload": "%s BWAS iteration on the device-resident engine, batch %d, weight %.2f, "
                                "%s semantics, heuristic = built-in 10+5*u01(hash) (engine-only, SURVEY §8d), no one-hot "
                                "rows (see engine_onehot_f32 for the north star's fused one-hot); BASELINE configs[2] "
@@ -353,6 +405,8 @@ def run_astar(args, world, rank):
                                  "achieved": it_bytes / (leg["ms_per_step"] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                  "frac": it_bytes / (leg["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS}
     res["per_rank_value"] = per_rank
+    if not args.full:
+        return res
     if args.onehot_leg:
         oh = run_astar_leg(args, world, rank, torch.float32, MIN_TIMED_S, args.profile_iters)
         algo = engine_bytes(args.env, B, 4)
@@ -674,13 +728,17 @@ def run_avi(args, world, rank):
     barrier(world)
     wall = reduce_ranks(time.perf_counter() - t0, world, "max")
     total = reduce_ranks(float(tot), world, "sum")
+    outputs = None
+    if args.dump_outputs:
+        outputs = {"states": sample_rows(sn, 1 << 16), "cost_to_go": sample_rows(out, 1 << 16),
+                   "is_solved": sample_rows(sv, 1 << 16)}
     if fast.l1_embed_w is not None:  # layer 1 as an embedding sum (dca_l1_embed): no multiply-adds issued for it
         macs -= model.fc1.in_features * model.fc1.out_features
     flops = 2.0 * macs * A * (tot / args.steps)
     published = {"cube3": "1.55e5 states/s on 3 GPUs + 30 CPU procs (saved_models/cube3/output.txt)",
                  "puzzle48": "9.4e4 states/s on 4 GPUs + 30 CPU procs (50M states in 528-530 s, saved_models/puzzle48/output.txt)"}
     return {
-        "value": total / wall, "ms_per_step": wall / args.steps * 1e3,
+        "value": total / wall, "ms_per_step": wall / args.steps * 1e3, "outputs": outputs,
         "config": {"workload": "%s AVI update step (BASELINE configs[4] / avi.py:do_update): generate %d states "
                                "(back_max %d) -> expand -> ResNet heuristic on %d children -> Bellman backup; %s "
                                "heuristic, synthetic weights" % (args.env, n, back_max, A, args.nnet_dtype),
@@ -724,7 +782,11 @@ def run_train(args, world, rank):
     barrier(world)
     wall = reduce_ranks(time.perf_counter() - t0, world, "max")
     flops = 3 * 2.0 * 14_621_000 * B  # forward + backward (2x) of the dense layers
-    return {"value": B * world * args.steps / wall, "ms_per_step": wall / args.steps * 1e3,
+    outputs = None
+    if args.dump_outputs:
+        params = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+        outputs = {"last_loss": np.array([last]), "parameters": sample_rows(params, 1 << 22)}
+    return {"value": B * world * args.steps / wall, "ms_per_step": wall / args.steps * 1e3, "outputs": outputs,
             "config": {"workload": "cube3 cost-to-go network training step (nnet_utils.train_nnet: Adam, MSE, lr*lr_d^itr), "
                                    "batch %d per GPU, fp32, BatchNorm training mode, data resident in HBM" % B,
                        "batch_per_gpu": B, "last_loss": last, "parallelism": "DDP x%d (RCCL gradient all-reduce)" % world,
@@ -772,39 +834,49 @@ def run_expand(args, world, rank, onehot=None, steps=None, warmup=None):
     total_exp = reduce_ranks(float(n * steps), world, "sum")
     alg = 54 + 12 * 54 + 12 * 324 * esz  # 16 254 B (f32 one-hot) / 8 478 B (16-bit)
     achieved = alg * n / (kern_ms * 1e-3) / 1e9
-    # the store-only yardstick in the SAME process, on the same buffer, right after the kernel (the "96 % of
-    # the achievable write bandwidth" of round 1 compared numbers from two boxes): the kernel's output bytes written by
-    # k_write_ceiling — plain 16-byte stores, one contiguous MiB per workgroup, nothing gathered
-    ceil_bytes = out["onehot"].numel() * esz // 16 * 16
-    cev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(max(5, steps // 2))]
-    for i in range(2 + len(cev)):
-        if i >= 2:
-            cev[i - 2][0].record()
-        _lib.check(_lib.lib().dca_debug_write_ceiling(C.c_void_p(out["onehot"].data_ptr()), C.c_int64(ceil_bytes),
-                                                      C.c_int64(1 << 20), _lib.stream_ptr()), "dca_debug_write_ceiling")
-        if i >= 2:
-            cev[i - 2][1].record()
-    torch.cuda.synchronize()
-    ceil_ms = float(np.mean([a.elapsed_time(b) for a, b in cev]))
-    write_ceiling = ceil_bytes / (ceil_ms * 1e-3) / 1e9
+    outputs = None
+    if args.dump_outputs:
+        keep = sample_rows(torch.arange(n, device="cuda"), 1024)  # parents; every one of their 12 children is kept
+        rows = (keep[:, None] * 12 + torch.arange(12, device="cuda")).reshape(-1)
+        h = out["hash"][rows]
+        outputs = {"children": out["children"][keep], "onehot": out["onehot"][rows], "solved": out["solved"][rows],
+                   "hash_hi32": (h >> 32) & 0xFFFFFFFF, "hash_lo32": h & 0xFFFFFFFF}
+    roof = {"bound": "hbm", "kernel": "expand_fused_kernel<cube3,%s>" % onehot, "achieved": achieved,
+            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+            "traffic": expand_pmc_traffic(onehot, n),
+            "traffic_source": PMC_SOURCE.get("expand_fused_kernel<cube3,%s>" % onehot),
+            "bytes_per_launch": alg * n, "kernel_ms": kern_ms,
+            "timing": "HIP events around each of the %d launches on the launch stream" % steps}
+    if args.full:
+        # the store-only yardstick in the SAME process, on the same buffer, right after the kernel (the "96 % of
+        # the achievable write bandwidth" of round 1 compared numbers from two boxes): the kernel's output bytes written by
+        # k_write_ceiling — plain 16-byte stores, one contiguous MiB per workgroup, nothing gathered
+        ceil_bytes = out["onehot"].numel() * esz // 16 * 16
+        cev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(max(5, steps // 2))]
+        for i in range(2 + len(cev)):
+            if i >= 2:
+                cev[i - 2][0].record()
+            _lib.check(_lib.lib().dca_debug_write_ceiling(C.c_void_p(out["onehot"].data_ptr()), C.c_int64(ceil_bytes),
+                                                          C.c_int64(1 << 20), _lib.stream_ptr()), "dca_debug_write_ceiling")
+            if i >= 2:
+                cev[i - 2][1].record()
+        torch.cuda.synchronize()
+        ceil_ms = float(np.mean([a.elapsed_time(b) for a, b in cev]))
+        write_ceiling = ceil_bytes / (ceil_ms * 1e-3) / 1e9
+        roof.update(write_ceiling_GBs=write_ceiling, frac_of_write_ceiling=achieved / write_ceiling,
+                    write_ceiling_how="same process, same buffer, right after the timed launches: %d bytes (the kernel's "
+                                      "one-hot output) by plain 16-byte stores, one contiguous MiB per workgroup "
+                                      "(dca_debug_write_ceiling), %.3f ms per launch" % (ceil_bytes, ceil_ms))
     del out, S
     torch.cuda.empty_cache()
     return {
         "value": total_exp / wall,
         "ms_per_step": wall / steps * 1e3,
+        "outputs": outputs,
         "config": {"workload": "cube3 fused next_state+one-hot(%s)+is_solved+hash kernel, %d synthetic states "
                                "(BASELINE configs[1])" % (onehot, n), "states": n, "moves": 12,
                    "onehot": onehot, "parallelism": "replica-per-gpu x%d" % world},
-        "roofline": {"bound": "hbm", "kernel": "expand_fused_kernel<cube3,%s>" % onehot, "achieved": achieved,
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": expand_pmc_traffic(onehot, n),
-                     "traffic_source": PMC_SOURCE.get("expand_fused_kernel<cube3,%s>" % onehot),
-                     "bytes_per_launch": alg * n, "kernel_ms": kern_ms,
-                     "timing": "HIP events around each of the %d launches on the launch stream" % steps,
-                     "write_ceiling_GBs": write_ceiling, "frac_of_write_ceiling": achieved / write_ceiling,
-                     "write_ceiling_how": "same process, same buffer, right after the timed launches: %d bytes (the kernel's "
-                                          "one-hot output) by plain 16-byte stores, one contiguous MiB per workgroup "
-                                          "(dca_debug_write_ceiling), %.3f ms per launch" % (ceil_bytes, ceil_ms)},
+        "roofline": roof,
     }
 
 
@@ -892,6 +964,11 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--tune", default="", help="diagnostics: dca_debug_tune knobs, e.g. 6=1,3=16384 (A/B runs; not for the record)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: launch profile and rooflines, the one-hot, "
+                         "concurrent, expand_1M, sharded-queue and network-in-the-loop legs, CPU baselines, the write ceiling")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))  # one rank per GPU under torch.distributed.run
@@ -909,6 +986,8 @@ def main():
             _lib.check(_lib.lib().dca_debug_tune(int(k), int(v)), "dca_debug_tune")
     res = {"astar": run_astar, "expand": run_expand, "avi": run_avi, "train": run_train,
            "selftest": run_selftest}[args.workload](args, world, rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res["outputs"])
     line = {
         "metric": {"astar": "A* nodes expanded/sec on %s, batch 20k" % args.env, "expand": "A* nodes expanded/sec on cube3",
                    "avi": "AVI update-step training states generated/sec on %s" % args.env,
@@ -933,14 +1012,14 @@ def main():
               "expand_1M"):
         if k in res:
             line[k] = res[k]
-    if args.workload == "astar" and args.nnet_steps > 0:
+    if args.full and args.workload == "astar" and args.nnet_steps > 0:
         line["end_to_end_nnet"] = {"fp32": run_astar_nnet(args, world, rank, "fp32"),
                                    "bf16": run_astar_nnet(args, world, rank, "bf16", gemm16="hip"),
                                    "bf16_library_gemm": run_astar_nnet(args, world, rank, "bf16", gemm16="library"),
                                    "fp8_hand_written_gemm": run_astar_nnet(args, world, rank, "fp8"),
                                    "fp8_block_scaled": run_astar_nnet(args, world, rank, "fp8mx"),
                                    "fp32_eval_all_children": run_astar_nnet(args, world, rank, "fp32", True)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("astar", "expand"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("astar", "expand"):
         if args.workload == "expand":
             line["cpu_baseline"] = cpu_baseline_expand()
         elif args.env == "cube3":

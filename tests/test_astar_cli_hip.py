@@ -307,7 +307,7 @@ def test_bench_two_ranks_real_engine_over_gloo():
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "5", "--warmup",
-           "2", "--nnet-steps", "0", "--no-cpu-baseline", "--concurrent", "0", "--queue-states", "2", "--no-expand-block"]
+           "2", "--nnet-steps", "0", "--no-cpu-baseline", "--concurrent", "0", "--queue-states", "2", "--no-expand-block", "--full"]
     env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)

@@ -167,9 +167,35 @@ def test_train_nnet_matches_reference_run():
         last = nnet_utils.train_nnet(net, [g[tag + ":x"]], g[tag + ":y"], torch.device("cpu"), int(bs), int(itrs),
                                      int(itr0), float(lr), float(lr_d), display=False)
         assert abs(last - float(g[tag + ":last_loss"])) < 1e-5 * max(1.0, abs(last))
+        # The bias of a Linear layer that feeds a training-mode BatchNorm has an identically zero gradient (the batch mean
+        # is subtracted right after it), so what Adam sees there is the rounding noise of the backward pass, which depends
+        # on the CPU kernels torch dispatches to, and it normalises that noise into steps of up to ~lr.  Those biases, and
+        # the running means that average them in, are held to the bound that a zero true gradient implies; every other
+        # parameter and statistic must match the reference run.
+        T = int(itrs)
+        lrs = [float(lr) * float(lr_d) ** (int(itr0) + t) for t in range(T)]
+        b1, b2 = 0.9, 0.999  # torch.optim.Adam defaults, as in the reference's train_nnet
+        step = []  # Cauchy-Schwarz bound on |m_hat / sqrt(v_hat)| at step t: sqrt(sum_s w_s^2 / u_s)
+        for t in range(1, T + 1):
+            w = np.array([(1 - b1) * b1 ** (t - s) for s in range(1, t + 1)]) / (1 - b1 ** t)
+            u = np.array([(1 - b2) * b2 ** (t - s) for s in range(1, t + 1)]) / (1 - b2 ** t)
+            step.append(lrs[t - 1] * np.sqrt(np.sum(w * w / u)))
+        drift = 2 * np.concatenate([[0.0], np.cumsum(step)])  # |bias(ours) - bias(reference)| after t steps
+        mom = 0.1  # nn.BatchNorm1d momentum
+        rm_drift = sum(mom * (1 - mom) ** (T - t) * drift[t - 1] for t in range(1, T + 1))
+        dead = {}
+        if bn:
+            pairs = [("fc1", "bn1"), ("fc2", "bn2")] + [("blocks.%d.%d" % (b, 2 * j), "blocks.%d.%d" % (b, 2 * j + 1))
+                                                        for b in range(net.num_resnet_blocks) for j in range(2)]
+            for lin, bnm in pairs:
+                assert isinstance(net.get_submodule(bnm), torch.nn.BatchNorm1d)
+                dead[lin + ".bias"], dead[bnm + ".running_mean"] = drift[T], rm_drift
         for k, v in net.state_dict().items():
             want = g["%s:final:%s" % (tag, k)]
-            assert np.allclose(v.numpy(), want, rtol=1e-5, atol=1e-6), (tag, k)
+            if k in dead:
+                assert np.all(np.abs(v.numpy() - want) <= dead[k] + 1e-5 * np.abs(want) + 1e-6), (tag, k)
+            else:
+                assert np.allclose(v.numpy(), want, rtol=1e-5, atol=1e-6), (tag, k)
     with pytest.raises(ValueError):
         nnet_utils.train_nnet(net, [g["nobn:x"][:3]], g["nobn:y"][:3], torch.device("cpu"), 8, 1, 0, 0.1, 1.0, False)
 

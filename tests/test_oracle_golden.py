@@ -5,6 +5,7 @@ the cpp-semantics known answers are the rows of SURVEY.md Appendix A (outputs of
 reference binary recorded during the survey).  CPU only.
 """
 import hashlib
+import json
 import os
 
 import numpy as np
@@ -19,6 +20,13 @@ PUZZLES = [("puzzle15", 4), ("puzzle24", 5), ("puzzle35", 6), ("puzzle48", 7)]
 
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+@pytest.fixture(scope="module")
+def ref_envs():
+    """Digests of the reference's compiled environments on the seeded inputs below (make_golden_ref_envs.py)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_envs.json")) as f:
+        return json.load(f)
 
 
 # ------------------------------------------------------------------ tables
@@ -159,23 +167,21 @@ def test_npuzzle_known_answers(golden, name, n):
 
 
 # ------------------------------------------------------------------ reference C++ envs
-def test_reference_cpp_envs_agree(golden):
-    """oracle/_ref = the reference's cpp/environments.cpp compiled in place."""
-    if co.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
+def test_reference_cpp_envs_agree(golden, ref_envs):
+    """The reference's cpp/environments.cpp (compiled in place as oracle/_ref), recorded in tests/golden/ref_envs.json."""
     S = synth_states(256, 54, 11)
-    ch, sv = co.ref_expand("cube3", S)
     och, osv, _ = co.expand("cube3", S)
-    assert np.array_equal(ch, och) and np.array_equal(sv, osv)
+    assert [sha(och), sha(osv)] == ref_envs["cube3_synth256_seed11_expand"]
     for name, n in PUZZLES:
         P = synth_states(128, n * n, 12)
-        ch, sv = co.ref_expand(name, P)
         och, osv, _ = co.expand(name, P)
-        assert np.array_equal(ch, och) and np.array_equal(sv, osv)
+        assert [sha(och), sha(osv)] == ref_envs[name + "_synth128_seed12_expand"], name
         goal = np.concatenate((np.arange(1, n * n), [0])).astype(np.uint8)[None]
         # no-op moves at the goal (blank in the corner: U and L) leave it solved
-        assert np.array_equal(co.ref_expand(name, goal)[1], golden[name + "_goal_children_is_solved"])
-        assert co.ref_expand(name, goal)[1].tolist() == [True, False, True, False]
+        ref_goal = np.array(ref_envs[name + "_goal_expand_solved"], dtype=bool)
+        assert np.array_equal(ref_goal, golden[name + "_goal_children_is_solved"])
+        assert ref_goal.tolist() == [True, False, True, False]
+        assert np.array_equal(co.expand(name, goal)[1], ref_goal)
 
 
 # ------------------------------------------------------------------ one-hot / heuristics

@@ -61,7 +61,7 @@ def _ref_pickle(path, arrays):
 def test_bench_eight_ranks_share_one_gpu():
     """`bench.py --gpus 8 --dist-backend gloo`: eight ranks under torch.distributed.run on GPU 0, the real engine in each."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dist-backend", "gloo", "--steps", "5", "--warmup", "2",
-           "--nnet-steps", "0", "--no-cpu-baseline", "--concurrent", "0", "--queue-states", "4", "--no-expand-block"]
+           "--nnet-steps", "0", "--no-cpu-baseline", "--concurrent", "0", "--queue-states", "4", "--no-expand-block", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-12000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -5,7 +5,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 timeout -s KILL 1200 python -m pytest tests/test_gemm8_hip.py tests/test_parity_configs_hip.py tests/test_engine_hip.py tests/test_astar_cli_hip.py -m gpu -q -s --timeout 600 -p no:cacheprovider > $out/pytest_fixed.log 2>&1; echo "fixed rc=$?" | tee $out/summary.txt
 grep -E "seed 20|puzzle48 \|h\||deviation / max|passed|failed" $out/pytest_fixed.log | cut -c1-600 | tee -a $out/summary.txt
-B="python bench.py --steps 20 --warmup 5 --nnet-steps 0 --no-cpu-baseline --concurrent 0 --queue-states 0 --no-expand-block"
+B="python bench.py --full --steps 20 --warmup 5 --nnet-steps 0 --no-cpu-baseline --concurrent 0 --queue-states 0 --no-expand-block"
 for cfg in "14=0" "14=2,15=1" "14=2,15=2" "14=2,15=4" "14=2,15=8" "14=0"; do
   timeout -s KILL 300 $B --tune $cfg > $out/onehot_$cfg.json 2> $out/onehot_$cfg.err
   python - "$out/onehot_$cfg.json" "$cfg" <<'PY' | tee -a $out/summary.txt

@@ -5,7 +5,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 timeout -s KILL 600 python tools/gemm_bench.py 204800 f16x3 2>&1 | grep "^{" | tee $out/gemm_bench_f16x3.txt | cut -c1-700
 bash tools/gpu_round.sh r06f nobench
-timeout -s KILL 900 python bench.py --steps 20 --warmup 5 > $out/bench_contract.json 2> $out/bench_contract.err; echo "bench rc=$?" | tee -a $out/summary.txt
+timeout -s KILL 900 python bench.py --steps 20 --warmup 5 --full > $out/bench_contract.json 2> $out/bench_contract.err; echo "bench rc=$?" | tee -a $out/summary.txt
 python - <<'PY' | tee -a $out/summary.txt
 import json
 j=json.loads(open('gpurun_out/r06f/bench_contract.json').read().strip().splitlines()[-1])

@@ -4,8 +4,8 @@ out=gpurun_out/r06h
 mkdir -p $out
 export TMPDIR=/tmp
 bash tools/gpu_round.sh r06h nobench
-t0=$(date +%s); timeout -s KILL 900 python bench.py --steps 20 --warmup 5 > $out/bench_contract.json 2> $out/bench_contract.err; echo "bench contract rc=$? $(( $(date +%s) - t0 )) s" | tee -a $out/summary.txt
-t0=$(date +%s); timeout -s KILL 900 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench default rc=$? $(( $(date +%s) - t0 )) s" | tee -a $out/summary.txt
+t0=$(date +%s); timeout -s KILL 900 python bench.py --steps 20 --warmup 5 --full > $out/bench_contract.json 2> $out/bench_contract.err; echo "bench contract rc=$? $(( $(date +%s) - t0 )) s" | tee -a $out/summary.txt
+t0=$(date +%s); timeout -s KILL 900 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench default rc=$? $(( $(date +%s) - t0 )) s" | tee -a $out/summary.txt
 python - <<'PY' | tee -a $out/summary.txt
 import json
 for f in ("bench_contract", "bench_default"):

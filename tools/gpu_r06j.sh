@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 bash tools/gpu_round.sh ${1:-r06j} nobench
 for args in "--env puzzle48" "--workload avi --env puzzle48" "--workload avi --env puzzle48 --nnet_dtype bf16" "--workload avi --env puzzle15"; do
   f=$out/bench_$(echo $args | tr -d '-' | tr ' ' '_').json
-  t0=$(date +%s); timeout -s KILL 900 python bench.py $args > $f 2> ${f%.json}.err; echo "bench $args rc=$? $(( $(date +%s) - t0 )) s" | tee -a $out/summary.txt
+  t0=$(date +%s); timeout -s KILL 900 python bench.py --full $args > $f 2> ${f%.json}.err; echo "bench $args rc=$? $(( $(date +%s) - t0 )) s" | tee -a $out/summary.txt
   python - "$f" <<'PY' | tee -a $out/summary.txt
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -6,8 +6,8 @@ out=gpurun_out/r06w
 mkdir -p $out
 export TMPDIR=/tmp
 bash tools/gpu_round.sh r06w nobench
-t0=$(date +%s); timeout -s KILL 900 python bench.py --steps 20 --warmup 5 > $out/bench_contract.json 2> $out/bench_contract.err; echo "bench contract rc=$? $(( $(date +%s) - t0 )) s" | tee -a $out/summary.txt
-t0=$(date +%s); timeout -s KILL 900 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench default rc=$? $(( $(date +%s) - t0 )) s" | tee -a $out/summary.txt
+t0=$(date +%s); timeout -s KILL 900 python bench.py --steps 20 --warmup 5 --full > $out/bench_contract.json 2> $out/bench_contract.err; echo "bench contract rc=$? $(( $(date +%s) - t0 )) s" | tee -a $out/summary.txt
+t0=$(date +%s); timeout -s KILL 900 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench default rc=$? $(( $(date +%s) - t0 )) s" | tee -a $out/summary.txt
 python - <<'PY' | tee -a $out/summary.txt
 import json
 for f in ("bench_contract", "bench_default"):
@@ -20,7 +20,7 @@ timeout -s KILL 300 python tools/l1_embed_bench.py 2>&1 | grep -v amdgpu.ids | t
 timeout -s KILL 600 python tools/nnet_forward_probe.py 2>&1 | grep -v amdgpu.ids | tee $out/nnet_forward_probe.txt
 for args in "--env puzzle48" "--workload avi" "--workload avi --nnet_dtype bf16" "--workload avi --env puzzle48" "--workload avi --env puzzle48 --nnet_dtype bf16" "--workload avi --env puzzle15" "--workload train --steps 20 --warmup 5"; do
   f=$out/bench_$(echo $args | tr -d '-' | tr ' ' '_').json
-  timeout -s KILL 900 python bench.py $args > $f 2> ${f%.json}.err; echo "bench $args rc=$?" | tee -a $out/summary.txt
+  timeout -s KILL 900 python bench.py --full $args > $f 2> ${f%.json}.err; echo "bench $args rc=$?" | tee -a $out/summary.txt
   python - "$f" <<'PY' | tee -a $out/summary.txt
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 out=gpurun_out/r06zb
 mkdir -p $out
 for e in puzzle15 puzzle24 puzzle35; do
-  timeout -s KILL 200 python bench.py --env $e > $out/bench_$e.json 2> $out/bench_$e.err; echo "bench --env $e rc=$?"
+  timeout -s KILL 200 python bench.py --full --env $e > $out/bench_$e.json 2> $out/bench_$e.err; echo "bench --env $e rc=$?"
   python - "$out/bench_$e.json" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -18,7 +18,7 @@ timeout -s KILL 2400 python -m pytest tests -m gpu -q --timeout 900 -p no:cachep
 tail -n 60 "$out/pytest_rest.log" | tee -a "$out/summary.txt"
 if [ "${2:-bench}" = "bench" ]; then
   echo "== bench" | tee -a "$out/summary.txt"
-  timeout -s KILL 900 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench rc=$?" | tee -a "$out/summary.txt"
+  timeout -s KILL 900 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench rc=$?" | tee -a "$out/summary.txt"
   tail -c 6000 "$out/bench_default.json" | tee -a "$out/summary.txt"
   tail -n 15 "$out/bench_default.err" | tee -a "$out/summary.txt"
 fi
