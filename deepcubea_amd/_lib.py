@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdca_hip.so")
 
 ENV_CUBE3, ENV_NPUZZLE, ENV_LIGHTSOUT, ENV_CUBE4 = 0, 1, 2, 3
-DT_F32, DT_F16, DT_BF16, DT_F16X3, DT_F16_PLANES, DT_E4M3 = 0, 1, 2, 3, 4, 5
+DT_F32, DT_F16, DT_BF16, DT_F16X3, DT_F16_PLANES, DT_E4M3, DT_F64 = 0, 1, 2, 3, 4, 5, 6
 E4M3 = torch.float8_e4m3fn  # OCP e4m3: the fp8 format of gfx950's matrix pipes
 SEM_PY, SEM_CPP = 0, 1
 HEUR_MOD97, HEUR_KNUTH3, HEUR_HASHU01, HEUR_ZERO, HEUR_MANHATTAN = 0, 1, 2, 3, 4
@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "dca_engine_set_weight_instance", "dca_engine_set_weights", "dca_engine_park_instance", "dca_engine_last_popped",
     "dca_engine_reset_many", "dca_engine_root_commit_many", "dca_engine_set_weights_dev", "dca_debug_write_ceiling",
     "dca_l1_supported8", "dca_l1_kpad8", "dca_l1_onehot_gemm8", "dca_l1_embed_supported", "dca_l1_embed",
+    "dca_gemm64", "dca_l1_embed64", "dca_head_gemv64",
 ]
 
 
@@ -640,18 +641,59 @@ def quant_e4m3(x: torch.Tensor, scale: float) -> torch.Tensor:
     return out
 
 
-def head_gemv(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    """Output layer (dca_head_gemv): x [m, k] fp32 / fp16 / bf16 (rows may be strided), w [n_out, k] fp32, bias [n_out] fp32
-    -> [m, n_out] fp32, summed in a fixed order (a row's bits do not depend on m or on the row's position)."""
-    assert x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in _TORCH_DT
+def head_gemv(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Output layer (dca_head_gemv): x [m, k] fp32 / fp16 / bf16 / float64 (rows may be strided), w [n_out, k] fp32, bias [n_out] fp32
+    -> [m, n_out] fp32, summed in float64 in a fixed order (a row's bits do not depend on m or on the row's position) and rounded
+    once.  out_dtype=torch.float64 (float64 rows only, dca_head_gemv64): the same sum, not rounded."""
+    dts = {**_TORCH_DT, torch.float64: DT_F64}
+    assert x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in dts
     assert w.dtype == torch.float32 and w.is_contiguous() and w.shape[1] == x.shape[1]
     assert bias is None or (bias.dtype == torch.float32 and bias.numel() == w.shape[0])
+    assert out_dtype == torch.float32 or (out_dtype == torch.float64 and x.dtype == torch.float64)
     m, k = x.shape
-    out = torch.empty((m, w.shape[0]), dtype=torch.float32, device=x.device)
+    out = torch.empty((m, w.shape[0]), dtype=out_dtype, device=x.device)
     if m == 0:
         return out
-    check(lib().dca_head_gemv(C.c_void_p(x.data_ptr()), _TORCH_DT[x.dtype], C.c_int64(m), int(k), C.c_int64(x.stride(0)), ptr(w),
+    if out_dtype == torch.float64:
+        check(lib().dca_head_gemv64(C.c_void_p(x.data_ptr()), C.c_int64(m), int(k), C.c_int64(x.stride(0)), ptr(w), ptr(bias),
+                                    int(w.shape[0]), ptr(out), stream_ptr()), "dca_head_gemv64")
+        return out
+    check(lib().dca_head_gemv(C.c_void_p(x.data_ptr()), dts[x.dtype], C.c_int64(m), int(k), C.c_int64(x.stride(0)), ptr(w),
                               ptr(bias), int(w.shape[0]), ptr(out), stream_ptr()), "dca_head_gemv")
+    return out
+
+
+def gemm64(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], skip: Optional[torch.Tensor], relu: bool,
+           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One dense layer of the fp64 mode (dca_gemm64): relu?(a . w^T + bias (+ skip)), a [m, k] / w [n, k] / bias [n] / skip [m, n]
+    float64, f64 MFMA, every element summed over k in ascending order.  `out` may be `skip` (in place)."""
+    assert a.dtype == torch.float64 and w.dtype == torch.float64 and a.is_contiguous() and w.is_contiguous()
+    m, k = a.shape
+    n = w.shape[0]
+    assert w.shape[1] == k and (bias is None or (bias.dtype == torch.float64 and bias.numel() == n and bias.is_contiguous()))
+    assert skip is None or (skip.dtype == torch.float64 and skip.shape == (m, n) and skip.is_contiguous())
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float64, device=a.device)
+    assert out.dtype == torch.float64 and out.shape == (m, n) and out.is_contiguous() and out.data_ptr() != a.data_ptr()
+    assert skip is None or skip.data_ptr() == out.data_ptr() or skip.data_ptr() != a.data_ptr()
+    check(lib().dca_gemm64(ptr(a), C.c_int64(m), int(k), C.c_int64(k), ptr(w), int(n), C.c_int64(k), ptr(bias), ptr(skip), int(relu),
+                           ptr(out), C.c_int64(n), stream_ptr()), "dca_gemm64")
+    return out
+
+
+def l1_embed64(states_nnet: torch.Tensor, depth: int, w_t: torch.Tensor, bias: torch.Tensor, relu: bool) -> torch.Tensor:
+    """Layer 1 of the fp64 mode as an embedding sum (dca_l1_embed64): relu?(b1 + sum_pos w_t[pos * depth + s[pos]]) in float64
+    (bias first, positions ascending) from the uint8 rows; w_t = W1^T float64 [state_dim * depth, n_pad] -> [m, n_pad] float64."""
+    x = _u8(states_nnet)
+    m, d = x.shape
+    n_pad = bias.numel()
+    assert w_t.dtype == torch.float64 and bias.dtype == torch.float64 and w_t.is_contiguous() and bias.is_contiguous()
+    assert tuple(w_t.shape) == (d * depth, n_pad)
+    out = torch.empty((m, n_pad), dtype=torch.float64, device=x.device)
+    if m == 0:
+        return out
+    check(lib().dca_l1_embed64(ptr(x), C.c_int64(m), int(d), int(depth), ptr(w_t), C.c_int64(n_pad), ptr(bias), int(relu), ptr(out),
+                               stream_ptr()), "dca_l1_embed64")
     return out
 
 

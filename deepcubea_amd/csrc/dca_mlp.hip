@@ -545,12 +545,17 @@ __device__ __forceinline__ float4 head_load4<uint16_t>(const uint16_t* p) {  // 
     return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xFFFF0000u), __uint_as_float(v.y << 16),
                        __uint_as_float(v.y & 0xFFFF0000u));
 }
+// float64 rows (the fp64 mode): loaded as they are — the accumulation below is in float64 already
+__device__ __forceinline__ double4 head_load4(const double* p) {
+    const double2 u = *reinterpret_cast<const double2*>(p), v = *reinterpret_cast<const double2*>(p + 2);
+    return make_double4(u.x, u.y, v.x, v.y);
+}
 
 constexpr int kHeadMaxOut = 8;
-template <typename XT>
+template <typename XT, typename OT = float>
 __global__ __launch_bounds__(256) void k_head_gemv(const XT* __restrict__ x, int64_t m, int k, int64_t ldx,
                                                    const float* __restrict__ w /*[n_out, k]*/, const float* __restrict__ b,
-                                                   int n_out, float* __restrict__ out /*[m, n_out]*/) {
+                                                   int n_out, OT* __restrict__ out /*[m, n_out]*/) {
     extern __shared__ __attribute__((aligned(16))) uint8_t head_lds[];
     float* lw = reinterpret_cast<float*>(head_lds);  // the weights, once per workgroup
     for (int i = threadIdx.x; i < n_out * k; i += 256) lw[i] = w[i];
@@ -563,7 +568,7 @@ __global__ __launch_bounds__(256) void k_head_gemv(const XT* __restrict__ x, int
 #pragma unroll
         for (int o = 0; o < kHeadMaxOut; o++) acc[o] = 0.0;
         for (int c = lane; c < nch; c += 64) {
-            const float4 v = head_load4<XT>(row + 4 * c);
+            const auto v = head_load4(row + 4 * c);
 #pragma unroll
             for (int o = 0; o < kHeadMaxOut; o++) {
                 if (o < n_out) {
@@ -580,7 +585,7 @@ __global__ __launch_bounds__(256) void k_head_gemv(const XT* __restrict__ x, int
             if (o < n_out) {
                 double s = acc[o];
                 for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);  // every lane ends with the same bits
-                if (lane == 0) out[r * n_out + o] = (float)(s + (b ? (double)b[o] : 0.0));
+                if (lane == 0) out[r * n_out + o] = (OT)(s + (b ? (double)b[o] : 0.0));
             }
         }
     }
@@ -656,9 +661,9 @@ int dca_act_split(const float* y, const float* bias, const float* skip, const fl
 int dca_head_gemv(const void* x, int x_dtype, int64_t m, int k, int64_t ldx, const float* w, const float* bias, int n_out,
                   float* out, void* stream) {
     DCA_ARG(x && w && out && m >= 0 && k >= 4 && k % 4 == 0 && ldx >= k && n_out >= 1 && n_out <= kHeadMaxOut);
-    DCA_ARG(x_dtype == DCA_DT_F32 || x_dtype == DCA_DT_F16 || x_dtype == DCA_DT_BF16);
+    DCA_ARG(x_dtype == DCA_DT_F32 || x_dtype == DCA_DT_F16 || x_dtype == DCA_DT_BF16 || x_dtype == DCA_DT_F64);
     DCA_ARG((size_t)n_out * (size_t)k * sizeof(float) <= 64 * 1024);
-    DCA_ARG((uintptr_t)x % (x_dtype == DCA_DT_F32 ? 16 : 8) == 0 && ldx % 4 == 0 && (uintptr_t)w % 16 == 0);
+    DCA_ARG((uintptr_t)x % (x_dtype == DCA_DT_F32 || x_dtype == DCA_DT_F64 ? 16 : 8) == 0 && ldx % 4 == 0 && (uintptr_t)w % 16 == 0);
     if (m == 0) return 0;
     int64_t blocks = (m + 3) / 4;
     if (blocks > 8192) blocks = 8192;
@@ -667,6 +672,9 @@ int dca_head_gemv(const void* x, int x_dtype, int64_t m, int k, int64_t ldx, con
     if (x_dtype == DCA_DT_F32)
         hipLaunchKernelGGL(k_head_gemv<float>, dim3((unsigned)blocks), dim3(256), lds, s, reinterpret_cast<const float*>(x), m, k,
                            ldx, w, bias, n_out, out);
+    else if (x_dtype == DCA_DT_F64)
+        hipLaunchKernelGGL(k_head_gemv<double>, dim3((unsigned)blocks), dim3(256), lds, s, reinterpret_cast<const double*>(x), m, k,
+                           ldx, w, bias, n_out, out);
     else if (x_dtype == DCA_DT_F16)
         hipLaunchKernelGGL(k_head_gemv<_Float16>, dim3((unsigned)blocks), dim3(256), lds, s,
                            reinterpret_cast<const _Float16*>(x), m, k, ldx, w, bias, n_out, out);
@@ -674,6 +682,20 @@ int dca_head_gemv(const void* x, int x_dtype, int64_t m, int k, int64_t ldx, con
         hipLaunchKernelGGL(k_head_gemv<uint16_t>, dim3((unsigned)blocks), dim3(256), lds, s,
                            reinterpret_cast<const uint16_t*>(x), m, k, ldx, w, bias, n_out, out);
     return launch_check("k_head_gemv");
+}
+
+int dca_head_gemv64(const double* x, int64_t m, int k, int64_t ldx, const float* w, const float* bias, int n_out, double* out,
+                    void* stream) {
+    DCA_ARG(x && w && out && m >= 0 && k >= 4 && k % 4 == 0 && ldx >= k && n_out >= 1 && n_out <= kHeadMaxOut);
+    DCA_ARG((size_t)n_out * (size_t)k * sizeof(float) <= 64 * 1024);
+    DCA_ARG((uintptr_t)x % 16 == 0 && ldx % 4 == 0 && (uintptr_t)w % 16 == 0);
+    if (m == 0) return 0;
+    int64_t blocks = (m + 3) / 4;
+    if (blocks > 8192) blocks = 8192;
+    const size_t lds = (size_t)n_out * (size_t)k * sizeof(float);
+    auto kern = k_head_gemv<double, double>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, x, m, k, ldx, w, bias, n_out, out);
+    return launch_check("k_head_gemv64");
 }
 
 }  // extern "C"

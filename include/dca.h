@@ -60,6 +60,7 @@ extern "C" {
 #define DCA_DT_F16_PLANES 4 /* dca_l1_onehot_gemm only: dca_f16x3_gemm's operand — [m, n_pad] fp16 high halves, then [m, n_pad] low halves */
 #define DCA_DT_E4M3 5 /* dca_l1_onehot_gemm only: OCP fp8 e4m3 bytes, saturating (dca_gemm8's operand; the caller folds the activation
                          scale into the layer's weights and bias) */
+#define DCA_DT_F64 6  /* dca_head_gemv only: float64 rows (the fp64 mode's residual stream) */
 
 /* BWAS semantics: which reference implementation is reproduced */
 #define DCA_SEM_PY 0  /* search_methods/astar.py: f64 cost, FIFO ties, CLOSED starts empty */
@@ -455,9 +456,27 @@ int dca_fill_inv_pow2(float* out, int64_t n, const uint32_t* amax_bits, void* st
  * environment of the reference): out[m, n_out] = x[m, k] . w[n_out, k]^T + bias, float64 accumulation in a FIXED order (one wave
  * per row, lane-strided FMA chains, xor-butterfly fold, one rounding to fp32): a row's value does not depend on its position, on m or on the launch
  * — the library GEMV this replaces chose its kernel (and summation order) from m.  x: DCA_DT_F32 / F16 / BF16 rows (row
- * stride ldx elements, k % 4 == 0, ldx % 4 == 0); w, bias, out fp32; n_out <= 8. */
+ * stride ldx elements, k % 4 == 0, ldx % 4 == 0); w, bias, out fp32; n_out <= 8.  DCA_DT_F64 rows (16-byte aligned): the float64
+ * sum is rounded to fp32 once, after the bias.  dca_head_gemv64: the same sum over float64 rows, left in float64 (out [m, n_out]). */
 int dca_head_gemv(const void* x, int x_dtype, int64_t m, int k, int64_t ldx, const float* w /*[n_out, k]*/,
                   const float* bias /*[n_out] or NULL*/, int n_out, float* out /*[m, n_out]*/, void* stream);
+int dca_head_gemv64(const double* x, int64_t m, int k, int64_t ldx, const float* w /*[n_out, k]*/, const float* bias /*[n_out] or NULL*/,
+                    int n_out, double* out /*[m, n_out]*/, void* stream);
+
+/* The float64 heuristic mode (`--nnet_dtype fp64`; csrc/dca_gemm64.hip): utils/pytorch_models.py:49-86 (BatchNorm folded in
+ * float64) evaluated in float64 from the fp32 weights, rounded once to fp32 by dca_head_gemv (DCA_DT_F64).
+ * dca_gemm64: one dense layer, out[m, n] (row stride ldo) = relu?( a[m, k] . w[n, k]^T + bias[n] (+ skip[m, n]) ), float64
+ * throughout, on v_mfma_f64_16x16x4_f64; every output element summed over k in ascending order by one lane (no split-K), so a
+ * row's value does not depend on m or on its position.  k % 2 == 0, lda / ldw even, a and w 16-byte aligned; bias may be NULL;
+ * skip has out's row stride and may be `out` itself (the residual form), never `a`.
+ * dca_l1_embed64: layer 1 as an embedding sum in float64 (one gathered weight per position, as dca_l1_embed):
+ *   out[r, j] = relu?( bias[j] + sum_pos w_t[pos * depth + s[r, pos]][j] )           (bias first, positions ascending)
+ * w_t = W1^T float64 [state_dim * depth][n_pad] (n_pad % 8 == 0), bias [n_pad], out [m, n_pad].  Any geometry whose table fits
+ * LDS in 8 columns (160 KB: puzzle48's 2401 rows fit, so every environment of the product).  State bytes must be < depth. */
+int dca_gemm64(const double* a, int64_t m, int k, int64_t lda, const double* w, int n, int64_t ldw, const double* bias /*[n] or NULL*/,
+               const double* skip /*[m, ldo] or NULL*/, int relu, double* out, int64_t ldo, void* stream);
+int dca_l1_embed64(const uint8_t* nnet_in /*[m, state_dim]*/, int64_t m, int state_dim, int depth, const double* w_t, int64_t n_pad,
+                   const double* bias /*[n_pad]*/, int relu, double* out /*[m, n_pad]*/, void* stream);
 
 #ifdef __cplusplus
 }
