@@ -58,8 +58,8 @@ constexpr int kSub = 2048;            // sub-bins of k_rank's per-bin bucketing
 constexpr int kScanBlocks = 256;      // grid of the OPEN scans: few fat blocks (cheap when they early-exit)
 constexpr int kCollectBlocks = 512;   // k_sel_collect: two workgroups per CU keep twice the loads in flight
 constexpr int kRankBlocks = 256;      // k_rank: one 512-thread workgroup per CU, the work units strided over them
-constexpr int kTinyBinDefault = 512;  // bins up to this size are ranked one THREAD per entry (all-pairs inside the bin): a bin of its
-                                      // own workgroup costs a chain of ~6 memory trips however small it is (g_tune[9] overrides)
+constexpr uint32_t kTinyBin = 512;    // bins up to this size are ranked one THREAD per entry (all-pairs inside the bin): a bin of its
+                                      // own workgroup costs a chain of ~6 memory trips however small it is
 constexpr int kSortCap = 8192;        // diagnostics only: bins beyond this many entries are counted as "giant"
 constexpr int RT = 512;                            // threads of a k_rank workgroup (8 waves: up to 256 VGPRs each)
 constexpr int kRegEnt = 16;                        // entries a thread keeps in registers
@@ -70,7 +70,7 @@ constexpr int kStash = 2560;          // per-workgroup LDS stash of k_sel_collec
 // place, the part that is certainly in the batch (segment bstar) and the last refinement level's sub-bins up to the one
 // holding the batch's last entry (segments bstar+1 ...).
 constexpr int kSegs = NBIN + 1 + kSub;
-constexpr uint32_t kGiantBinDefault = 8192;   // = kLdsEnt: larger threshold bins are refined by the grid, not by one workgroup
+constexpr uint32_t kGiantBin = 8192;          // = kLdsEnt: larger threshold bins are refined by the grid, not by one workgroup
 constexpr int kMaxLevels = 9;                 // 96 composite bits / 11 bits per level
 constexpr unsigned long long kBarrierTimeout = 200000000ull;  // 2 s of the 100 MHz wall clock: a stuck grid barrier fails the search
 // The FIRST barrier of a giant iteration doubles as the residency check: nothing of the search has been modified before it, so
@@ -186,13 +186,15 @@ __device__ __forceinline__ bool pair_less(uint64_t ka, uint32_t ia, uint64_t kb,
 
 // launch slots of the device-side profile (dca_engine_profile_builtin)
 enum {
-    P_REFILL_HIST = 0, P_REFILL_SCAN, P_REFILL_MOVE, P_SEL_HIST, P_SEL_SCAN, P_SEL_COLLECT, P_RANK, P_EXPAND, P_PROBE,
+    P_REFILL_HIST = 0, P_REFILL_SCAN, P_REFILL_MOVE, P_SEL_HIST, P_SEL_SCAN, P_SEL_COLLECT, P_RANK, P_EXPAND,
+    P_PROBE,  // unused: the probe runs inside k_expand (the slot stays, so that the slot numbers of the profile do not move)
     P_DECIDE, P_PACK, P_COMMIT, P_RANK_SMALL, P_RANK_BIG, P_RB_LOAD, P_RB_COUNT, P_RB_SCATTER, P_RB_ORDER, P_COUNT
 };
 constexpr int kProfSlots = 1024;
-// diagnostics: knobs a tuning run can flip without a rebuild (dca_debug_tune); 0 = the shipped behaviour
-__device__ int g_tune[16];
-#define kTinyBin ((uint32_t)(g_tune[9] > 0 ? g_tune[9] : kTinyBinDefault))
+// test hooks of dca_debug_tune (0 = the shipped behaviour): knob 2 lowers the mark at which BACK is squeezed without a refill,
+// knob 10 makes the first grid barrier of every giant iteration give up at once
+__device__ int g_back_squeeze_mark;
+__device__ int g_first_barrier_gives_up;
 // workgroups of k_rank that share one large bin (each reads and counts all of it, then scatters / orders / emits its own run of
 // sub-bins): one per 1024 entries, at most 8 — the callers clamp.  (One per 512 or 256 entries — 3 to 6 workgroups on the
 // 1250-1950-entry threshold bin instead of 2 — changes nothing: the bin's workgroups spend their time in the chain load ->
@@ -236,7 +238,6 @@ struct Eng {
                          // entries, one unit per workgroup that shares the segment (segment | share << 16 | shares << 20)
     uint64_t* pop_key;   // the batch in pop order
     uint32_t *pop_id, *pop_g;
-    uint64_t* child_hash;
     uint32_t *child_slot, *child_next, *child_v0;
     uint8_t *child_flags, *child_multi;
     float* child_h;
@@ -695,8 +696,9 @@ __global__ __launch_bounds__(1024) void k_refill_scan(const Eng* __restrict__ en
             // tombstones stay: when the buffer nears its physical end, squeeze them out now (a compaction-only pass of
             // k_refill_move) instead of failing a search whose OPEN would fit.
             const uint32_t b = c->cur_b, phys = c->open_n[b].v, dead = c->back_dead.v;
-            // (g_tune[2]: test hook — squeeze once BACK holds more than max_nodes * v / 1024 physical entries)
-            const uint32_t mark = g_tune[2] > 0 ? (uint32_t)(((uint64_t)E.max_nodes * (uint32_t)g_tune[2]) >> 10) : (E.max_nodes / 8) * 7;
+            // (g_back_squeeze_mark: test hook — squeeze once BACK holds more than max_nodes * v / 1024 physical entries)
+            const uint32_t mark = g_back_squeeze_mark > 0 ? (uint32_t)(((uint64_t)E.max_nodes * (uint32_t)g_back_squeeze_mark) >> 10)
+                                                          : (E.max_nodes / 8) * 7;
             const bool squeeze = dead != 0 && phys > mark;
             c->refill = squeeze ? 1u : 0u;
             c->compact = squeeze ? 1u : 0u;
@@ -998,8 +1000,7 @@ __global__ __launch_bounds__(1024) void k_sel_scan(const Eng* __restrict__ engs,
     // A threshold bin too large for k_rank's LDS bucketing (massive cost ties: an integer-valued heuristic makes every
     // f-level one tie group of up to millions of entries) is not handed to k_rank whole: k_sel_collect refines it across
     // the grid first ("giant" iteration) and k_rank only sees the few thousand entries around the batch's end.
-    const uint32_t giant_limit = g_tune[3] > 0 ? (uint32_t)g_tune[3] : kGiantBinDefault;
-    const bool giant = E.coop && !*E.coop_off && want != 0 && pre[s_bstar + 1] - pre[s_bstar] > giant_limit;
+    const bool giant = E.coop && !*E.coop_off && want != 0 && pre[s_bstar + 1] - pre[s_bstar] > kGiantBin;
     if (giant)
         for (int i = t; i < kMaxLevels * kSub; i += 1024) E.subhist[i] = 0;
     for (int k = 0; k < kBinsPerThread; k++) {
@@ -1179,8 +1180,8 @@ __device__ __forceinline__ int collect_grid_barrier(const Eng& E, Ctl* c, Collec
         uint32_t v = __hip_atomic_fetch_add(&c->gbar.v, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
         int res = BAR_PASS;
         const unsigned long long t0 = wall_clock64();
-        // (knob 10: the first barrier gives up at once — what a launch that is not fully resident does after 0.25 s; tests)
-        const unsigned long long limit = first ? (g_tune[10] ? 0ull : kBarrierTimeoutFirst) : kBarrierTimeout;
+        // (g_first_barrier_gives_up: what a launch that is not fully resident does after 0.25 s; tests)
+        const unsigned long long limit = first ? (g_first_barrier_gives_up ? 0ull : kBarrierTimeoutFirst) : kBarrierTimeout;
         for (;;) {
             if (v & GBAR_BROKEN) {
                 res = first ? BAR_BROKEN : BAR_FAIL;
@@ -1296,7 +1297,6 @@ __device__ __noinline__ int collect_giant(const Eng& E, Ctl* c, CollectLds& L, c
     u128 V0 = ((u128)gkmin << 32) + (u128)gimin;
     u128 span = ((u128)(gkmax - gkmin) << 32) + (u128)(gimax - gimin);  // (upper bound: ids of the top key are <= imax)
     uint32_t need = want - pre_b, below = 0, shc = 0, tsub = 0;
-    const uint32_t giant_limit = g_tune[3] > 0 ? (uint32_t)g_tune[3] : kGiantBinDefault;
     uint32_t* lh = reinterpret_cast<uint32_t*>(L.u.g.st_key);  // (the stash is idle until the collection pass)
     uint32_t* subpre = L.u.g.subpre;
     for (int lvl = 0;; lvl++) {
@@ -1359,7 +1359,7 @@ __device__ __noinline__ int collect_giant(const Eng& E, Ctl* c, CollectLds& L, c
             return BAR_FAIL;
         }
         const uint32_t cn = subpre[tsub + 1] - subpre[tsub];
-        if (cn <= giant_limit || shc == 0 || lvl + 1 >= kMaxLevels) break;
+        if (cn <= kGiantBin || shc == 0 || lvl + 1 >= kMaxLevels) break;
         // descend into the threshold sub-bin: everything below it is certainly in the batch
         below += subpre[tsub];
         need -= subpre[tsub];
@@ -1569,8 +1569,7 @@ __global__ __launch_bounds__(256) void k_sel_collect(const Eng* __restrict__ eng
         P.bstar = L.bstar;
         P.pre_b = L.pre[P.bstar];
         P.cn_star = L.pre[P.bstar + 1] - P.pre_b;
-        const uint32_t giant_limit = g_tune[3] > 0 ? (uint32_t)g_tune[3] : kGiantBinDefault;
-        P.giant = E.coop && !*E.coop_off && P.cn_star > giant_limit;
+        P.giant = E.coop && !*E.coop_off && P.cn_star > kGiantBin;
         if (blockIdx.x == 0) {
             // the record k_rank (and the rest of the iteration) reads — what k_sel_scan writes in a rebase iteration
             for (uint32_t i = t; i <= (uint32_t)NBIN; i += 256) E.pre[i] = L.pre[i];
@@ -1760,8 +1759,7 @@ __global__ __launch_bounds__(256) void k_sel_collect(const Eng* __restrict__ eng
 
 constexpr int kRankStack = 512;    // pending oversized sub-bins of one bin
 constexpr uint32_t kDirectMax = 512;  // items up to this size are ranked all-pairs out of LDS
-constexpr uint32_t kSubMaxDefault = 512;  // sub-bins up to this size are ranked in place, larger ones are refined again
-#define kSubMax ((uint32_t)(g_tune[1] ? g_tune[1] : (int)kSubMaxDefault))
+constexpr uint32_t kSubMax = 512;     // sub-bins up to this size are ranked in place, larger ones are refined again
 
 struct RankItem {
     uint32_t off, n, need, src;  // slice [off, off+n) of scratch array `src` (0 tmp, 1 ord); pop rank of its first entry = off
@@ -2083,10 +2081,7 @@ __device__ __noinline__ void rank_item(const Eng& E, Ctl* c, RankShared& S, uint
     }
     uint32_t lg = 0;
     while ((8u << lg) <= n && lg < 11) lg++;  // 2^lg <= n / 4, at most kSub sub-bins
-    {  // one step finer than n / 4 (shorter ranking loops), tunable for experiments
-        const uint32_t lgx = lg + 1u + (uint32_t)g_tune[0];
-        lg = lgx < 11u ? lgx : 11u;
-    }
+    if (lg < 11) lg++;                         // one step finer than n / 4: shorter ranking loops
     if (n <= kLdsEnt) {
         // ---- the item is read from HBM ONCE (kRegEnt entries per thread, kept in registers), bucketed and ranked in LDS.
         // Inside the item an entry is held as a 64-bit offset — key minus the item's smallest key; or, when all keys of
@@ -2493,13 +2488,13 @@ __device__ __forceinline__ uint32_t child_word_from_parent(uint32_t pw, uint32_t
 }
 
 constexpr int kEngTile = 16;  // parents per workgroup: a 20 000-parent batch then fills the chip (1250 workgroups)
-// PROBE: the CLOSED probe of the batch's children (what k_probe does in a launch of its own) runs here, from the rows the
-// tile holds in LDS — one launch, one boundary and one 13 MB re-read of the child rows less per iteration.  The one thing
-// k_probe could rely on and this kernel cannot: a representative inserted by ANOTHER workgroup of the same launch has no
-// row in HBM yet.  It needs none: its id says which popped parent and which move made it (id = base + rank * A + move),
-// and the parent's row was written an iteration ago — the tile rebuilds the representative from it (16 lanes per pending
-// comparison) and compares exactly.
-template <int ENV, int DIM, int OH, bool PROBE>
+// The CLOSED probe of the batch's children (first half of the dedup: find-or-insert every child's slot, verify it against the
+// representative's row, chain the child to the slot) runs here, from the rows the tile holds in LDS — one launch, one boundary
+// and one 13 MB re-read of the child rows less per iteration than a launch of its own.  A representative inserted by ANOTHER
+// workgroup of the same launch has no row in HBM yet.  It needs none: its id says which popped parent and which move made it
+// (id = base + rank * A + move), and the parent's row was written an iteration ago — the tile rebuilds the representative
+// from it (16 lanes per pending comparison) and compares exactly.
+template <int ENV, int DIM, int OH>
 __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ engs, int heur_id, int write_nn) {
     const Eng& E = engs[blockIdx.y];
     using EV = EnvT<ENV, DIM>;
@@ -2515,7 +2510,7 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
     uint8_t* ltab = smem + TL::PAR_BYTES;
     uint8_t* lst = smem + TL::LDS_BYTES;  // child rows of the tile, laid out exactly like their HBM destination
     __shared__ uint32_t l_pid[TP], l_g[TP];
-    __shared__ uint32_t l_qn, l_qcc[PROBE ? kThreads : 1], l_qrep[PROBE ? kThreads : 1], l_qres[PROBE ? kThreads : 1];
+    __shared__ uint32_t l_qn, l_qcc[kThreads], l_qrep[kThreads], l_qres[kThreads];
     __shared__ uint32_t l_ohq;  // one-hot rows: next 1 KiB piece (one wave-wide 16-byte store) nobody has claimed yet
     static_assert((EV::D + 3) / 4 < 16, "no spare lane per row for the parent's path cost");
     // batch geometry: every workgroup derives it from the state the previous iteration left (S[iters & 1]) and the
@@ -2672,12 +2667,12 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
 
     // per child: hash, is_solved, node fields, built-in heuristic (rounds of 256 children; uniform: the probe below
     // synchronises the workgroup inside a round)
-    if (PROBE && threadIdx.x == 0) l_qn = 0;
+    if (threadIdx.x == 0) l_qn = 0;
     for (uint32_t cc0 = 0; cc0 < nchild; cc0 += kThreads) {
         const uint32_t cc = cc0 + threadIdx.x;
         const bool cvalid = cc < nchild;
         uint64_t h = 0;
-        uint64_t roww[(EV::D + 7) / 8];  // the child's row, 8 bytes a word (PROBE: compared against representatives' rows)
+        uint64_t roww[(EV::D + 7) / 8];  // the child's row, 8 bytes a word (compared against representatives' rows)
         if (cvalid) {
         uint32_t r = cc / EV::A, a = cc - r * EV::A;
         uint64_t sum = 0;
@@ -2716,19 +2711,16 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
         const uint32_t j = j0 + cc, id = base + j, pid = l_pid[r];
         const uint32_t gp = l_g[r];
         if (a == 0) E.pop_g[r0 + r] = gp;  // the parents' path costs in pop order: what the dedup / push kernels read
-        if constexpr (!PROBE) {
-            E.child_hash[j] = h;
-            E.child_multi[j] = 0;  // (PROBE: the marks are cleared by k_commit after it has read them — another workgroup of this
-                                   // launch may set this child's mark before or after this point)
-        }
+        // (the chain marks child_multi are cleared by k_commit after it has read them, not here: another workgroup of this
+        // launch may set this child's mark before or after this point)
         E.g[id] = (int32_t)(gp + 1u);  // path cost + unit transition cost (astar.py:125-126 / cpp:219)
         E.parent[id] = pid;
         E.move[id] = (uint8_t)a;
         E.solved[id] = ok ? 1 : 0;
         if (heur_id >= 0) E.child_h[j] = heur_from(heur_id, sum, h, manh);
         }
-        if constexpr (PROBE) {
-            // ---- find-or-insert the CLOSED slot of this round's children (k_probe's loop, rows taken from LDS)
+        {
+            // ---- find-or-insert the CLOSED slot of this round's children (rows taken from LDS)
             constexpr int NWD = (EV::D + 3) / 4;
             const uint32_t j = j0 + cc, id = base + j;
             const uint64_t tag = h >> 32;
@@ -2738,10 +2730,14 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
             for (;;) {
                 if (active && !paused) {
                     for (;;) {
-                        // look first, claim second; one 16-byte load fetches the entry with its value (see k_probe)
+                        // look first, claim second (a compare-and-swap on every probed slot — one round trip instead of two
+                        // for a new state — was measured and lost badly: 61 us vs 26 us for the probe of a batch; returning
+                        // atomics are that much dearer here).  ONE 16-byte load fetches the slot's entry together with its value: entries never
+                        // change once written and values only change in k_commit, so a line cached by an earlier reader on
+                        // this CU is either current or shows an EMPTY entry that the compare-and-swap then corrects.
                         const uint4 sl = *reinterpret_cast<const uint4*>(&E.tab[slot]);
                         uint64_t e = ((uint64_t)sl.y << 32) | sl.x;
-                        v0 = sl.z;
+                        v0 = sl.z;  // the slot's value before this batch (GINF while nothing was recorded)
                         if (e == EMPTY) {
                             const uint64_t old = atomicCAS((unsigned long long*)&E.tab[slot].entry, (unsigned long long)EMPTY,
                                                            (unsigned long long)((tag << 32) | id));
@@ -2832,21 +2828,23 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
                 if (threadIdx.x == 0) l_qn = 0;
                 __syncthreads();
             }
-            // chain hook (see k_probe): the child that claimed an empty slot needs none
+            // chain hook.  The child that just claimed an empty slot needs none: its id IS the slot's entry, and the next
+            // child of this batch to land here finds it there (entry id >= base) when its own exchange returns a stale head —
+            // which spares most children (new states are ~85 % on cube3) their second atomic.
             if (cvalid) {
-                uint32_t prev = NIL;
+                uint32_t prev = NIL;  // the child chained in front of this one (batch-relative index)
                 if (!inserted) {
                     const uint32_t old_head = atomicExch(&E.tab[slot].head, id);
                     if (old_head >= base)
                         prev = old_head - base;
                     else if (rep_id >= base)
-                        prev = rep_id - base;
+                        prev = rep_id - base;  // first to follow the child that inserted the slot in this very batch
                 }
                 E.child_next[j] = prev;
                 E.child_slot[j] = slot;
                 E.child_v0[j] = v0;
-                E.child_flags[j] = inserted ? F_NEW : 0;
-                if (prev != NIL) {
+                E.child_flags[j] = inserted ? F_NEW : 0;  // counted in k_commit (one atomic per block there)
+                if (prev != NIL) {  // both ends of the link learn that their chain has company
                     E.child_multi[j] = 1;
                     E.child_multi[prev] = 1;
                 }
@@ -2897,106 +2895,7 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
     oh_emit();
 }
 
-// ---------------------------------------------------------------------------------------------
-// dedup A: find-or-insert the CLOSED slot of every child, chain the child to it
-// ---------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_probe(const Eng* __restrict__ engs) {
-    const Eng& E = engs[blockIdx.y];
-    Ctl* c = E.ctl;
-    if (c->done) return;
-    Stamp stamp(E, P_PROBE);
-    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-    const IterState& S1 = st_next(c);
-    const uint32_t m = S1.m, base = S1.base;
-    if (j >= m) return;
-    constexpr int NW = (D + 3) / 4;
-    const uint32_t id = base + j;
-    const uint64_t h = E.child_hash[j];
-    const uint64_t tag = h >> 32;
-    // this child's row, as words (the row was written by k_expand; the tail word is masked)
-    uint32_t mine[NW];
-    {
-        const uint8_t* row = E.state + (size_t)id * D;
-#pragma unroll
-        for (int k = 0; k < NW; k++) {
-            if (4 * k + 4 <= D) {
-                __builtin_memcpy(&mine[k], row + 4 * k, 4);
-            } else {
-                mine[k] = 0;
-                for (int b = 0; 4 * k + b < D; b++) mine[k] |= (uint32_t)row[4 * k + b] << (8 * b);
-            }
-        }
-    }
-    bool inserted = false;
-    uint32_t slot = (uint32_t)h & E.tab_mask;
-    uint32_t v0 = GINF, rep_id = 0;
-    for (uint32_t probes = 0;; probes++) {
-        // look first, claim second (a compare-and-swap on every probed slot — one round trip instead of two for a new
-        // state — was measured and lost badly: 61 us vs 26 us per launch; returning atomics are that much dearer here).
-        // ONE 16-byte load fetches the slot's entry together with its value: entries never change once written and
-        // values only change in k_commit, so a line cached by an earlier reader on this CU is either current or shows an
-        // EMPTY entry that the compare-and-swap then corrects.
-        const uint4 sl = *reinterpret_cast<const uint4*>(&E.tab[slot]);
-        uint64_t e = ((uint64_t)sl.y << 32) | sl.x;
-        v0 = sl.z;  // the slot's value before this batch (GINF while nothing was recorded)
-        if (e == EMPTY) {
-            const uint64_t old = atomicCAS((unsigned long long*)&E.tab[slot].entry, (unsigned long long)EMPTY,
-                                           (unsigned long long)((tag << 32) | id));
-            if (old == EMPTY) {
-                inserted = true;
-                break;
-            }
-            e = old;  // claimed meanwhile by another child of this batch: its value is still GINF, as loaded
-        }
-        if ((e >> 32) == tag) {
-            // exact key equality against the representative's state bytes (State.__eq__, cube3.py:23-24)
-            const uint8_t* rep = E.state + (size_t)(uint32_t)e * D;
-            uint32_t diff = 0;
-#pragma unroll
-            for (int k = 0; k < NW; k++) {
-                uint32_t v;
-                if (4 * k + 4 <= D) {
-                    __builtin_memcpy(&v, rep + 4 * k, 4);
-                } else {
-                    v = 0;
-                    for (int b = 0; 4 * k + b < D; b++) v |= (uint32_t)rep[4 * k + b] << (8 * b);
-                }
-                diff |= v ^ mine[k];
-            }
-            if (diff == 0) {
-                rep_id = (uint32_t)e;
-                break;
-            }
-        }
-        slot = (slot + 1) & E.tab_mask;
-        if (probes > E.tab_mask) {  // table full (cannot happen while pool <= cap/2)
-            c->failed = 1;
-            break;
-        }
-    }
-    // chain hook.  The child that just claimed an empty slot needs none: its id IS the slot's entry, and the next child
-    // of this batch to land here finds it there (entry id >= base) when its own exchange returns a stale head — which
-    // spares most children (new states are ~85 % on cube3) their second atomic.
-    uint32_t prev = NIL;  // the child chained in front of this one (batch-relative index)
-    if (!inserted) {
-        const uint32_t old_head = atomicExch(&E.tab[slot].head, id);
-        if (old_head >= base)
-            prev = old_head - base;
-        else if (rep_id >= base)
-            prev = rep_id - base;  // first to follow the child that inserted the slot in this very batch
-    }
-    E.child_next[j] = prev;
-    E.child_slot[j] = slot;
-    E.child_v0[j] = v0;
-    E.child_flags[j] = inserted ? F_NEW : 0;  // counted in k_commit (one atomic per block there)
-    if (prev != NIL) {  // both ends of the link learn that their chain has company (k_expand cleared the marks)
-        E.child_multi[j] = 1;
-        E.child_multi[prev] = 1;
-    }
-}
-
-// dedup B: keep decision in sequential order for child j of the batch (astar.py:81-88 / cpp:247-265): kept iff its
+// dedup, second half (the first runs inside k_expand): keep decision in sequential order for child j of the batch (astar.py:81-88 / cpp:247-265): kept iff its
 // path cost beats the slot's value before the batch and no earlier child of the batch on the same state has g <= g_j.
 // is_min: j is the first occurrence of the batch minimum on its slot (it records the slot's new value);
 // first: the sequentially first child on the slot.  A child alone on its slot needs no memory access at all.
@@ -3291,12 +3190,12 @@ __global__ __launch_bounds__(1024) void k_commit(const Eng* __restrict__ engs, i
     // This workgroup's pushes per selection bin -> FRONT's histogram (block_reserveK's barriers have ordered the LDS counts).
     // In a young search nearly every child lies below the histogram horizon and a workgroup's 1024 children touch 600-900
     // different bins: 235 workgroups x that many device-scope atomics were 10 of this launch's 23 us (iterations 8-27 — the
-    // window a 20-step bench episode lives in; tools/engine_probe.py @13=1 times the launch without them, profiles/
-    // r05_engine_ab.txt) — and they sat at the very END of the launch, behind everything else.  So: two bins per atomic (a
+    // window a 20-step bench episode lives in; profiles/r05_engine_ab.txt) — and they sat at the very END of the launch, behind
+    // everything else.  So: two bins per atomic (a
     // 64-bit add on an aligned pair of 32-bit counters: no carry, counts stay below 2^31), issued HERE, as soon as the counts
     // are complete, so that their trip to the memory side runs under the scattered stores and the range fold below.
     static_assert(kBinsPerThread % 2 == 0, "bins are flushed in aligned pairs");
-    if (kBinsPerThread * threadIdx.x < hbin && !(g_tune[13] & 1)) {  // (knob 13 bit 0, diagnostics: timing without the flush)
+    if (kBinsPerThread * threadIdx.x < hbin) {
 #pragma unroll
         for (int k = 0; k < kBinsPerThread; k += 2) {
             const uint32_t v0 = lh[kBinsPerThread * threadIdx.x + k], v1 = lh[kBinsPerThread * threadIdx.x + k + 1];
@@ -3347,8 +3246,7 @@ __global__ __launch_bounds__(1024) void k_commit(const Eng* __restrict__ engs, i
             for (int w = 1; w < 16; w++) v = (q & 1) ? (red[q][w] > v ? red[q][w] : v) : (red[q][w] < v ? red[q][w] : v);
             const uint32_t buf = q < 2 ? fb : bb;
             asm volatile("" : "+v"(rng_snap));  // (the snapshot is the wave's oldest load: long since back)
-            if (g_tune[13] & 2) {  // (knob 13 bit 1, diagnostics: timing without the range atomics)
-            } else if (q & 1) {
+            if (q & 1) {
                 if (v > rng_snap) atomicMax((unsigned long long*)&c->rng[buf].kmax, (unsigned long long)v);
             } else {
                 if (v < rng_snap) atomicMin((unsigned long long*)&c->rng[buf].kmin, (unsigned long long)v);
@@ -3502,12 +3400,10 @@ constexpr int kScanGrid = kScanBlocks;
 // k_rank's rocprofv3 maximum).  While OPEN is still growing by a factor of A per iteration a fresh binning each time is cheap.
 constexpr int kRampIters = 8;
 static inline bool rebase_due(long host_iter) { return host_iter < kRampIters || host_iter % kRefillPeriod == 0; }
-static int h_tune[16];  // host copy of the diagnostic knobs (dca_debug_tune)
+// knob 5 of dca_debug_tune: engines created while it is set never take the grid-wide giant-bin path (processes sharing a GPU)
+static int h_giant_path_off;
 
 inline dim3 gxy(unsigned x, const dca_engine* e) { return dim3(x, (unsigned)e->K); }
-// the CLOSED probe runs inside the expansion launch (four launches per iteration); knob 11 restores the separate k_probe
-// launch (round-3 behaviour, the A/B reference)
-inline bool fuse_probe() { return h_tune[11] == 0; }
 
 template <int ENV, int DIM>
 int launch_expand_env(const dca_engine* e, int heur_id, bool want_oh, bool want_nn, hipStream_t s) {
@@ -3516,24 +3412,13 @@ int launch_expand_env(const dca_engine* e, int heur_id, bool want_oh, bool want_
     dim3 g = gxy((E.B + kEngTile - 1) / kEngTile, e), b(kThreads);
     // tile + tables, then the staged child rows (16 parents x A children x D bytes)
     const size_t lds = TL::LDS_BYTES + ((kEngTile * EnvT<ENV, DIM>::A * EnvT<ENV, DIM>::D + 15) / 16) * 16 + 64;  // (+ slack: the one-hot loop peeks one byte past the tile)
-    const bool fuse = fuse_probe();
-    const int wnn = ((want_nn && heur_id < 0) || h_tune[12] != 0) ? 1 : 0;  // (knob 12: always write them, the round-4 behaviour, for A/B runs)
-    if (E.onehot == nullptr || !want_oh) {
-        if (fuse)
-            hipLaunchKernelGGL((k_expand<ENV, DIM, 0, true>), g, b, lds, s, e->d_engs, heur_id, wnn);
-        else
-            hipLaunchKernelGGL((k_expand<ENV, DIM, 0, false>), g, b, lds, s, e->d_engs, heur_id, wnn);
-    } else if (E.oh_dtype == DCA_DT_F32) {
-        if (fuse)
-            hipLaunchKernelGGL((k_expand<ENV, DIM, 4, true>), g, b, lds, s, e->d_engs, heur_id, wnn);
-        else
-            hipLaunchKernelGGL((k_expand<ENV, DIM, 4, false>), g, b, lds, s, e->d_engs, heur_id, wnn);
-    } else {
-        if (fuse)
-            hipLaunchKernelGGL((k_expand<ENV, DIM, 2, true>), g, b, lds, s, e->d_engs, heur_id, wnn);
-        else
-            hipLaunchKernelGGL((k_expand<ENV, DIM, 2, false>), g, b, lds, s, e->d_engs, heur_id, wnn);
-    }
+    const int wnn = want_nn && heur_id < 0 ? 1 : 0;
+    if (E.onehot == nullptr || !want_oh)
+        hipLaunchKernelGGL((k_expand<ENV, DIM, 0>), g, b, lds, s, e->d_engs, heur_id, wnn);
+    else if (E.oh_dtype == DCA_DT_F32)
+        hipLaunchKernelGGL((k_expand<ENV, DIM, 4>), g, b, lds, s, e->d_engs, heur_id, wnn);
+    else
+        hipLaunchKernelGGL((k_expand<ENV, DIM, 2>), g, b, lds, s, e->d_engs, heur_id, wnn);
     return launch_check("k_expand");
 }
 
@@ -3576,35 +3461,21 @@ int launch_pack(const dca_engine* e, hipStream_t s) {
     return DCA_E_BADARG;
 }
 
-void launch_probe(const dca_engine* e, hipStream_t s) {
-    const Eng& E = e->E[0];
-    const dim3 g = gxy((E.M + 255) / 256, e), b(256);
-    switch (E.D) {
-        case 54: hipLaunchKernelGGL(k_probe<54>, g, b, 0, s, e->d_engs); break;
-        case 16: hipLaunchKernelGGL(k_probe<16>, g, b, 0, s, e->d_engs); break;
-        case 25: hipLaunchKernelGGL(k_probe<25>, g, b, 0, s, e->d_engs); break;
-        case 36: hipLaunchKernelGGL(k_probe<36>, g, b, 0, s, e->d_engs); break;
-        default: hipLaunchKernelGGL(k_probe<49>, g, b, 0, s, e->d_engs); break;
-    }
-}
-
 constexpr size_t kRankLdsBytes = (size_t)kLdsEnt * 12;
 
 int enqueue_first_half(dca_engine* e, int heur_id, bool with_refill, hipStream_t s, bool want_oh = true, bool want_nn = true) {
     const Eng* d = e->d_engs;
     if (with_refill) {
+        // a rebase iteration: refill from BACK, compact FRONT and recount its selection histogram (maintained incrementally
+        // in between: k_sel_scan's writeback + k_commit's pushes), then k_sel_scan opens the pop
         hipLaunchKernelGGL(k_refill_hist, gxy(kScanGrid, e), dim3(256), 0, s, d);
         hipLaunchKernelGGL(k_refill_scan, gxy(1, e), dim3(1024), 0, s, d);
         hipLaunchKernelGGL(k_refill_move, gxy(kScanGrid, e), dim3(256), 0, s, d);
-    }
-    // FRONT's selection histogram is recounted only in the refill-check ("rebase") iterations — every kRefillPeriod-th —
-    // and maintained incrementally in between (k_sel_scan's writeback + k_commit's pushes)
-    if (with_refill) hipLaunchKernelGGL(k_front_rebase, gxy(kCollectBlocks, e), dim3(256), 0, s, d);
-    // the iteration's opening launch: k_sel_scan in a rebase iteration, k_sel_collect itself otherwise (FUSED)
-    if (with_refill || h_tune[6] != 0) {  // (knob 6: a k_sel_scan launch in every iteration, round-2 behaviour)
-        hipLaunchKernelGGL(k_sel_scan, gxy(1, e), dim3(1024), 0, s, d, with_refill ? 1 : 0);
+        hipLaunchKernelGGL(k_front_rebase, gxy(kCollectBlocks, e), dim3(256), 0, s, d);
+        hipLaunchKernelGGL(k_sel_scan, gxy(1, e), dim3(1024), 0, s, d, /*rebased=*/1);
         hipLaunchKernelGGL(k_sel_collect<false>, gxy(e->collect_blocks, e), dim3(256), sizeof(CollectLds), s, d);
     } else {
+        // otherwise k_sel_collect opens the iteration and scans the histogram itself (FUSED)
         hipLaunchKernelGGL(k_sel_collect<true>, gxy(e->collect_blocks, e), dim3(256), sizeof(CollectLds), s, d);
     }
     hipLaunchKernelGGL(k_rank, gxy(kRankBlocks, e), dim3(RT), kRankLdsBytes, s, d);
@@ -3612,15 +3483,8 @@ int enqueue_first_half(dca_engine* e, int heur_id, bool with_refill, hipStream_t
     return launch_expand(e, heur_id, want_oh, want_nn, s);
 }
 
-// CLOSED check of the batch's children.  with_decide: the stand-alone keep decision of the dedup-first stepping
-// (k_pack needs the flags before the heuristic runs); otherwise k_commit<true> decides while it pushes.
-int enqueue_dedup(dca_engine* e, bool with_decide, hipStream_t s) {
-    const Eng& E = e->E[0];
-    if (!fuse_probe()) launch_probe(e, s);
-    if (with_decide) hipLaunchKernelGGL(k_decide, gxy((E.M + 255) / 256, e), dim3(256), 0, s, e->d_engs);
-    return launch_check("dedup kernels");
-}
-
+// packed: the dedup-first stepping (the keep flags come from k_decide, before the heuristic runs); otherwise k_commit<true>
+// decides while it pushes
 int enqueue_commit(dca_engine* e, bool packed, hipStream_t s) {
     const Eng& E = e->E[0];
     const dim3 g = gxy((E.M + 1023) / 1024, e);
@@ -3629,11 +3493,6 @@ int enqueue_commit(dca_engine* e, bool packed, hipStream_t s) {
     else
         hipLaunchKernelGGL(k_commit<true>, g, dim3(1024), 0, s, e->d_engs, 0);
     return launch_check("k_commit");
-}
-
-int enqueue_second_half(dca_engine* e, hipStream_t s) {
-    if (int rc = enqueue_dedup(e, false, s)) return rc;
-    return enqueue_commit(e, false, s);
 }
 
 void drop_graph_slot(dca_engine::GraphSlot& g) {
@@ -3726,7 +3585,6 @@ int dca_engine_create_multi(dca_engine** out, int env, int dim, double weight, i
         (void)hipGetDevice(&dev);
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
         e->collect_blocks = (unsigned)(2 * cus < kCollectBlocks ? 2 * cus : kCollectBlocks);
-        if (h_tune[4] > 0 && h_tune[4] < (int)e->collect_blocks) e->collect_blocks = (unsigned)h_tune[4];
         // K instances share every launch (grid.y): keep the launch at about two workgroups per CU in total
         if (num_instances > 1) {
             const unsigned per = e->collect_blocks / (unsigned)num_instances;
@@ -3756,7 +3614,7 @@ int dca_engine_create_multi(dca_engine** out, int env, int dim, double weight, i
         E.wf = (float)weight;  // cpp:353 (float) atof(argv[2])
         E.max_nodes = (uint32_t)max_nodes;
         E.M = (uint32_t)Mll;
-        E.coop = (num_instances == 1 && h_tune[5] == 0) ? 1 : 0;  // (knob 5: giant-bin path off, round-2 behaviour)
+        E.coop = (num_instances == 1 && h_giant_path_off == 0) ? 1 : 0;
         E.f_keep = (uint32_t)(32 * batch_size > 65536 ? 32 * batch_size : 65536);
         E.f_max = 3 * E.f_keep;
         E.tab_cap = (uint32_t)cap;
@@ -3795,7 +3653,6 @@ int dca_engine_create_multi(dca_engine** out, int env, int dim, double weight, i
         ALLOC(pop_key, Bz);
         ALLOC(pop_id, Bz);
         ALLOC(pop_g, Bz);
-        ALLOC(child_hash, M);
         ALLOC(child_slot, M);
         ALLOC(child_next, M);
         ALLOC(child_flags, M);
@@ -3963,7 +3820,7 @@ int dca_engine_commit(dca_engine* e, const float* h, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     DCA_HIP(hipMemcpyAsync(e->h_all, h, (size_t)e->E[0].M * e->K * sizeof(float), hipMemcpyDeviceToDevice, s));
     e->phase = 0;
-    return enqueue_second_half(e, s);
+    return enqueue_commit(e, false, s);
 }
 
 
@@ -4017,7 +3874,8 @@ int dca_engine_pop_expand_packed(dca_engine* e, const uint8_t** nnet_in, const v
     hipStream_t s = (hipStream_t)stream;
     DCA_HIP(hipMemsetAsync(e->pk_n, 0, 4 * sizeof(uint32_t), s));
     if (int rc = enqueue_first_half(e, -1, rebase_due(e->host_iter++), s, false, false)) return rc;
-    if (int rc = enqueue_dedup(e, true, s)) return rc;
+    hipLaunchKernelGGL(k_decide, gxy((e->E[0].M + 255) / 256, e), dim3(256), 0, s, e->d_engs);  // k_pack reads the keep flags
+    if (int rc = launch_check("k_decide")) return rc;
     if (int rc = launch_pack(e, s)) return rc;
     DCA_HIP(hipMemcpyAsync(e->h_pk_n, e->pk_n, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     DCA_HIP(hipStreamSynchronize(s));
@@ -4058,11 +3916,9 @@ int dca_engine_commit_packed(dca_engine* e, const float* h, void* stream) {
 // The next chunk of a run of iterations that starts at iteration `host_iter` of the search: up to the next rebase-period
 // boundary first (so that a steady search replays whole periods, whose pattern repeats), then whole periods, kGraphChunk
 // iterations at most; during the ramp up to its end.  mask: bit i = iteration i of the chunk is a rebase iteration.
-static void plan_chunk(long host_iter, int remaining, bool single_only, int* n_out, unsigned long long* mask_out) {
+static void plan_chunk(long host_iter, int remaining, int* n_out, unsigned long long* mask_out) {
     int n = remaining;
-    if (single_only) {
-        n = 1;
-    } else if (host_iter < kRampIters) {
+    if (host_iter < kRampIters) {
         n = n < (int)(kRampIters - host_iter) ? n : (int)(kRampIters - host_iter);
     } else {
         const int to_boundary = (int)(kRefillPeriod - host_iter % kRefillPeriod) % kRefillPeriod;
@@ -4082,7 +3938,7 @@ static void plan_chunk(long host_iter, int remaining, bool single_only, int* n_o
 int dca_engine_plan_chunk(int64_t host_iter, int remaining, int* n, uint64_t* rebase_mask) {
     DCA_ARG(host_iter >= 0 && remaining >= 1 && n != nullptr && rebase_mask != nullptr);
     unsigned long long m = 0;
-    plan_chunk((long)host_iter, remaining, false, n, &m);
+    plan_chunk((long)host_iter, remaining, n, &m);
     *rebase_mask = (uint64_t)m;
     return 0;
 }
@@ -4097,7 +3953,7 @@ int dca_engine_run_builtin(dca_engine* e, int heur_id, int iters, int use_graph,
     if (!use_graph) {
         for (int i = 0; i < iters; i++) {
             if (int rc = enqueue_first_half(e, heur_id, rebase_due(e->host_iter++), s)) return rc;
-            if (int rc = enqueue_second_half(e, s)) return rc;
+            if (int rc = enqueue_commit(e, false, s)) return rc;
         }
         return 0;
     }
@@ -4108,7 +3964,7 @@ int dca_engine_run_builtin(dca_engine* e, int heur_id, int iters, int use_graph,
     for (int i = 0; i < iters;) {
         int n = 0;
         unsigned long long mask = 0;
-        plan_chunk(e->host_iter, iters - i, h_tune[7] != 0, &n, &mask);  // (knob 7: single-iteration graphs only)
+        plan_chunk(e->host_iter, iters - i, &n, &mask);
         dca_engine::GraphSlot* g = nullptr;
         for (int q = 0; q < kGraphSlots && !g; q++)
             if (e->gslot[q].exec && e->gslot[q].n == n && e->gslot[q].mask == mask) g = &e->gslot[q];
@@ -4127,7 +3983,7 @@ int dca_engine_run_builtin(dca_engine* e, int heur_id, int iters, int use_graph,
             if (err == hipSuccess) {
                 for (int it = 0; it < n && !rc; it++) {
                     rc = enqueue_first_half(e, heur_id, (mask >> it) & 1ull, cs);
-                    if (!rc) rc = enqueue_second_half(e, cs);
+                    if (!rc) rc = enqueue_commit(e, false, cs);
                 }
                 err = hipStreamEndCapture(cs, &g->graph);
             }
@@ -4160,7 +4016,8 @@ int dca_engine_profile_builtin(dca_engine* e, int heur_id, int iters, int use_gr
     // the device wall clock at entry and exit (Stamp), per launch the host takes max(end) - min(start) as the launch's
     // busy span and min(start of the next launch) - max(end) as the gap in front of it.  Slots (span_ms / gap_ms
     // [DCA_PROF_SLOTS], summed over the iterations): 0-2 refill hist/scan/move (every 8th iteration), 3 sel_hist,
-    // 4 sel_scan, 5 sel_collect, 6 rank, 7 expand, 8 probe, 9 decide, 10 pack (dedup-first stepping only), 11 commit.
+    // 4 sel_scan, 5 sel_collect, 6 rank, 7 expand (with the CLOSED probe), 8 unused, 9 decide, 10 pack (dedup-first stepping
+    // only), 11 commit.
     // gap_ms[k] = idle time in front of launch k inside an iteration (the first launch of an iteration has none).
     DCA_ARG(e != nullptr && span_ms != nullptr && heur_id >= 0 && heur_id <= DCA_HEUR_MANHATTAN && iters >= 0);
     if (e->phase != 0) {
@@ -4215,12 +4072,19 @@ int dca_engine_profile_builtin(dca_engine* e, int heur_id, int iters, int use_gr
 }
 
 int dca_debug_tune(int knob, int value) {
-    if (knob >= 0 && knob < 16) h_tune[knob] = value;  // (host-side knobs: 4 = workgroups of k_sel_collect; set before the first step)
-    // diagnostics: 0 extra log2 of sub-bins per large bin, 1 sub-bin size above which a sub-bin is refined on its own,
-    // 2 BACK squeeze mark in 1/1024ths of max_nodes, 3 threshold-bin size above which the grid refines the bin (giant
-    // iterations), 5 (host, before create) giant-bin path off, 6 (host) k_sel_scan launched in every iteration, 7 (host) single-iteration graphs only, 9 largest bin ranked a thread per entry
-    DCA_ARG(knob >= 0 && knob < 16);
-    DCA_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_tune), &value, sizeof(int), (size_t)knob * sizeof(int), hipMemcpyHostToDevice));
+    // the three hooks of include/dca_debug.h; checked before any HIP call, so that a refusal needs no device
+    if (knob != 2 && knob != 5 && knob != 10) {
+        set_error("dca_debug_tune: knob %d does not exist (the hooks are 2, 5 and 10)", knob);
+        return DCA_E_BADARG;
+    }
+    if (knob == 5) {
+        h_giant_path_off = value;  // (host side: read by the next dca_engine_create*)
+        return 0;
+    }
+    if (knob == 2)
+        DCA_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_back_squeeze_mark), &value, sizeof(int), 0, hipMemcpyHostToDevice));
+    else
+        DCA_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_first_barrier_gives_up), &value, sizeof(int), 0, hipMemcpyHostToDevice));
     return 0;
 }
 

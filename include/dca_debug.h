@@ -1,8 +1,8 @@
 /* dca_debug.h — test, tuning and profiling hooks of libdca_hip.so, kept apart from the product ABI (include/dca.h).
  *
  * Nothing here is needed to run a search, an update or a network forward: these entry points exist for tests/ (race screens
- * against a plain schedule, forced fallbacks, tiny tiers), for bench.py's device-side launch profile and for the A/B tools
- * under tools/.  Same conventions as dca.h (plain C, int return codes, the error text of the last failure through dca.h).  Exported by the same library. */
+ * against a plain schedule, forced fallbacks, tiny tiers), for bench.py's device-side launch profile and for the measurement
+ * tools under tools/ — and knob 5 of dca_debug_tune, which processes sharing one GPU set.  Same conventions as dca.h (plain C, int return codes, the error text of the last failure through dca.h).  Exported by the same library. */
 #ifndef DCA_DEBUG_H
 #define DCA_DEBUG_H
 
@@ -23,8 +23,8 @@ int dca_engine_plan_chunk(int64_t host_iter, int remaining, int* n, uint64_t* re
  * the previous launch's end as the gap in front of it — measured INSIDE the replayed hipGraph, which HIP events between
  * eager launches cannot do.  span_ms / gap_ms: host float[DCA_PROF_SLOTS], summed milliseconds over the iterations
  * (gap_ms may be NULL).  Slots: 0 refill_hist 1 refill_scan 2 refill_move 3 sel_hist (= the FRONT rebase pass; 0-3 only in
- * rebase iterations: every 8th, and the first twelve after a reset) 4 sel_scan 5 sel_collect 6 rank 7 expand 8 probe 9 decide
- * 10 pack (dedup-first stepping only) 11 commit; 12 / 13 = the two halves of the rank launch (small-bin pass, large-bin
+ * rebase iterations: every 8th, and the first twelve after a reset) 4 sel_scan 5 sel_collect 6 rank 7 expand (with the CLOSED
+ * probe) 8 unused (stays empty: the slot numbers do not move) 9 decide 10 pack (dedup-first stepping only) 11 commit; 12 / 13 = the two halves of the rank launch (small-bin pass, large-bin
  * workgroups), 14-17 = phases of the large-bin path (load + range, count + prefix, scatter, order) as envelopes over the
  * workgroups — for tuning.  Synchronises every iteration.                                                            */
 #define DCA_PROF_SLOTS 18
@@ -36,11 +36,15 @@ int dca_engine_set_tiers(dca_engine* e, int64_t front_keep, int64_t front_max);
 
 /* internals of the last iteration for diagnostics (host double[16]; layout in dca_engine.hip); synchronises */
 int dca_engine_debug(dca_engine* e, double* out /*host [16]*/, void* stream);
-/* diagnostics: flips a tuning knob of the engine kernels process-wide (0 = shipped behaviour); never needed in production.
- * knob 0: extra log2 of sub-bins per large bin in k_rank; 1: sub-bin size above which a sub-bin is refined on its own;
- * 2: BACK squeeze mark (1/1024ths of max_nodes); 3: threshold-bin size above which the grid refines the bin; 4: workgroups of
- * k_sel_collect, 5: grid-wide refinement off, 6: k_sel_scan in every iteration, 7: single-iteration graphs only (4-7 host side,
- * set before the engine is created / first stepped); 9: largest bin k_rank orders a thread per entry; 0-15 accepted.      */
+/* Sets one of the engine's three hooks process-wide (value 0 = the shipped behaviour):
+ *   2: BACK is squeezed without a refill once it holds more than max_nodes * value / 1024 physical entries (tests: the
+ *      compaction-only pass under tiny tiers);
+ *   5: value != 0 turns the grid-wide refinement of giant tie bins off for every engine created afterwards (host side, no
+ *      device needed).  search_methods/sharding.py sets it when several processes share one GPU: that path needs every
+ *      workgroup of its launch resident, which such processes cannot promise each other;
+ *   10: value != 0 makes the first grid barrier of every giant iteration give up at once (tests: the consensus fallback that
+ *      dca_engine_info [4] reports).
+ * Any other knob is refused with DCA_E_BADARG (the error text names it) before any HIP call.                             */
 int dca_debug_tune(int knob, int value);
 
 /* ---- environment kernels ------------------------------------------------------------------------------------------- */

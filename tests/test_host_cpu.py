@@ -452,6 +452,17 @@ def test_graph_chunk_plan_covers_any_run_and_repeats_in_a_steady_search():
     assert len(set(plan(8, 5000)[1:-1])) == 1
 
 
+def test_debug_tune_refuses_every_knob_but_the_three_hooks():
+    """dca_debug_tune has three hooks (2, 5, 10).  Any other knob number is refused with DCA_E_BADARG and an error text that
+    names it, before any HIP call (no device needed): `bench.py --tune` with a retired knob fails instead of silently
+    measuring the default."""
+    from deepcubea_amd import _lib
+    L = _lib.lib()
+    for k in [k for k in range(16) if k not in (2, 5, 10)] + [-1, 16, 1 << 20]:
+        assert L.dca_debug_tune(k, 1) == -1, k  # DCA_E_BADARG
+        assert "knob %d" % k in L.dca_last_error().decode(), (k, L.dca_last_error())
+
+
 def test_power_of_two_operand_scaling_keeps_fp32_products_on_fp16_planes():
     """The arithmetic behind `_lib.linear_train` (training-step GEMMs through dca_f16x3_gemm), restated in numpy: an operand is
     multiplied by the power of two that brings its largest magnitude into [2^14, 2^15) (exact), split into hi = fp16(x) and
