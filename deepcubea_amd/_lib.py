@@ -330,6 +330,8 @@ class _BnTrainFn(torch.autograd.Function):
 def bn_train(x: torch.Tensor, bn: "torch.nn.BatchNorm1d", relu: bool, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Training-mode `relu?(bn(x) (+ skip))` on the device, updating bn.running_mean / running_var /
     num_batches_tracked exactly like nn.BatchNorm1d (momentum average, unbiased variance)."""
+    if x.shape[0] == 1:  # one sample has no batch variance: nn.BatchNorm1d refuses it in training mode, with these words
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (torch.Size(x.shape),))
     stats = []
     y = _BnTrainFn.apply(x, skip, bn.weight, bn.bias, float(bn.eps), bool(relu), stats)
     if bn.track_running_stats and bn.running_mean is not None:
@@ -347,39 +349,98 @@ def _pad64(k: int) -> int:
     return (k + 63) // 64 * 64
 
 
+def _raw(t: Optional[torch.Tensor]) -> C.c_void_p:
+    """Device address of a tensor that the callee walks with an explicit row stride (views welcome); None -> NULL."""
+    if t is None:
+        return C.c_void_p(0)
+    assert t.is_cuda
+    return C.c_void_p(t.data_ptr())
+
+
+def _rows_cols_ld(x: torch.Tensor, m, n, ld):
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    return (int(x.shape[0]) if m is None else int(m), int(x.shape[1]) if n is None else int(n),
+            int(x.stride(0)) if ld is None else int(ld))
+
+
+def absmax_bits(x: torch.Tensor, m: Optional[int] = None, n: Optional[int] = None, ld: Optional[int] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """max |x| of an fp32 matrix as float bits in a device int32 word (dca_absmax_bits; the word is zeroed by the call).
+    x: rows of unit column stride — a column slice of a wider matrix is fine; m / n / ld (row stride in elements) default to
+    x's own shape and stride."""
+    m, n, ld = _rows_cols_ld(x, m, n, ld)
+    if out is None:
+        out = torch.empty(1, dtype=torch.int32, device=x.device)
+    check(lib().dca_absmax_bits(_raw(x), C.c_int64(m), C.c_int64(n), C.c_int64(ld), _raw(out), stream_ptr()), "dca_absmax_bits")
+    return out
+
+
+def split_planes_scaled(x: torch.Tensor, amax: Optional[torch.Tensor] = None, n_pad: Optional[int] = None,
+                        ldo: Optional[int] = None, out: Optional[torch.Tensor] = None, m: Optional[int] = None,
+                        n: Optional[int] = None, ld: Optional[int] = None) -> torch.Tensor:
+    """fp32 [m, n] (row stride ld) * 2^e -> its fp16 planes out[0] (high) / out[1] (low), [2, m, ldo] (dca_split_planes_scaled):
+    2^e takes the |max| whose bits `amax` holds into [2^14, 2^15) (amax None: unscaled); columns n..n_pad are written as zeros,
+    columns n_pad..ldo are not touched.  n_pad defaults to n, ldo to n_pad; `out` may be a buffer of the caller's."""
+    m, n, ld = _rows_cols_ld(x, m, n, ld)
+    n_pad = n if n_pad is None else int(n_pad)
+    ldo = n_pad if ldo is None else int(ldo)
+    if out is None:
+        out = torch.empty((2, m, ldo), dtype=torch.float16, device=x.device)
+    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (2, m, ldo)
+    check(lib().dca_split_planes_scaled(_raw(x), C.c_int64(m), C.c_int64(n), C.c_int64(ld), _raw(amax), _raw(out[0]), _raw(out[1]),
+                                        C.c_int64(ldo), C.c_int64(n_pad), stream_ptr()), "dca_split_planes_scaled")
+    return out
+
+
+def split_rows_scaled(w: torch.Tensor, other_amax: Optional[torch.Tensor] = None, k_pad: Optional[int] = None,
+                      ldo: Optional[int] = None, out: Optional[torch.Tensor] = None, col_scale: Optional[torch.Tensor] = None,
+                      n: Optional[int] = None, k: Optional[int] = None, ld: Optional[int] = None):
+    """Per row of w [n, k] fp32 (row stride ld): the row's own power-of-two scale 2^e (its |max| into [2^14, 2^15)), the fp16
+    planes of row * 2^e in out [2, n, ldo] (columns k..k_pad zero, k_pad..ldo untouched) and col_scale[row] = 1 / (2^e * the scale
+    of the OTHER operand, whose |max| bits `other_amax` holds; None: 1) (dca_split_rows_scaled).  -> (out, col_scale)."""
+    n, k, ld = _rows_cols_ld(w, n, k, ld)
+    k_pad = k if k_pad is None else int(k_pad)
+    ldo = k_pad if ldo is None else int(ldo)
+    if out is None:
+        out = torch.empty((2, n, ldo), dtype=torch.float16, device=w.device)
+    if col_scale is None:
+        col_scale = torch.empty(n, dtype=torch.float32, device=w.device)
+    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (2, n, ldo)
+    assert col_scale.dtype == torch.float32 and col_scale.is_contiguous() and col_scale.numel() >= n
+    check(lib().dca_split_rows_scaled(_raw(w), C.c_int64(n), C.c_int64(k), C.c_int64(ld), _raw(out[0]), _raw(out[1]), C.c_int64(ldo),
+                                      C.c_int64(k_pad), _raw(col_scale), _raw(other_amax), stream_ptr()), "dca_split_rows_scaled")
+    return out, col_scale
+
+
+def fill_inv_pow2(amax: torch.Tensor, n: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[0..n) = the reciprocal of the power-of-two scale split_planes_scaled derives from `amax` (dca_fill_inv_pow2)."""
+    if out is None:
+        out = torch.empty(int(n), dtype=torch.float32, device=amax.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n
+    check(lib().dca_fill_inv_pow2(_raw(out), C.c_int64(n), _raw(amax), stream_ptr()), "dca_fill_inv_pow2")
+    return out
+
+
 def linear_f16x3(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], scale_a: bool,
                  amax: Optional[torch.Tensor] = None) -> torch.Tensor:
     """a [m, k] fp32 . w [n, k]^T (+ bias) -> [m, n] fp32 through dca_f16x3_gemm (fp32-accurate on the f16 matrix pipes),
-    operands prepared on the spot: rows of w scaled by their own power of two (dca_split_rows_scaled), `a` by one power of two
-    for the whole tensor when scale_a (gradients; dca_absmax_bits + dca_split_planes_scaled) — activations (O(1) after
-    BatchNorm) are split as they are.  k, n % 4 == 0; K is zero-padded to a multiple of 64 inside the planes."""
+    operands prepared on the spot: rows of w scaled by their own power of two (split_rows_scaled), `a` by one power of two
+    for the whole tensor when scale_a (absmax_bits + split_planes_scaled; the forward's activations and the backward's
+    gradients both take it).  k, n % 4 == 0; K is zero-padded to a multiple of 64 inside the planes (the kernels write the
+    pad: the planes come from torch.empty)."""
     assert a.is_cuda and a.dtype == torch.float32 and w.dtype == torch.float32 and a.dim() == 2 and w.dim() == 2
     a, w = a.contiguous(), w.contiguous()
     m, k = a.shape
     n = w.shape[0]
     assert w.shape[1] == k and k % 4 == 0 and n % 4 == 0
     kp = _pad64(k)
-    dev = a.device
     if scale_a and amax is None:  # (the backward pass takes max|dy| once for both of its GEMMs)
-        amax = torch.empty(1, dtype=torch.int32, device=dev)
-        check(lib().dca_absmax_bits(ptr(a), C.c_int64(m), C.c_int64(k), C.c_int64(k), ptr(amax), stream_ptr()), "dca_absmax_bits")
+        amax = absmax_bits(a)
     if not scale_a:
         amax = None
-    ap = torch.empty((2, m, kp), dtype=torch.float16, device=dev)
-    check(lib().dca_split_planes_scaled(ptr(a), C.c_int64(m), C.c_int64(k), C.c_int64(k), ptr(amax), ptr(ap[0]), ptr(ap[1]),
-                                        C.c_int64(kp), C.c_int64(kp), stream_ptr()), "dca_split_planes_scaled")
-    wp = torch.empty((2, n, kp), dtype=torch.float16, device=dev)
-    cs = torch.empty(n, dtype=torch.float32, device=dev)
-    check(lib().dca_split_rows_scaled(ptr(w), C.c_int64(n), C.c_int64(k), C.c_int64(k), ptr(wp[0]), ptr(wp[1]), C.c_int64(kp),
-                                      C.c_int64(kp), ptr(cs), ptr(amax), stream_ptr()), "dca_split_rows_scaled")
+    ap = split_planes_scaled(a, amax, n_pad=kp)
+    wp, cs = split_rows_scaled(w, amax, k_pad=kp)
     _, out = f16x3_gemm(ap, wp[0], wp[1], cs, 1.0, None if bias is None else bias.contiguous(), None, False, False, True)
-    return out
-
-
-def _absmax_bits(a: torch.Tensor) -> torch.Tensor:
-    out = torch.empty(1, dtype=torch.int32, device=a.device)
-    check(lib().dca_absmax_bits(ptr(a), C.c_int64(a.shape[0]), C.c_int64(a.shape[1]), C.c_int64(a.shape[1]), ptr(out), stream_ptr()),
-          "dca_absmax_bits")
     return out
 
 
@@ -402,7 +463,7 @@ class _LinearTrainFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
         dy = dy.contiguous()
-        amax = _absmax_bits(dy) if ctx.needs_input_grad[0] else None
+        amax = absmax_bits(dy) if ctx.needs_input_grad[0] else None
         dx = linear_f16x3(dy, weight.t().contiguous(), None, scale_a=True, amax=amax) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:

@@ -159,10 +159,12 @@ def test_avi_loop_end_to_end(tmp_path):
 
 
 @pytest.mark.parametrize("n,c,relu,use_skip", [(1003, 1000, True, False), (517, 72, True, True), (64, 37, False, False),
-                                               (2, 5000, True, True), (10000, 1024, False, True)])
+                                               (2, 5000, True, True), (10000, 1024, False, True),
+                                               (129, 3, True, True), (100000, 8, True, False)])
 def test_bn_train_kernels_match_float64_reference(n, c, relu, use_skip):
     """csrc/dca_train.hip vs nn.BatchNorm1d(train) [+ skip] [+ ReLU] evaluated in float64: outputs, running statistics,
-    and all gradients (dx, dskip, dgamma, dbeta)."""
+    and all gradients (dx, dskip, dgamma, dbeta).  (129, 3): fewer than 4 columns, the scalar path alone; (100 000, 8): long
+    column slices."""
     from deepcubea_amd import _lib
     torch.manual_seed(n + c)
     dev = "cuda"
@@ -198,6 +200,94 @@ def test_bn_train_kernels_match_float64_reference(n, c, relu, use_skip):
     assert torch.allclose(bn.bias.grad.double(), ref.bias.grad, rtol=1e-3, atol=1e-3 * max(1.0, float(ref.bias.grad.abs().max())))
     if use_skip:
         assert torch.allclose(skip.grad.double(), sd.grad, **tol)
+
+
+def _bn_three_ways(x, w, relu):
+    """relu?(BatchNorm1d(x)) in training mode and the gradients of sum(y * w): (dca_train.hip, torch fp32, float64), each
+    [y, running_mean, running_var, dx, dgamma, dbeta] as float64."""
+    from deepcubea_amd import _lib
+    c = x.shape[1]
+    torch.manual_seed(c)
+    proto = torch.nn.BatchNorm1d(c).cuda()
+    with torch.no_grad():
+        proto.weight.uniform_(0.5, 1.5)
+        proto.bias.normal_(0, 0.3)
+        proto.running_mean.normal_(0, 0.2)
+        proto.running_var.uniform_(0.5, 2.0)
+    outs = []
+    for mode in ("ours", "torch32", "float64"):
+        bn = torch.nn.BatchNorm1d(c).cuda()
+        bn.load_state_dict(proto.state_dict())
+        xx, ww = x.clone(), w
+        if mode == "float64":
+            bn, xx, ww = bn.double(), xx.double(), w.double()
+        xx.requires_grad_(True)
+        y = _lib.bn_train(xx, bn, relu=relu) if mode == "ours" else (torch.relu(bn(xx)) if relu else bn(xx))
+        (y * ww).sum().backward()
+        assert int(bn.num_batches_tracked) == 1
+        outs.append([t.detach().double() for t in (y, bn.running_mean, bn.running_var, xx.grad, bn.weight.grad, bn.bias.grad)])
+    return outs
+
+
+def test_bn_train_constant_column_has_variance_zero():
+    """A column that holds one value: mean = that value exactly, variance 0, invstd = 1 / sqrt(eps); y = beta there, the running
+    variance decays by the momentum alone, and no gradient flows back into the column (finite everywhere)."""
+    torch.manual_seed(3)
+    n, c = 1003, 40
+    x = torch.randn(n, c, device="cuda") * 1.7 + 0.4
+    x[:, 5] = 2.75
+    x[:, 39] = -1.0e-3
+    w = torch.randn(n, c, device="cuda")
+    ours, t32, f64 = _bn_three_ways(x, w, relu=False)
+    for o in ours:
+        assert bool(torch.isfinite(o).all())
+    tol = dict(rtol=2e-4, atol=2e-4)
+    assert torch.allclose(ours[0], f64[0], **tol)
+    assert torch.allclose(ours[1], f64[1], rtol=1e-5, atol=1e-6) and torch.allclose(ours[2], f64[2], rtol=1e-5, atol=1e-6)
+    for col in (5, 39):  # every row of a constant column leaves with the same bits, the running variance only decays
+        assert float((ours[0][:, col] - ours[0][0, col]).abs().max()) == 0.0
+        assert abs(float(ours[2][col] - f64[2][col])) <= 1e-6
+    # gradients: dx = gamma * invstd * (dy - mean(dy)) there, with invstd = 316
+    scale = max(1.0, float(f64[3].abs().max()))
+    assert scale > 300.0
+    assert torch.allclose(ours[3], f64[3], rtol=1e-3, atol=2e-4 * scale)
+    others = [j for j in range(c) if j not in (5, 39)]
+    assert torch.allclose(ours[3][:, others], f64[3][:, others], rtol=1e-3, atol=2e-4 * max(1.0, float(f64[3][:, others].abs().max())))
+    for i in (4, 5):
+        assert torch.allclose(ours[i], f64[i], rtol=1e-3, atol=1e-3 * max(1.0, float(f64[i].abs().max())))
+
+
+def test_bn_train_column_with_mean_ten_thousand_standard_deviations():
+    """|mean| / std = 1e4: the fp32 mean carries a rounding error of 1e4 * 2^-24 standard deviations into every normalised value,
+    in torch's kernels as in these — the absolute tolerances of the test above do not apply.  Outputs, statistics and gradients
+    are as close to float64 as torch's fp32 BatchNorm is, a factor 4 allowed (floor: 2e-7 of the tensor's largest element)."""
+    torch.manual_seed(4)
+    n, c = 4096, 64
+    x = torch.randn(n, c, device="cuda")
+    x[:, 7] = x[:, 7] * 1.0e-2 + 100.0
+    x[:, 20] = x[:, 20] - 1.0e4
+    w = torch.randn(n, c, device="cuda")
+    for relu in (False, True):
+        ours, t32, f64 = _bn_three_ways(x, w, relu=relu)
+        for name, o, t, r in zip(("y", "running_mean", "running_var", "dx", "dgamma", "dbeta"), ours, t32, f64):
+            e_o, e_t = float((o - r).abs().max()), float((t - r).abs().max())
+            assert e_o <= max(4.0 * e_t, 2e-7 * float(r.abs().max())), (name, relu, e_o, e_t)
+
+
+def test_bn_train_refuses_a_single_sample_like_nn_batchnorm():
+    """One row has no batch variance: nn.BatchNorm1d raises ValueError in training mode, and so does _lib.bn_train, which
+    refuses before it touches the running statistics.  (nn.BatchNorm1d itself counts the batch before it refuses, so the
+    library's error is provoked on a module of its own.)"""
+    from deepcubea_amd import _lib
+    bn = torch.nn.BatchNorm1d(8).cuda()
+    x = torch.randn(1, 8, device="cuda")
+    with pytest.raises(ValueError, match="Expected more than 1 value per channel when training"):
+        torch.nn.BatchNorm1d(8).cuda()(x)
+    with pytest.raises(ValueError, match="Expected more than 1 value per channel when training"):
+        _lib.bn_train(x, bn, relu=True)
+    assert int(bn.num_batches_tracked) == 0 and float(bn.running_mean.abs().max()) == 0.0
+    assert float((bn.running_var - 1.0).abs().max()) == 0.0
+    assert tuple(_lib.bn_train(torch.randn(2, 8, device="cuda"), bn, relu=True).shape) == (2, 8)
 
 
 def test_avi_two_ranks_ddp(tmp_path):
