@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdca_hip.so")
 
 ENV_CUBE3, ENV_NPUZZLE, ENV_LIGHTSOUT, ENV_CUBE4 = 0, 1, 2, 3
-DT_F32, DT_F16, DT_BF16, DT_F16X3, DT_F16_PLANES, DT_E4M3, DT_F64 = 0, 1, 2, 3, 4, 5, 6
+DT_F32, DT_F16, DT_BF16, DT_F16_PLANES, DT_E4M3, DT_F64 = 0, 1, 2, 4, 5, 6  # (3 is unused)
 E4M3 = torch.float8_e4m3fn  # OCP e4m3: the fp8 format of gfx950's matrix pipes
 SEM_PY, SEM_CPP = 0, 1
 HEUR_MOD97, HEUR_KNUTH3, HEUR_HASHU01, HEUR_ZERO, HEUR_MANHATTAN = 0, 1, 2, 3, 4
@@ -84,7 +84,7 @@ def lib() -> C.CDLL:
         _lib.dca_bn_workspace_bytes.restype = C.c_int64
         _lib.dca_bn_workspace_bytes.argtypes = [C.c_int64]
         _lib.dca_engine_destroy.restype = None
-        if _lib.dca_abi_version() != 5:
+        if _lib.dca_abi_version() != 6:
             raise DcaError("libdca_hip.so ABI version mismatch")
     return _lib
 
@@ -495,17 +495,16 @@ def l1_kpad(state_dim: int, depth: int) -> int:
 def l1_onehot_gemm(states_nnet: torch.Tensor, depth: int, w_tiles: torch.Tensor, planes: int, bias: torch.Tensor,
                    relu: bool, out_dtype, split=False, overflow: Optional[torch.Tensor] = None) -> torch.Tensor:
     """relu?(onehot(states_nnet) @ W1^T + b1) from the uint8 rows, [m, n_pad] in out_dtype (dca_l1_onehot_gemm);
-    split=True: the library-GEMM f16x3 operand [m, 3*n_pad] fp16 of the next layer instead (DCA_DT_F16X3);
-    split="planes": dca_f16x3_gemm's operand [2, m, n_pad] fp16 (high halves, low halves; DCA_DT_F16_PLANES)."""
+    split="planes": dca_f16x3_gemm's operand [2, m, n_pad] fp16 of the next layer instead (high halves, low halves;
+    DCA_DT_F16_PLANES)."""
+    if split not in (False, "planes"):
+        raise ValueError("l1_onehot_gemm: split is False or 'planes', not %r" % (split,))
     x = _u8(states_nnet)
     m, d = x.shape
     n_pad = bias.numel()
     if split == "planes":
         out = torch.empty((2, m, n_pad), dtype=torch.float16, device=x.device)
         code = DT_F16_PLANES
-    elif split:
-        out = torch.empty((m, 3 * n_pad), dtype=torch.float16, device=x.device)
-        code = DT_F16X3
     elif out_dtype == E4M3:  # (planes == 1; the caller has folded the activation scale into the weights and bias)
         out = torch.empty((m, n_pad), dtype=E4M3, device=x.device)
         code = DT_E4M3
@@ -572,22 +571,19 @@ def l1_embed(states_nnet: torch.Tensor, depth: int, w_t: torch.Tensor, bias: tor
 
 
 def act_split(y: torch.Tensor, bias: Optional[torch.Tensor], skip: Optional[torch.Tensor], alpha, relu: bool,
-              want_x: bool, want_a3=True, overflow: Optional[torch.Tensor] = None):
-    """v = relu?(y*alpha + bias (+ skip)) -> (a3, v fp32 or None).  want_a3=True: the library-GEMM operand [m,3n] fp16,
-    a3[3k..3k+2] = (vh, vl, vh); want_a3="planes": dca_f16x3_gemm's operand [2,m,n] fp16; False: None."""
+              want_x: bool, want_a3="planes", overflow: Optional[torch.Tensor] = None):
+    """v = relu?(y*alpha + bias (+ skip)) -> (a3, v fp32 or None).  want_a3="planes": a3 = dca_f16x3_gemm's operand [2,m,n] fp16
+    (high halves, low halves); False: None."""
+    if want_a3 not in (False, "planes"):
+        raise ValueError("act_split: want_a3 is 'planes' or False, not %r" % (want_a3,))
     assert y.dtype == torch.float32 and y.is_contiguous() and (want_x or want_a3)
     m, n = y.shape
-    planes = want_a3 == "planes"
-    a3 = None
-    if planes:
-        a3 = torch.empty((2, m, n), dtype=torch.float16, device=y.device)
-    elif want_a3:
-        a3 = torch.empty((m, 3 * n), dtype=torch.float16, device=y.device)
+    a3 = torch.empty((2, m, n), dtype=torch.float16, device=y.device) if want_a3 else None
     x_out = torch.empty_like(y) if want_x else None
     col_scale = alpha if isinstance(alpha, torch.Tensor) else None  # per-output-unit scale vector or one scalar
     check(lib().dca_act_split(ptr(y), ptr(bias), ptr(skip), ptr(col_scale), C.c_double(1.0 if col_scale is not None else alpha),
-                              int(relu), C.c_int64(m), C.c_int64(n), ptr(x_out), ptr(a3), int(planes), ptr(overflow),
-                              stream_ptr()), "dca_act_split")
+                              int(relu), C.c_int64(m), C.c_int64(n), ptr(x_out), ptr(a3), ptr(overflow), stream_ptr()),
+          "dca_act_split")
     return a3, x_out
 
 

@@ -54,7 +54,7 @@ __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {  // gfx950's v_cv
 }
 
 template <int D, int DEPTH, int P,
-          int OUT /*0 f32, 1 f16, 2 bf16, 3 f16x3 split (vh, vl, vh) interleaved, 4 two fp16 planes (high, then low at +m*ldo),
+          int OUT /*0 f32, 1 f16, 2 bf16, (3 unused,) 4 two fp16 planes (high, then low at +m*ldo),
                     5 e4m3 bytes (saturating), 6 e4m3 bytes with one E8M0 block scale per row and 64 columns (out_scale)*/>
 __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __restrict__ nn, int64_t m,
                                                         const uint8_t* __restrict__ wt /*[ntile][P][KC][64][8] bf16*/,
@@ -377,14 +377,7 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
                             reinterpret_cast<_Float16*>(out)[r * ldo + col] = (_Float16)v;
                         else if constexpr (OUT == 2)
                             reinterpret_cast<uint16_t*>(out)[r * ldo + col] = f32_to_bf16_rne(v);
-                        else if constexpr (OUT == 3) {  // the library-GEMM f16x3 A operand: 192 contiguous bytes per 32 lanes
-                            _Float16* q = reinterpret_cast<_Float16*>(out) + (r * ldo + col) * 3;
-                            if (!(fabsf(v) <= 60000.0f) && overflow) *overflow = 1;
-                            const _Float16 hh = (_Float16)v;
-                            q[0] = hh;
-                            q[1] = (_Float16)(v - (float)hh);
-                            q[2] = hh;
-                        } else {  // the two fp16 planes dca_f16x3_gemm reads: high halves, then (m*ldo further) low halves
+                        else {  // the two fp16 planes dca_f16x3_gemm reads: high halves, then (m*ldo further) low halves
                             _Float16* q = reinterpret_cast<_Float16*>(out) + r * ldo + col;
                             if (!(fabsf(v) <= 60000.0f) && overflow) *overflow = 1;
                             const _Float16 hh = (_Float16)v;
@@ -417,8 +410,6 @@ int launch_l1_out(const uint8_t* nn, int64_t m, const uint8_t* wt, const float* 
         DCA_L1_LAUNCH(1);
     else if (out_dtype == DCA_DT_BF16)
         DCA_L1_LAUNCH(2);
-    else if (out_dtype == DCA_DT_F16X3)
-        DCA_L1_LAUNCH(3);
     else if (out_dtype == DCA_DT_E4M3) {
         if constexpr (P == 1) {  // (the fp8 mode keeps layer 1's weights as ONE bf16 plane: no other combination is built)
             if (out_scale != nullptr)
@@ -447,15 +438,13 @@ int launch_l1(int planes, const uint8_t* nn, int64_t m, const uint8_t* wt, const
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// fp32-accurate dense layers on the f16 MFMA pipes ("f16x3").  An fp32 value splits exactly into two fp16 numbers to
-// 22 bits (x = xh + xl, xh = f16(x), xl = f16(x - xh)); with the weights split the same way (pre-scaled by a power of two
-// so their low parts stay normal)  x.w = xh.wh + xl.wh + xh.wl + O(2^-22 |x.w|).  Laid out along K as A3[3k..3k+2] =
-// (xh, xl, xh) and W3[3k..3k+2] = (wh, wh, wl), ONE library f16 GEMM with fp32 output is an fp32-accurate GEMM at 3x the f16 cost — 2.4-2.9x
-// faster than the library's fp32 GEMM (f32-input MFMA runs at 1/16 of the f16 rate), same error class (measured
-// 1.7e-6 vs 1.2e-6 max-relative at K = 1024).  This kernel is the glue between two such GEMMs: it applies what follows
-// the Linear in the network (scale back — per output unit, the weight rows carry their own power-of-two scale —, bias,
-// residual add, ReLU — utils/pytorch_models.py:57-86 with BatchNorm folded)
-// and emits the next layer's A3 in one pass (read 4-8 B, write 6-10 B per element).
+// Glue in front of the fp32-accurate dense layers on the f16 MFMA pipes ("f16x3", csrc/dca_gemm.hip).  An fp32 value
+// splits exactly into two fp16 numbers to 22 bits (x = xh + xl, xh = f16(x), xl = f16(x - xh)); dca_f16x3_gemm reads its
+// activations as those two planes.  Its own epilogue writes them for the layer after it; this kernel makes them from an
+// fp32 matrix that some other GEMM produced — layer 1 on materialised one-hot rows (two library f16 GEMMs with fp32 output,
+// FastResnet.forward_onehot) — applying what follows the Linear in the network on the way (scale back — per output unit,
+// the weight rows carry their own power-of-two scale —, bias, residual add, ReLU — utils/pytorch_models.py:57-86 with
+// BatchNorm folded): one pass, read 4-8 B, write 4-8 B per element.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr float kF16Safe = 60000.0f;  // |v| above this cannot be split into fp16 halves (fp16 max 65504)
 
@@ -463,8 +452,8 @@ __global__ __launch_bounds__(256) void k_act_split(const float* __restrict__ y, 
                                                    const float* __restrict__ skip, const float* __restrict__ col_scale,
                                                    float alpha, int relu, int64_t m, int64_t n,
                                                    float* __restrict__ x_out /*[m,n] or null*/,
-                                                   _Float16* __restrict__ a3 /*[m,3n], or two planes [2][m][n]*/,
-                                                   int planes, int* __restrict__ overflow) {
+                                                   _Float16* __restrict__ planes /*[2][m][n] or null*/,
+                                                   int* __restrict__ overflow) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t col = ((int64_t)blockIdx.x * 64 + lane) * 4;
     if (col >= n) return;
@@ -500,18 +489,9 @@ __global__ __launch_bounds__(256) void k_act_split(const float* __restrict__ y, 
             lo[k] = (_Float16)(u - (float)hh);
         }
         if (x_out) *reinterpret_cast<float4*>(x_out + r * n + col) = make_float4(v[0], v[1], v[2], v[3]);
-        if (a3 && planes) {  // dca_f16x3_gemm's operand: the high halves [m,n], then the low halves [m,n]
-            *reinterpret_cast<h4*>(a3 + r * n + col) = hi;
-            *reinterpret_cast<h4*>(a3 + (m + r) * n + col) = lo;
-        } else if (a3) {  // element k of the row -> halves 3k..3k+2 = (vh, vl, vh): 24 contiguous bytes per lane
-            h4* row = reinterpret_cast<h4*>(a3 + (r * n + col) * 3);
-            h4 q0, q1, q2;
-            q0[0] = hi[0], q0[1] = lo[0], q0[2] = hi[0], q0[3] = hi[1];
-            q1[0] = lo[1], q1[1] = hi[1], q1[2] = hi[2], q1[3] = lo[2];
-            q2[0] = hi[2], q2[1] = hi[3], q2[2] = lo[3], q2[3] = hi[3];
-            row[0] = q0;
-            row[1] = q1;
-            row[2] = q2;
+        if (planes) {  // dca_f16x3_gemm's operand: the high halves [m,n], then the low halves [m,n]
+            *reinterpret_cast<h4*>(planes + r * n + col) = hi;
+            *reinterpret_cast<h4*>(planes + (m + r) * n + col) = lo;
         }
     }
 }
@@ -608,6 +588,10 @@ int dca_l1_onehot_gemm(const uint8_t* nnet_in, int64_t m, int state_dim, int dep
                        int64_t n_pad, const float* bias, int relu, void* out, int out_dtype, int* overflow, void* stream) {
     DCA_ARG(nnet_in && w_tiles && bias && out && m >= 0 && planes >= 1 && planes <= 3 && n_pad >= 64 && n_pad % 64 == 0);
     DCA_ARG(out_dtype >= DCA_DT_F32 && out_dtype <= DCA_DT_E4M3);
+    if (out_dtype == 3) {  // no DCA_DT_* has this code (dca.h)
+        set_error("dca_l1_onehot_gemm: out_dtype 3 is not an output type");
+        return DCA_E_BADARG;
+    }
     if (!dca_l1_supported(state_dim, depth)) {
         set_error("dca_l1_onehot_gemm: geometry (%d, %d) not instantiated (weight tile must fit LDS)", state_dim, depth);
         return DCA_E_BADARG;
@@ -645,16 +629,15 @@ int dca_l1_onehot_gemm_mx(const uint8_t* nnet_in, int64_t m, int state_dim, int 
 }
 
 int dca_act_split(const float* y, const float* bias, const float* skip, const float* col_scale, double alpha, int relu,
-                  int64_t m, int64_t n, float* x_out, void* a3, int a3_planes, int* overflow, void* stream) {
-    DCA_ARG(y && (a3 || x_out) && m >= 0 && n >= 4 && n % 4 == 0 && m * n < (1ll << 40));
+                  int64_t m, int64_t n, float* x_out, void* planes, int* overflow, void* stream) {
+    DCA_ARG(y && (planes || x_out) && m >= 0 && n >= 4 && n % 4 == 0 && m * n < (1ll << 40));
     if (m == 0) return 0;
     const unsigned gx = (unsigned)((n + 255) / 256);
     int64_t gy = 4096 / gx;
     if (gy > (m + 15) / 16) gy = (m + 15) / 16;
     if (gy < 1) gy = 1;
     hipLaunchKernelGGL(k_act_split, dim3(gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, y, bias, skip, col_scale,
-                       (float)alpha, relu,
-                       m, n, x_out, reinterpret_cast<_Float16*>(a3), a3_planes, overflow);
+                       (float)alpha, relu, m, n, x_out, reinterpret_cast<_Float16*>(planes), overflow);
     return launch_check("k_act_split");
 }
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DCA_ABI_VERSION 5
+#define DCA_ABI_VERSION 6
 
 /* library error codes (negative; positive values are hipError_t) */
 #define DCA_E_BADARG (-1)
@@ -56,7 +56,7 @@ extern "C" {
 #define DCA_DT_F32 0
 #define DCA_DT_F16 1
 #define DCA_DT_BF16 2
-#define DCA_DT_F16X3 3 /* dca_l1_onehot_gemm only: the f16x3 split operand (vh, vl, vh) per element, [m, 3*n_pad] fp16 */
+/* (3 is unused: dca_l1_onehot_gemm refuses it) */
 #define DCA_DT_F16_PLANES 4 /* dca_l1_onehot_gemm only: dca_f16x3_gemm's operand — [m, n_pad] fp16 high halves, then [m, n_pad] low halves */
 #define DCA_DT_E4M3 5 /* dca_l1_onehot_gemm only: OCP fp8 e4m3 bytes, saturating (dca_gemm8's operand; the caller folds the activation
                          scale into the layer's weights and bias) */
@@ -323,8 +323,8 @@ int dca_bn_train_backward(const float* dy, const float* x, const float* y /*need
  * materialises the one-hot matrix.  Weights arrive as `planes` bf16 planes whose sum is the fp32 weight matrix
  * (planes = 3: exact fp32 products => an fp32 GEMM on the bf16 MFMA pipes; 2 for fp16 weights; 1 for bf16), tiled as
  * [n_pad/64][planes][k_pad/8][64][8] (k_pad = dca_l1_kpad(state_dim, depth), zero padded; deepcubea_amd/utils/
- * pytorch_models.py:l1_weight_tiles builds it).  out: [m, n_pad] in out_dtype (DCA_DT_*), row stride n_pad; DCA_DT_F16X3
- * writes the next f16x3 layer's A operand [m, 3*n_pad] directly (see dca_act_split).
+ * pytorch_models.py:l1_weight_tiles builds it).  out: [m, n_pad] in out_dtype (DCA_DT_*), row stride n_pad; DCA_DT_F16_PLANES
+ * writes the next layer's dca_f16x3_gemm operand directly ([m, n_pad] fp16 high halves, then [m, n_pad] low halves).
  * K is walked in LDS-sized chunks (cube3: one piece; the sliding puzzles, K up to 2401: 320 one-hot columns at a time).
  * Instantiated for cube3 (54, 6) and the sliding puzzles (16/25/36/49): dca_l1_supported(state_dim, depth) != 0.
  * ------------------------------------------------------------------------------------------------------------------ */
@@ -332,7 +332,7 @@ int dca_l1_supported(int state_dim, int depth);
 int64_t dca_l1_kpad(int state_dim, int depth);
 int dca_l1_onehot_gemm(const uint8_t* nnet_in /*[m, state_dim]*/, int64_t m, int state_dim, int depth, const void* w_tiles,
                        int planes, int64_t n_pad, const float* bias /*[n_pad]*/, int relu, void* out, int out_dtype,
-                       int* overflow /*device flag, set to 1 if a DCA_DT_F16X3 value exceeds fp16; or NULL*/, void* stream);
+                       int* overflow /*device flag, set to 1 if a DCA_DT_F16_PLANES value exceeds fp16; or NULL*/, void* stream);
 
 /* The same layer in the NON-parity fp8 mode, on gfx950's f8f6f4 matrix pipe (csrc/dca_mlp8.hip): a one-hot row is exact in
  * OCP e4m3, so with the layer's weights as e4m3 bytes + one fp32 scale per output unit (what every other fp8 layer carries)
@@ -364,15 +364,12 @@ int dca_l1_embed(const uint8_t* nnet_in /*[m, state_dim]*/, int64_t m, int state
                  const float* bias /*[n_pad]*/, int relu, void* out, int out_dtype, int* overflow /*device flag or NULL*/,
                  void* stream);
 
-/* Glue of the fp32-accurate "f16x3" dense layers (csrc/dca_mlp.hip): v = relu?(y*alpha*col_scale + bias (+ skip)) over the row-major
- * fp32 GEMM output y [m, n]; writes the next layer's A operand a3 [m, 3n] fp16, a3[3k..3k+2] = (vh, vl, vh) with
- * vh = f16(v), vl = f16(v - vh), and, if x_out != NULL, v itself (the next residual block's skip).  With the weights as
- * W3[3k..3k+2] = (wh, wh, wl) (row n pre-scaled by the power of two 1/(alpha*col_scale[n])) one f16 GEMM with fp32 output reproduces the fp32 layer
- * utils/pytorch_models.py:57-86 computes (BatchNorm folded) to fp32 accuracy.  n % 4 == 0.                            */
+/* Glue in front of the fp32-accurate "f16x3" dense layers (csrc/dca_mlp.hip): v = relu?(y*alpha*col_scale + bias (+ skip)) over a
+ * row-major fp32 GEMM output y [m, n] (layer 1 on materialised one-hot rows); writes dca_f16x3_gemm's operand `planes` — [m, n]
+ * fp16 high halves vh = f16(v), then [m, n] low halves vl = f16(v - vh) — and / or, if x_out != NULL, v itself.  n % 4 == 0. */
 int dca_act_split(const float* y, const float* bias /*[n] or NULL*/, const float* skip /*[m,n] or NULL*/,
                   const float* col_scale /*[n] or NULL: per-output-unit inverse weight scale*/, double alpha, int relu,
-                  int64_t m, int64_t n, float* x_out /*[m,n] or NULL*/, void* a3 /*[m,3n] fp16 or NULL*/,
-                  int a3_planes /*!= 0: write dca_f16x3_gemm's operand instead: [m,n] high halves then [m,n] low halves*/,
+                  int64_t m, int64_t n, float* x_out /*[m,n] or NULL*/, void* planes /*[2][m][n] fp16 or NULL*/,
                   int* overflow /*device flag, set to 1 if some |v| > 60000 (not splittable into fp16); or NULL*/,
                   void* stream);
 
@@ -381,7 +378,7 @@ int dca_act_split(const float* y, const float* bias /*[n] or NULL*/, const float
  * of utils/pytorch_models.py:57-86 with BatchNorm folded — as ONE hand-written MFMA kernel with fp32 accuracy on the f16
  * matrix pipes ("f16x3": x = xh + xl, w = wh + wl in fp16; x.w = xl.wh + xh.wl + xh.wh accumulated in fp32; csrc/dca_gemm.hip).
  * Operands are fp16 PLANES: a_h / a_l [m, lda] (high / low halves of the fp32 activations: what this kernel, dca_l1_onehot_gemm
- * (DCA_DT_F16_PLANES), dca_act_split (a3_planes) and dca_split_planes emit), w_h / w_l [n, ldw] (rows = output units,
+ * (DCA_DT_F16_PLANES), dca_act_split and dca_split_planes emit), w_h / w_l [n, ldw] (rows = output units,
  * pre-scaled by the power of two 1 / col_scale[row]).  k % 64 == 0; lda, ldw % 8 == 0; 16-byte aligned bases.
  * Outputs (row stride ldo): out_h / out_l — the result's planes, i.e. the NEXT layer's operand — and / or x_out, the fp32
  * result (the next residual block's skip, or the input of the 1-wide output layer).  overflow: device flag set when a value

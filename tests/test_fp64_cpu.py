@@ -79,7 +79,7 @@ def test_fp64_symbols_declared_and_exported():
     for name in NEW_SYMBOLS:
         assert name in declared and name in _lib.ABI_SYMBOLS and hasattr(L, name)
     assert re.search(r"#define DCA_DT_F64 6\b", hdr) and _lib.DT_F64 == 6
-    assert _lib.lib().dca_abi_version() == 5
+    assert _lib.lib().dca_abi_version() == 6
 
 
 def test_cli_accepts_fp64():

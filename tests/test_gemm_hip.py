@@ -98,23 +98,28 @@ def test_overflow_flag_and_split_planes():
 
 
 @torch.no_grad()
-def test_hand_written_layers_equal_the_library_arrangement(golden):
-    """FastResnet(gemm="hip") (one dca_f16x3_gemm launch per layer) vs round 1's library f16 GEMM + glue kernel on the same
-    split weights: both fp32-accurate, so they agree to a few fp32 ulps of the activations; both within 1e-5 of the reference."""
-    from deepcubea_amd.utils.pytorch_models import FastResnet, ResnetModel
+def test_hand_written_layers_match_the_float64_evaluation(golden):
+    """The fp32 parity mode (layer-1 kernel + one dca_f16x3_gemm launch per dense layer) against an independent evaluation of
+    the same network: within 1e-5 of the reference's values on the fixture rows, and within 1e-5 absolute of
+    `Fp64Resnet.forward64` (float64 throughout, nothing rounded) on 20 000 random rows.
+    Measured once before the library-GEMM arrangement was removed, max |fp32 mode - forward64| on 20 000 seeded random rows
+    (max |h| 1.51): hand-written layers 1.79e-6, library f16 GEMM + glue kernel 1.67e-6 (plain fp32 GEMMs, split=False:
+    2.28e-6)."""
+    from deepcubea_amd.utils.pytorch_models import FastResnet, Fp64Resnet, ResnetModel
     from deepcubea_amd.utils.synthetic_weights import load_synthetic_weights
     full = ResnetModel(54, 6, 5000, 1000, 4, 1, True)
     load_synthetic_weights(full, 2024)
     x = torch.tensor(golden["cube3_resnet_seed2024_x"]).cuda()
     ref = golden["cube3_resnet_seed2024_y"]
-    hip, lib_ = FastResnet(full, gemm="hip").cuda(), FastResnet(full, gemm="library").cuda()
-    yh, yl = hip(x)[:, 0].cpu().numpy(), lib_(x)[:, 0].cpu().numpy()
-    assert np.max(np.abs(yh - ref)) < 1e-5 and np.max(np.abs(yl - ref)) < 1e-5
+    hip = FastResnet(full).cuda()
+    assert np.max(np.abs(hip(x)[:, 0].cpu().numpy() - ref)) < 1e-5
     xb = torch.randint(0, 6, (20000, 54), dtype=torch.uint8, device="cuda")
-    assert float((hip(xb) - lib_(xb)).abs().max()) < 1e-5
+    d = float((hip(xb).double() - Fp64Resnet(full).cuda().forward64(xb)).abs().max())
+    print("max |fp32 parity mode - forward64| =", d)
+    assert d < 1e-5
     # the one-hot entry (geometries fed with one-hot rows) takes the same layers
     assert float((hip.forward_onehot(hip.encode(xb[:700])) - hip(xb[:700])).abs().max()) < 1e-5
-    assert hip.split_fallbacks == 0 and lib_.split_fallbacks == 0
+    assert hip.split_fallbacks == 0
 
 
 def test_f16x3_schedules_agree_bit_for_bit_under_load():

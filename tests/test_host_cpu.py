@@ -25,7 +25,7 @@ def test_library_loads_and_exports_every_declared_symbol():
     L = C.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(L, name), "libdca_hip.so does not export %s" % name
-    assert _lib.lib().dca_abi_version() == 5
+    assert _lib.lib().dca_abi_version() == 6
 
 
 def test_host_tables_match_golden(golden):
@@ -244,28 +244,77 @@ def test_network_weight_layouts_for_the_mfma_paths():
     m = ResnetModel(54, 6, 64, 32, 2, 1, True).eval()
     with torch.no_grad():
         m.bn2.weight[:8] *= 1e3  # spread the folded unit magnitudes
-    f = FastResnet(m, gemm="library")  # (each mode keeps only the operand layout it reads)
-    assert f.split and len(f.split_w) == 5 and len(f.split_wh) == 0 and f.onehot_dtype == torch.float16 and f.in_pad == 384
-    fh = FastResnet(m)  # default: the hand-written kernel's planes
-    assert fh.split and len(fh.split_w) == 0 and len(fh.split_wh) == 5 and len(fh.split_wl) == 5
-    for w3, wh, wl in zip(f.split_w, fh.split_wh, fh.split_wl):
-        v = w3.view(w3.shape[0], -1, 3)
-        assert torch.equal(v[:, :, 0], wh) and torch.equal(v[:, :, 2], wl)
+    f = FastResnet(m)
+    assert f.split and len(f.split_wh) == 5 and len(f.split_wl) == 5 and f.onehot_dtype == torch.float16 and f.in_pad == 384
     from deepcubea_amd.utils.pytorch_models import fold_batchnorm
     fm = fold_batchnorm(m)
     lins = [fm.fc2] + [l for blk in fm.blocks for l in (blk[0], blk[2])]
-    for w3, alpha, bias, lin in zip(f.split_w, f.split_alpha, f.split_b, lins):
+    for wh, wl, alpha, bias, lin in zip(f.split_wh, f.split_wl, f.split_alpha, f.split_b, lins):
         n, k = lin.weight.shape
-        v = w3.float().view(w3.shape[0], -1, 3)            # W3[:, 3k..3k+2] = (wh, wh, wl)
-        assert torch.equal(v[:, :, 0], v[:, :, 1])
-        rec = (v[:, :, 0] + v[:, :, 2]) * alpha[:, None]  # undo the per-unit power-of-two scale
+        assert wh.dtype == torch.float16 and wl.dtype == torch.float16 and wh.shape == wl.shape
+        rec = (wh.float() + wl.float()) * alpha[:, None]  # undo the per-unit power-of-two scale
         assert torch.all(torch.log2(alpha) == torch.round(torch.log2(alpha)))
         err = (rec[:n, :k] - lin.weight.detach()).abs().amax(dim=1) / lin.weight.detach().abs().amax(dim=1)
-        assert float(err.max()) <= 2.0 ** -20 and torch.all(rec[n:] == 0) and torch.allclose(bias[:n], lin.bias.detach())
+        assert float(err.max()) <= 2.0 ** -20 and torch.all(rec[n:] == 0) and torch.all(rec[:, k:] == 0)
+        assert torch.equal(bias[:n], lin.bias.detach()) and torch.all(bias[n:] == 0)
     oh = torch.zeros(5, f.in_pad)
     oh[:, ::6] = 1.0
     with torch.no_grad():  # host path of the same module = plain fp32 GEMMs
         assert torch.allclose(f.forward_onehot(oh), m.forward_onehot(oh[:, :324]), atol=1e-5)
+
+
+def test_padded_layers_is_the_float64_fold_zero_padded_and_the_constant_one_unit_is_exact():
+    """`padded_layers` (the re-layout FastResnet, Fp8Resnet and Fp64Resnet share): every pair holds `fold_batchnorm64`'s values
+    inside the padding and exactly 0 outside; `constant_one_bias` computes the block that explicit biases compute."""
+    from deepcubea_amd.utils.pytorch_models import ResnetModel, _pad_dim, constant_one_bias, fold_batchnorm64, padded_layers
+    torch.manual_seed(5)
+    m = ResnetModel(54, 6, 70, 40, 2, 1, True).eval()
+    with torch.no_grad():
+        for bn in [m.bn1, m.bn2] + [b for blk in m.blocks for b in (blk[1], blk[3])]:
+            bn.running_mean.uniform_(-1, 1), bn.running_var.uniform_(0.5, 2.0)
+            bn.weight.uniform_(0.5, 1.5), bn.bias.uniform_(-0.5, 0.5)
+    layers, (wo, bo) = padded_layers(m)
+    want, (wo_ref, bo_ref) = fold_batchnorm64(m)
+    h1p, rp = _pad_dim(70, 0), _pad_dim(40, 1)
+    assert (h1p, rp) == (128, 64) and len(layers) == len(want) == 6
+    assert [tuple(w.shape) for w, _ in layers] == [(h1p, 324), (rp, h1p)] + [(rp, rp)] * 4
+    for (w, b), (wr, br) in zip(layers, want):
+        n, k = wr.shape
+        assert w.dtype == torch.float64 and b.dtype == torch.float64 and b.shape == (w.shape[0],)
+        assert torch.equal(w[:n, :k], wr) and torch.equal(b[:n], br)
+        assert torch.all(w[n:] == 0) and torch.all(w[:, k:] == 0) and torch.all(b[n:] == 0)
+    assert wo.dtype == torch.float32 and wo.shape == (1, rp) and torch.equal(wo[:, :40], wo_ref) and torch.all(wo[:, 40:] == 0)
+    assert torch.equal(bo, bo_ref)
+    x = torch.randn(33, rp, dtype=torch.float64).abs()
+    x[:, 40:] = 0.0  # (what the padded units of the residual stream hold)
+    for first, second in zip(layers[2::2], layers[3::2]):
+        (wa, ba), (wb, bb) = first, second
+        explicit = torch.relu(x + torch.relu(x @ wa.t() + ba) @ wb.t() + bb)
+        (wa1, ba1), (wb1, none) = constant_one_bias(first, second, 40)
+        assert none.numel() == 0 and float(ba1[40]) == 1.0 and torch.equal(wb1[:, 40], bb) and torch.equal(wa1, wa)
+        assert torch.equal(ba, first[1]) and torch.equal(wb, second[0])  # (the helper leaves its inputs alone)
+        folded = torch.relu(x + torch.relu(x @ wa1.t() + ba1) @ wb1.t())
+        assert float((folded - explicit).abs().max()) <= 1e-12
+
+
+def test_fp8_network_holds_explicit_bf16_biases_and_clears_the_bases_constant_one_unit():
+    """`Fp8Resnet` right after construction: its biases are the explicit ones at the base's bf16 rounding, and — the KNOWN
+    DEFECT its constructor documents, on which every calibrated scale depends — the constant-one unit is cleared in the
+    base's fp32 bias copies (not in its bf16 biases), so whoever removes that must regenerate the fp8 results knowingly."""
+    from deepcubea_amd.utils.pytorch_models import Fp8Resnet, ResnetModel, padded_layers
+    torch.manual_seed(3)
+    m = ResnetModel(54, 6, 64, 32, 2, 1, True).eval()
+    f = Fp8Resnet(m)
+    b, r = f.base, f.base.res_dim
+    layers, _ = padded_layers(m)
+    assert len(f.bias) == len(layers) - 1 == 5
+    for bias, (_, want) in zip(f.bias, layers[1:]):
+        assert torch.equal(bias, want.float().to(torch.bfloat16).float())
+    assert torch.equal(f.bias[0], b.biases_f32[1])
+    for k in (2, 4):
+        assert float(b.biases[k][r]) == 1.0 and float(b.biases_f32[k][r]) == 0.0
+        assert torch.equal(b.biases_f32[k][:r], b.biases[k][:r].float()) and torch.all(b.biases_f32[k][r + 1:] == 0)
+        assert torch.equal(b.weights[k + 1][:, r].float(), f.bias[k])  # (the second bias still rides in the base's weights)
 
 
 def test_layer1_kernel_choice_by_geometry_and_mode():
@@ -489,6 +538,29 @@ def test_debug_tune_refuses_every_knob_but_the_three_hooks():
     for k in [k for k in range(16) if k not in (2, 5, 10)] + [-1, 16, 1 << 20]:
         assert L.dca_debug_tune(k, 1) == -1, k  # DCA_E_BADARG
         assert "knob %d" % k in L.dca_last_error().decode(), (k, L.dca_last_error())
+
+
+def test_layer1_kernel_refuses_output_type_code_3_before_any_hip_call():
+    """No DCA_DT_* carries code 3: dca_l1_onehot_gemm refuses it with DCA_E_BADARG and an error text that names the value,
+    before any HIP call (no device needed: host buffers stand in, and stay as they were); the bindings take
+    split=False|"planes" and want_a3="planes"|False only and raise on anything else before the library is called."""
+    import ctypes as C
+    from deepcubea_amd import _lib
+    L = _lib.lib()
+    m, n_pad = 8, 64
+    x, tiles, bias = torch.zeros(m, 54, dtype=torch.uint8), torch.zeros(3 * 336 * 64, dtype=torch.bfloat16), torch.zeros(n_pad)
+    out = torch.full((m, 3 * n_pad), -7.0, dtype=torch.float16)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = L.dca_l1_onehot_gemm(p(x), C.c_int64(m), 54, 6, p(tiles), 3, C.c_int64(n_pad), p(bias), 1, p(out), 3, C.c_void_p(0),
+                              C.c_void_p(0))
+    assert rc == -1 and "out_dtype 3" in L.dca_last_error().decode(), (rc, L.dca_last_error())
+    assert bool((out == -7.0).all())
+    assert not hasattr(_lib, "DT_F16X3") and (_lib.DT_F16_PLANES, _lib.DT_E4M3, _lib.DT_F64) == (4, 5, 6)
+    for bad in (True, 1, "a3"):
+        with pytest.raises(ValueError):
+            _lib.l1_onehot_gemm(x, 6, tiles, 3, bias, True, torch.float32, split=bad)
+        with pytest.raises(ValueError):
+            _lib.act_split(torch.zeros(4, 4), None, None, 1.0, False, True, want_a3=bad)
 
 
 def test_power_of_two_operand_scaling_keeps_fp32_products_on_fp16_planes():

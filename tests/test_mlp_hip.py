@@ -71,8 +71,8 @@ def test_act_split_kernel_matches_torch():
         assert torch.equal(x, v)  # same fp32 operations in the same order
         hi = v.to(torch.float16)
         lo = (v - hi.float()).to(torch.float16)
-        a3v = a3.view(m, n, 3)  # a3[3k..3k+2] = (vh, vl, vh)
-        assert torch.equal(a3v[:, :, 0], hi) and torch.equal(a3v[:, :, 1], lo) and torch.equal(a3v[:, :, 2], hi)
+        # the planes dca_f16x3_gemm reads on the one-hot-row path: high halves, then low halves
+        assert a3.shape == (2, m, n) and torch.equal(a3[0], hi) and torch.equal(a3[1], lo)
         # the split reproduces v to 2^-21
         assert float((hi.float() + lo.float() - v).abs().max()) <= float(v.abs().max()) * 2.0 ** -21
     a3, x = _lib.act_split(y, b, None, 1.0, True, True, want_a3=False)
@@ -105,21 +105,6 @@ def test_f16x3_split_network_is_fp32_accurate(golden, tiny_resnet):
     m.load_state_dict({k[2:]: torch.tensor(tiny_resnet[k]) for k in tiny_resnet.files if k.startswith("w:")})
     yt = FastResnet(m).cuda()(torch.tensor(tiny_resnet["x"]).cuda())[:, 0].cpu().numpy()
     assert np.max(np.abs(yt - tiny_resnet["y"])) < 1e-5
-
-
-def test_l1_kernel_split_epilogue_equals_act_split_of_its_fp32_output():
-    from deepcubea_amd import _lib
-    from deepcubea_amd.utils.pytorch_models import l1_weight_tiles
-    torch.manual_seed(9)
-    m, n_pad = 1111, 128
-    w = torch.randn(n_pad, 324) * 0.3
-    b = torch.randn(n_pad).cuda()
-    x = torch.randint(0, 6, (m, 54), dtype=torch.uint8).cuda()
-    tiles = l1_weight_tiles(w, 3, _lib.l1_kpad(54, 6)).cuda()
-    y = _lib.l1_onehot_gemm(x, 6, tiles, 3, b, True, torch.float32)
-    a3 = _lib.l1_onehot_gemm(x, 6, tiles, 3, b, True, torch.float32, split=True)
-    want, _ = _lib.act_split(y, None, None, 1.0, False, False)
-    assert a3.shape == (m, 3 * n_pad) and torch.equal(a3, want)
 
 
 def test_f16x3_survives_a_wide_spread_of_unit_scales():
@@ -156,13 +141,38 @@ def test_l1_kernel_planes_epilogue_is_the_split_of_its_fp32_output(D, depth):
     from deepcubea_amd import _lib
     from deepcubea_amd.utils.pytorch_models import l1_weight_tiles
     torch.manual_seed(11)
-    m, n_pad = 777, 128
+    n_pad = 128
     w = torch.randn(n_pad, D * depth) * 0.3
     b = torch.randn(n_pad).cuda()
-    x = torch.stack([torch.randperm(D) for _ in range(m)]).to(torch.uint8).cuda() if depth == D else \
-        torch.randint(0, depth, (m, D), dtype=torch.uint8).cuda()
     tiles = l1_weight_tiles(w, 3, _lib.l1_kpad(D, depth)).cuda()
-    y = _lib.l1_onehot_gemm(x, depth, tiles, 3, b, True, torch.float32)
-    pl = _lib.l1_onehot_gemm(x, depth, tiles, 3, b, True, torch.float32, split="planes")
-    hi = y.to(torch.float16)
-    assert pl.shape == (2, m, n_pad) and torch.equal(pl[0], hi) and torch.equal(pl[1], (y - hi.float()).to(torch.float16))
+    for m in (777, 1111):
+        x = torch.stack([torch.randperm(D) for _ in range(m)]).to(torch.uint8).cuda() if depth == D else \
+            torch.randint(0, depth, (m, D), dtype=torch.uint8).cuda()
+        y = _lib.l1_onehot_gemm(x, depth, tiles, 3, b, True, torch.float32)
+        pl = _lib.l1_onehot_gemm(x, depth, tiles, 3, b, True, torch.float32, split="planes")
+        hi = y.to(torch.float16)
+        assert pl.shape == (2, m, n_pad) and torch.equal(pl[0], hi) and torch.equal(pl[1], (y - hi.float()).to(torch.float16))
+        # the other producer of planes (the glue kernel of the one-hot-row path) agrees bit for bit
+        assert torch.equal(pl, _lib.act_split(y, None, None, 1.0, False, False)[0])
+
+
+def test_l1_kernel_refuses_output_type_code_3():
+    """Output type code 3 (no DCA_DT_* carries it) is refused before anything is launched; so are the bindings' other values."""
+    import ctypes as C
+    from deepcubea_amd import _lib
+    from deepcubea_amd.utils.pytorch_models import l1_weight_tiles
+    m, n_pad = 64, 64
+    x = torch.randint(0, 6, (m, 54), dtype=torch.uint8).cuda()
+    tiles = l1_weight_tiles(torch.ones(n_pad, 324), 3, _lib.l1_kpad(54, 6)).cuda()
+    b = torch.ones(n_pad).cuda()
+    out = torch.full((m, 3 * n_pad), -7.0, dtype=torch.float16, device="cuda")
+    rc = _lib.lib().dca_l1_onehot_gemm(_lib.ptr(x), C.c_int64(m), 54, 6, _lib.ptr(tiles), 3, C.c_int64(n_pad), _lib.ptr(b), 1,
+                                       _lib.ptr(out), 3, _lib.ptr(None), _lib.stream_ptr())
+    assert rc == -1  # DCA_E_BADARG
+    assert "out_dtype 3" in _lib.lib().dca_last_error().decode()
+    torch.cuda.synchronize()
+    assert bool((out == -7.0).all())
+    with pytest.raises(ValueError):
+        _lib.l1_onehot_gemm(x, 6, tiles, 3, b, True, torch.float32, split=True)
+    with pytest.raises(ValueError):
+        _lib.act_split(torch.zeros(4, 4, device="cuda"), None, None, 1.0, False, True, want_a3=True)

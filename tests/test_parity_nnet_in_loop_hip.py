@@ -56,7 +56,7 @@ def _trace_with_network(L, co, env_name, root, w, B, iters, mode, seed):
     rows = max(10000, cli._MIN_NNET_ROWS)  # what `--nnet_batch_size 10000` (train.sh) becomes in the CLI (_nnet_rows)
     if mode == "dedup_first":  # astar.py's default here: _load_heuristic + BwasEngine(packed=True)
         fast = FastResnet(net).cuda()
-        assert fast.split and fast.gemm == "hip"
+        assert fast.split and len(fast.split_wh) > 0  # the fp32 parity mode on dca_f16x3_gemm
         hfn = nnet_utils.get_heuristic_fn_dev(fast, clip_zero=False, batch_size=rows)
         if fast.uses_l1_kernel:
             eng = BwasEngine(env_name, w, B, max_nodes=iters * M + (1 << 20), packed=True)
