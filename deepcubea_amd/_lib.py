@@ -698,17 +698,27 @@ def quant_e4m3(x: torch.Tensor, scale: float) -> torch.Tensor:
     return out
 
 
-def head_gemv(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+def _row_view(t: torch.Tensor, even: bool) -> bool:
+    """A 2-d device view whose rows are contiguous and do not overlap (row stride >= width; even where the kernel loads pairs)."""
+    return (t.is_cuda and t.dim() == 2 and (t.shape[1] == 0 or t.stride(1) == 1) and t.stride(0) >= t.shape[1]
+            and not (even and t.stride(0) % 2))
+
+
+def head_gemv(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out_dtype: torch.dtype = torch.float32,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Output layer (dca_head_gemv): x [m, k] fp32 / fp16 / bf16 / float64 (rows may be strided), w [n_out, k] fp32, bias [n_out] fp32
     -> [m, n_out] fp32, summed in float64 in a fixed order (a row's bits do not depend on m or on the row's position) and rounded
-    once.  out_dtype=torch.float64 (float64 rows only, dca_head_gemv64): the same sum, not rounded."""
+    once.  out_dtype=torch.float64 (float64 rows only, dca_head_gemv64): the same sum, not rounded.  `out`: a contiguous
+    [m, n_out] tensor of out_dtype to write into."""
     dts = {**_TORCH_DT, torch.float64: DT_F64}
     assert x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype in dts
     assert w.dtype == torch.float32 and w.is_contiguous() and w.shape[1] == x.shape[1]
     assert bias is None or (bias.dtype == torch.float32 and bias.numel() == w.shape[0])
     assert out_dtype == torch.float32 or (out_dtype == torch.float64 and x.dtype == torch.float64)
     m, k = x.shape
-    out = torch.empty((m, w.shape[0]), dtype=out_dtype, device=x.device)
+    if out is None:
+        out = torch.empty((m, w.shape[0]), dtype=out_dtype, device=x.device)
+    assert out.dtype == out_dtype and tuple(out.shape) == (m, w.shape[0])
     if m == 0:
         return out
     if out_dtype == torch.float64:
@@ -723,30 +733,38 @@ def head_gemv(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], ou
 def gemm64(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], skip: Optional[torch.Tensor], relu: bool,
            out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One dense layer of the fp64 mode (dca_gemm64): relu?(a . w^T + bias (+ skip)), a [m, k] / w [n, k] / bias [n] / skip [m, n]
-    float64, f64 MFMA, every element summed over k in ascending order.  `out` may be `skip` (in place)."""
-    assert a.dtype == torch.float64 and w.dtype == torch.float64 and a.is_contiguous() and w.is_contiguous()
+    float64, f64 MFMA, every element summed over k in ascending order.  `out` may be `skip` (in place).  a, w, skip and out may
+    be row-strided views (stride(1) == 1, row stride >= width; a's and w's even): their row strides go to the kernel as lda,
+    ldw and ldo, and skip must have out's."""
+    assert a.dtype == torch.float64 and w.dtype == torch.float64 and _row_view(a, True) and _row_view(w, True)
     m, k = a.shape
     n = w.shape[0]
     assert w.shape[1] == k and (bias is None or (bias.dtype == torch.float64 and bias.numel() == n and bias.is_contiguous()))
-    assert skip is None or (skip.dtype == torch.float64 and skip.shape == (m, n) and skip.is_contiguous())
     if out is None:
         out = torch.empty((m, n), dtype=torch.float64, device=a.device)
-    assert out.dtype == torch.float64 and out.shape == (m, n) and out.is_contiguous() and out.data_ptr() != a.data_ptr()
+    assert out.dtype == torch.float64 and tuple(out.shape) == (m, n) and _row_view(out, False) and out.data_ptr() != a.data_ptr()
+    assert skip is None or (skip.dtype == torch.float64 and tuple(skip.shape) == (m, n) and _row_view(skip, False)
+                            and skip.stride(0) == out.stride(0))  # one ldo for both
     assert skip is None or skip.data_ptr() == out.data_ptr() or skip.data_ptr() != a.data_ptr()
-    check(lib().dca_gemm64(ptr(a), C.c_int64(m), int(k), C.c_int64(k), ptr(w), int(n), C.c_int64(k), ptr(bias), ptr(skip), int(relu),
-                           ptr(out), C.c_int64(n), stream_ptr()), "dca_gemm64")
+    vp = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+    check(lib().dca_gemm64(vp(a), C.c_int64(m), int(k), C.c_int64(a.stride(0)), vp(w), int(n), C.c_int64(w.stride(0)), ptr(bias),
+                           vp(skip), int(relu), vp(out), C.c_int64(out.stride(0)), stream_ptr()), "dca_gemm64")
     return out
 
 
-def l1_embed64(states_nnet: torch.Tensor, depth: int, w_t: torch.Tensor, bias: torch.Tensor, relu: bool) -> torch.Tensor:
+def l1_embed64(states_nnet: torch.Tensor, depth: int, w_t: torch.Tensor, bias: torch.Tensor, relu: bool,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Layer 1 of the fp64 mode as an embedding sum (dca_l1_embed64): relu?(b1 + sum_pos w_t[pos * depth + s[pos]]) in float64
-    (bias first, positions ascending) from the uint8 rows; w_t = W1^T float64 [state_dim * depth, n_pad] -> [m, n_pad] float64."""
+    (bias first, positions ascending) from the uint8 rows; w_t = W1^T float64 [state_dim * depth, n_pad] -> [m, n_pad] float64.
+    The entry point takes no row strides: a strided view of the states is packed first, `out` (optional) is contiguous."""
     x = _u8(states_nnet)
     m, d = x.shape
     n_pad = bias.numel()
     assert w_t.dtype == torch.float64 and bias.dtype == torch.float64 and w_t.is_contiguous() and bias.is_contiguous()
     assert tuple(w_t.shape) == (d * depth, n_pad)
-    out = torch.empty((m, n_pad), dtype=torch.float64, device=x.device)
+    if out is None:
+        out = torch.empty((m, n_pad), dtype=torch.float64, device=x.device)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (m, n_pad)
     if m == 0:
         return out
     check(lib().dca_l1_embed64(ptr(x), C.c_int64(m), int(d), int(depth), ptr(w_t), C.c_int64(n_pad), ptr(bias), int(relu), ptr(out),
