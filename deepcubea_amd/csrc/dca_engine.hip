@@ -203,67 +203,136 @@ __device__ __forceinline__ uint32_t rank_shares(uint32_t cn) {
     return cn <= (uint32_t)(512 * 16) ? (cn + 1023u) / 1024u : 1u;  // (512 * 16 = kLdsEnt: larger bins stream through one workgroup)
 }
 
-struct Eng {
+// The engine's arrays live in global memory, and the kernels say so: every pointer of the DEVICE view of an instance
+// descriptor (Eng, what the kernels read) is an address-space-1 pointer, so its loads / stores / atomics are global_*
+// instructions with a scalar base that count on vmcnt alone (a pointer loaded from memory is otherwise generic: flat_*
+// accesses, which count on vmcnt AND lgkmcnt, so that every wait drains every queue), and uniform control-block reads
+// become scalar loads.  The HOST view (EngH, what the host fills in and uploads) holds plain pointers; same layout.
+// (Only the device compilation pass sees the address space: the host pass parses the kernels too, without the device
+// language's implicit conversions between a global and a generic pointer, and never runs them.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DCA_GLOBAL __attribute__((address_space(1)))
+#else
+#define DCA_GLOBAL
+#endif
+template <class T>
+using gp = T DCA_GLOBAL*;  // pointer into global memory
+template <class T>
+using gr = T DCA_GLOBAL&;
+// four bytes of a byte row as one word (node rows start at id * D: not word aligned for every D)
+typedef uint32_t __attribute__((aligned(1), may_alias)) unaligned_u32;
+__device__ __forceinline__ uint32_t load_word(gp<const uint8_t> p) { return *(gp<const unaligned_u32>)p; }
+template <class T, bool DEV>
+struct EngPtr {
+    typedef T* type;
+};
+template <class T>
+struct EngPtr<T, true> {
+    typedef gp<T> type;
+};
+// a global pointer as the generic one (library calls that take generic pointers; after inlining the access is still global_*)
+template <class T>
+__device__ __forceinline__ T* generic(gp<T> p) {
+    return (T*)p;
+}
+// the atomics on words in global memory (unqualified calls inside this namespace pick these for a gp<T>, HIP's own for a
+// generic or LDS pointer)
+using ::atomicAdd;
+using ::atomicCAS;
+using ::atomicExch;
+using ::atomicMax;
+using ::atomicMin;
+template <class T, class V>
+__device__ __forceinline__ T atomicAdd(gp<T> p, V v) {
+    return ::atomicAdd(generic(p), (T)v);
+}
+template <class T, class V>
+__device__ __forceinline__ T atomicMin(gp<T> p, V v) {
+    return ::atomicMin(generic(p), (T)v);
+}
+template <class T, class V>
+__device__ __forceinline__ T atomicMax(gp<T> p, V v) {
+    return ::atomicMax(generic(p), (T)v);
+}
+template <class T, class V>
+__device__ __forceinline__ T atomicExch(gp<T> p, V v) {
+    return ::atomicExch(generic(p), (T)v);
+}
+template <class T, class U, class V>
+__device__ __forceinline__ T atomicCAS(gp<T> p, U cmp, V v) {
+    return ::atomicCAS(generic(p), (T)cmp, (T)v);
+}
+
+template <bool DEV>
+struct EngT {
+    template <class T>
+    using P = typename EngPtr<T, DEV>::type;
     int env, dim, D, A, B, sem, oh_dtype, depth;
     double w;
     float wf;
     uint32_t max_nodes, M, tab_cap, tab_mask;
     uint32_t front_cap;  // entries a FRONT buffer holds: max_nodes + room for the tombstones of kRefillPeriod iterations
-    uint8_t* state;
-    int32_t* g;
-    uint32_t* parent;
-    uint8_t* move;
-    uint8_t* solved;
-    Slot* tab;
-    uint32_t* closed_slots;  // [max_nodes] the CLOSED slots in use, in insertion order: a reset clears these instead of the whole table
-    uint64_t* open_key[4];
-    uint32_t* open_id[4];
+    P<uint8_t> state;
+    P<int32_t> g;
+    P<uint32_t> parent;
+    P<uint8_t> move;
+    P<uint8_t> solved;
+    P<Slot> tab;
+    P<uint32_t> closed_slots;  // [max_nodes] the CLOSED slots in use, in insertion order: a reset clears these instead of the whole table
+    P<uint64_t> open_key[4];
+    P<uint32_t> open_id[4];
     uint32_t f_keep, f_max;  // FRONT hysteresis: refill/spill down to ~f_keep, spill when above f_max
-    uint32_t *hist, *pre, *fill;  // selection histogram, its exclusive prefix [NBIN+1], per-bin fill of the scratch array
-    uint32_t* rhist;              // histogram of BACK (refill), separate: `hist` is maintained across iterations
-    uint32_t* subhist;            // [kMaxLevels][kSub] sub-bin counts of a giant threshold bin, one array per refinement level
+    P<uint32_t> hist, pre, fill;  // selection histogram, its exclusive prefix [NBIN+1], per-bin fill of the scratch array
+    P<uint32_t> rhist;              // histogram of BACK (refill), separate: `hist` is maintained across iterations
+    P<uint32_t> subhist;            // [kMaxLevels][kSub] sub-bin counts of a giant threshold bin, one array per refinement level
     int coop;                     // k_sel_collect's grid is fully resident (single-instance engine): grid barriers allowed
-    uint32_t* coop_off;           // device word, set once a grid barrier found the launch NOT fully resident (the GPU is shared): giant
+    P<uint32_t> coop_off;           // device word, set once a grid barrier found the launch NOT fully resident (the GPU is shared): giant
                                   // bins go to k_rank's streaming path from then on.  Outside the control block: resets do not touch it
-    uint64_t* part;  // [2][kCollectBlocks] per-block key ranges (min, max) of the entries k_front_rebase kept
+    P<uint64_t> part;  // [2][kCollectBlocks] per-block key ranges (min, max) of the entries k_front_rebase kept
     // scratch of the pop: every FRONT entry at or below the threshold bin, grouped by bin (bin f occupies
     // [pre[f], pre[f+1])), and — only for bins too large for LDS — the single-workgroup sub-bin ordering
-    uint64_t* tmp_key;
-    uint32_t* tmp_id;
-    uint16_t* tmp_f;   // bin of every scratch entry (k_rank's thread-per-entry pass over the small bins)
-    uint32_t* tmp_idx;  // FRONT position each scratch entry was taken from (k_rank hands entries back into those slots)
-    uint64_t* ord_key;
-    uint32_t* ord_id;
-    uint32_t* big_list;  // work units of k_rank's large-bin pass: the segments at or below the threshold with more than kTinyBin
+    P<uint64_t> tmp_key;
+    P<uint32_t> tmp_id;
+    P<uint16_t> tmp_f;   // bin of every scratch entry (k_rank's thread-per-entry pass over the small bins)
+    P<uint32_t> tmp_idx;  // FRONT position each scratch entry was taken from (k_rank hands entries back into those slots)
+    P<uint64_t> ord_key;
+    P<uint32_t> ord_id;
+    P<uint32_t> big_list;  // work units of k_rank's large-bin pass: the segments at or below the threshold with more than kTinyBin
                          // entries, one unit per workgroup that shares the segment (segment | share << 16 | shares << 20)
-    uint64_t* pop_key;   // the batch in pop order
-    uint32_t *pop_id, *pop_g;
-    uint32_t *child_slot, *child_next, *child_v0;
-    uint8_t *child_flags, *child_multi;
-    float* child_h;
-    uint8_t* nnet_in;
-    uint8_t* onehot;
-    uint8_t* root_nnet;
-    int32_t* d_moves;
-    Ctl* ctl;
-    unsigned long long* prof;  // [P_COUNT][kProfSlots][2] device wall-clock stamps (min start, max end) or null
+    P<uint64_t> pop_key;   // the batch in pop order
+    P<uint32_t> pop_id, pop_g;
+    P<uint32_t> child_slot, child_next, child_v0;
+    P<uint8_t> child_flags, child_multi;
+    P<float> child_h;
+    P<uint8_t> nnet_in;
+    P<uint8_t> onehot;
+    P<uint8_t> root_nnet;
+    P<int32_t> d_moves;
+    P<Ctl> ctl;
+    P<unsigned long long> prof;  // [P_COUNT][kProfSlots][2] device wall-clock stamps (min start, max end) or null
     // dedup-first ("packed") stepping: only the children that survive the CLOSED check reach the heuristic
-    uint32_t* kept_pos;   // [M] row of child j in the packed batch (NIL = dropped)
-    uint32_t* pk_n;       // rows packed this iteration, shared by every instance of the engine
-    uint32_t* pk_src;     // [K*M] packed row -> instance*M + child index
-    uint8_t* pk_nnet;     // [K*M, D] network-input rows of the kept children
-    uint8_t* pk_onehot;   // [K*M, pk_stride] one-hot rows (pk_dtype), tail of each row zero
-    const float* pk_h;    // [K*M] heuristic of the packed rows (written by the caller between the two halves)
+    P<uint32_t> kept_pos;   // [M] row of child j in the packed batch (NIL = dropped)
+    P<uint32_t> pk_n;       // rows packed this iteration, shared by every instance of the engine
+    P<uint32_t> pk_src;     // [K*M] packed row -> instance*M + child index
+    P<uint8_t> pk_nnet;     // [K*M, D] network-input rows of the kept children
+    P<uint8_t> pk_onehot;   // [K*M, pk_stride] one-hot rows (pk_dtype), tail of each row zero
+    P<const float> pk_h;    // [K*M] heuristic of the packed rows (written by the caller between the two halves)
     uint32_t pk_stride, inst;
     int pk_dtype;
 };
+typedef EngT<true> Eng;    // device view
+typedef EngT<false> EngH;  // host view
+static_assert(sizeof(Eng) == sizeof(EngH) && alignof(Eng) == alignof(EngH), "the two views of an instance descriptor share one layout");
+static_assert(offsetof(Eng, state) == offsetof(EngH, state) && offsetof(Eng, ctl) == offsetof(EngH, ctl) &&
+                  offsetof(Eng, pk_dtype) == offsetof(EngH, pk_dtype),
+              "the two views of an instance descriptor share one layout");
 
-__device__ __forceinline__ const IterState& st_cur(const Ctl* c) { return c->S[c->iters & 1]; }
-__device__ __forceinline__ const IterState& st_next(const Ctl* c) { return c->S[(c->iters + 1) & 1]; }
+__device__ __forceinline__ gr<const IterState> st_cur(gp<const Ctl> c) { return c->S[c->iters & 1]; }
+__device__ __forceinline__ gr<const IterState> st_next(gp<const Ctl> c) { return c->S[(c->iters + 1) & 1]; }
 
 // the binning a rebase iteration installs (k_front_rebase recounts under it, k_sel_scan records it): FRONT's exact key range,
 // its top raised to the tier threshold — no key above T enters FRONT before the next rebase
-__device__ __forceinline__ void fresh_binning(const Ctl* c, uint32_t buf, uint64_t& kmin, uint32_t& shift) {
+__device__ __forceinline__ void fresh_binning(gp<const Ctl> c, uint32_t buf, uint64_t& kmin, uint32_t& shift) {
     kmin = c->rng[buf].kmin;
     uint64_t kmax = c->rng[buf].kmax;
     const uint64_t T = c->T;
@@ -302,10 +371,16 @@ __device__ __forceinline__ void prof_end(const Eng& E, int kid) {
         atomicMax(E.prof + ((size_t)kid * kProfSlots + (blockIdx.x & (kProfSlots - 1))) * 2 + 1, (unsigned long long)wall_clock64());
 }
 
+// coop_off is set by a workgroup of k_sel_collect while the others of the same launch may still be reading it: an atomic load,
+// never a plain (scalar, cached) one
+__device__ __forceinline__ bool coop_is_off(const Eng& E) {
+    return __hip_atomic_load(E.coop_off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+}
+
 // ---------------------------------------------------------------------------------------------
 // wave-aggregated append to the live OPEN buffer (+ running min/max of its keys)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void open_append(const Eng& E, Ctl* c, uint32_t buf, bool pred, uint64_t key, uint32_t id) {
+__device__ __forceinline__ void open_append(const Eng& E, gp<Ctl> c, uint32_t buf, bool pred, uint64_t key, uint32_t id) {
     unsigned long long mask = __ballot(pred);
     if (mask == 0) return;
     int lane = threadIdx.x & 63;
@@ -425,7 +500,7 @@ __device__ __forceinline__ Pos3 block_reserve3(uint32_t cntA, uint32_t cntB, uin
 
 // K-way variant: cnt[k] slots wanted in the array behind ctr[k]; pos[k] receives the first slot
 template <int NT, int K>
-__device__ __forceinline__ void block_reserveK(const uint32_t (&cnt)[K], uint32_t* const (&ctr)[K], uint32_t (&pos)[K],
+__device__ __forceinline__ void block_reserveK(const uint32_t (&cnt)[K], const gp<uint32_t> (&ctr)[K], uint32_t (&pos)[K],
                                                uint32_t* sh /*K*NW+K*/) {
     constexpr int NW = NT / 64;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -461,7 +536,7 @@ __device__ __forceinline__ void block_reserveK(const uint32_t (&cnt)[K], uint32_
 }
 
 // fold a thread's running key range into a buffer's kmin/kmax (one atomic per wave, only if it helps)
-__device__ __forceinline__ void fold_range(Ctl* c, uint32_t buf, uint64_t kmn, uint64_t kmx) {
+__device__ __forceinline__ void fold_range(gp<Ctl> c, uint32_t buf, uint64_t kmn, uint64_t kmx) {
     for (int o = 32; o > 0; o >>= 1) {
         uint64_t a = __shfl_xor(kmn, o), b = __shfl_xor(kmx, o);
         kmn = a < kmn ? a : kmn;
@@ -482,11 +557,11 @@ __device__ __forceinline__ void fold_range(Ctl* c, uint32_t buf, uint64_t kmn, u
 // random 16-byte stores then), the table has never been cleared, or the last iteration was abandoned between its probe and
 // its commit (`force`: slots were claimed that the list does not hold yet).  Both kernels are enqueued; each one looks at the
 // previous search's count (still in the control block: k_reset runs behind them) and one of them returns at once.
-__device__ __forceinline__ bool clear_by_list(const Ctl* c, uint32_t cap, int force) {
+__device__ __forceinline__ bool clear_by_list(gp<const Ctl> c, uint32_t cap, int force) {
     return !force && (uint64_t)c->closed_n.v * 8ull < (uint64_t)cap;
 }
 __global__ void k_init_table(Slot* tab, uint32_t cap, const Ctl* c, int force) {
-    if (clear_by_list(c, cap, force)) return;
+    if (clear_by_list((gp<const Ctl>)c, cap, force)) return;
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t stride = gridDim.x * blockDim.x;
     for (; i < cap; i += stride) {
@@ -496,7 +571,7 @@ __global__ void k_init_table(Slot* tab, uint32_t cap, const Ctl* c, int force) {
     }
 }
 __global__ void k_clear_table_list(Slot* tab, uint32_t cap, const uint32_t* __restrict__ slots, const Ctl* c, int force) {
-    if (!clear_by_list(c, cap, force)) return;
+    if (!clear_by_list((gp<const Ctl>)c, cap, force)) return;
     const uint32_t n = c->closed_n.v;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t sl = slots[i];
@@ -508,7 +583,7 @@ __global__ void k_clear_table_list(Slot* tab, uint32_t cap, const uint32_t* __re
     }
 }
 
-__global__ void k_reset(Eng E) {
+__global__ void k_reset(EngH E) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     Ctl* c = E.ctl;
     memset(c, 0, sizeof(Ctl));
@@ -557,7 +632,7 @@ __global__ void k_reset(Eng E) {
     }
 }
 
-__global__ void k_root_commit(Eng E, const float* h_root) {
+__global__ void k_root_commit(EngH E, const float* h_root) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     Ctl* c = E.ctl;
     if (E.sem != DCA_SEM_PY || c->open_n[c->cur_f].v != 0) return;
@@ -585,14 +660,14 @@ __device__ __forceinline__ uint32_t front_keep(const Eng& E) {
     const uint32_t floor_ = (uint32_t)(kRefillPeriod + 1) * (uint32_t)E.B;
     return E.f_keep > floor_ ? E.f_keep : floor_;
 }
-__device__ __forceinline__ bool need_refill(const Eng& E, const Ctl* c) {
+__device__ __forceinline__ bool need_refill(const Eng& E, gp<const Ctl> c) {
     return c->open_n[c->cur_b].v != c->back_dead.v &&
            c->open_n[c->cur_f].v - c->front_dead.v - c->front_above < (uint32_t)(kRefillPeriod + 1) * (uint32_t)E.B;
 }
 
 __global__ __launch_bounds__(256) void k_refill_hist(const Eng* __restrict__ engs) {
     const Eng& E = engs[blockIdx.y];
-    Ctl* c = E.ctl;
+    gp<Ctl> c = E.ctl;
     if (c->done || !need_refill(E, c)) return;
     Stamp stamp(E, P_REFILL_HIST);
     __shared__ uint32_t lh[NBIN];
@@ -601,7 +676,7 @@ __global__ __launch_bounds__(256) void k_refill_hist(const Eng* __restrict__ eng
     const uint32_t b = c->cur_b, n = c->open_n[b].v;
     const uint64_t kmin = c->rng[b].kmin;
     const uint32_t shift = select_shift(kmin, c->rng[b].kmax);
-    const uint64_t* __restrict__ keys = E.open_key[b];
+    gp<const uint64_t> __restrict__ keys = E.open_key[b];
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         uint64_t k = keys[i];
         if (k == DEAD) continue;
@@ -683,7 +758,7 @@ __device__ __forceinline__ void scan_bins(uint32_t* __restrict__ hist, bool zero
 
 __global__ __launch_bounds__(1024) void k_refill_scan(const Eng* __restrict__ engs) {
     const Eng& E = engs[blockIdx.y];
-    Ctl* c = E.ctl;
+    gp<Ctl> c = E.ctl;
     if (c->done) return;
     Stamp stamp(E, P_REFILL_SCAN);
     // this launch opens a "rebase" iteration: k_front_rebase compacts and recounts FRONT from scratch under a fresh binning right after
@@ -750,7 +825,7 @@ __global__ __launch_bounds__(1024) void k_refill_scan(const Eng* __restrict__ en
 // entries are only the ones that moved, a small fraction of what keeps arriving)
 __global__ __launch_bounds__(256) void k_refill_move(const Eng* __restrict__ engs) {
     const Eng& E = engs[blockIdx.y];
-    Ctl* c = E.ctl;
+    gp<Ctl> c = E.ctl;
     if (c->done || !c->refill) return;
     Stamp stamp(E, P_REFILL_MOVE);
     __shared__ uint32_t sh[2 * 4 + 2];
@@ -760,8 +835,8 @@ __global__ __launch_bounds__(256) void k_refill_move(const Eng* __restrict__ eng
     const uint64_t kmin = c->r_kmin;
     const uint32_t shift = c->r_shift, bstar = c->r_bstar;
     const bool move = c->r_move != 0;  // (false: compaction-only pass, nothing crosses over to FRONT)
-    uint64_t* __restrict__ keys = E.open_key[sb];
-    const uint32_t* __restrict__ ids = E.open_id[sb];
+    gp<uint64_t> __restrict__ keys = E.open_key[sb];
+    gp<const uint32_t> __restrict__ ids = E.open_id[sb];
     constexpr uint32_t ITEMS = 8, TILE = 256 * ITEMS;
     uint64_t fmn = ~0ull, fmx = 0;
     uint32_t moved = 0;
@@ -819,7 +894,7 @@ __global__ __launch_bounds__(256) void k_front_rebase(const Eng* __restrict__ en
     // reservation per 2048-entry tile), recount the selection histogram under a fresh binning and take the exact key
     // range of what is left (the next rebase bins by it)
     const Eng& E = engs[blockIdx.y];
-    Ctl* c = E.ctl;
+    gp<Ctl> c = E.ctl;
     if (c->done) return;
     Stamp stamp(E, P_SEL_HIST);
     __shared__ uint32_t lh[NBIN];
@@ -834,8 +909,8 @@ __global__ __launch_bounds__(256) void k_front_rebase(const Eng* __restrict__ en
     uint64_t kmin;
     uint32_t shift;
     fresh_binning(c, b, kmin, shift);
-    const uint64_t* __restrict__ keys = E.open_key[b];
-    const uint32_t* __restrict__ ids = E.open_id[b];
+    gp<const uint64_t> __restrict__ keys = E.open_key[b];
+    gp<const uint32_t> __restrict__ ids = E.open_id[b];
     constexpr uint32_t ITEMS = 8, TILE = 256 * ITEMS;
     uint64_t fmn = ~0ull, fmx = 0, bmn = ~0ull, bmx = 0;
     const uint32_t ntiles = (n + TILE - 1) / TILE;
@@ -914,7 +989,7 @@ __global__ __launch_bounds__(256) void k_front_rebase(const Eng* __restrict__ en
 // S2: one workgroup — prefix over the bins, threshold bin, spill decision, per-iteration counter reset
 __global__ __launch_bounds__(1024) void k_sel_scan(const Eng* __restrict__ engs, int rebased) {
     const Eng& E = engs[blockIdx.y];
-    Ctl* c = E.ctl;
+    gp<Ctl> c = E.ctl;
     __shared__ uint32_t pre[NBIN + 1];
     __shared__ uint32_t wsum[16];
     __shared__ uint32_t s_spill, s_bstar, s_maxbin, s_giant, s_nbig, s_sp, s_hbin;
@@ -1000,7 +1075,7 @@ __global__ __launch_bounds__(1024) void k_sel_scan(const Eng* __restrict__ engs,
     // A threshold bin too large for k_rank's LDS bucketing (massive cost ties: an integer-valued heuristic makes every
     // f-level one tie group of up to millions of entries) is not handed to k_rank whole: k_sel_collect refines it across
     // the grid first ("giant" iteration) and k_rank only sees the few thousand entries around the batch's end.
-    const bool giant = E.coop && !*E.coop_off && want != 0 && pre[s_bstar + 1] - pre[s_bstar] > kGiantBin;
+    const bool giant = E.coop && !coop_is_off(E) && want != 0 && pre[s_bstar + 1] - pre[s_bstar] > kGiantBin;
     if (giant)
         for (int i = t; i < kMaxLevels * kSub; i += 1024) E.subhist[i] = 0;
     for (int k = 0; k < kBinsPerThread; k++) {
@@ -1171,7 +1246,7 @@ struct SelParams {
 // swap's expected value is stale) or every workgroup — those polling, and those that only become resident after the early ones
 // left — sees the bit and takes the same fallback.  Nothing of the search has been modified before the first barrier.
 enum { BAR_FAIL = 0, BAR_PASS = 1, BAR_BROKEN = 2 };
-__device__ __forceinline__ int collect_grid_barrier(const Eng& E, Ctl* c, CollectLds& L, uint32_t target, bool first) {
+__device__ __forceinline__ int collect_grid_barrier(const Eng& E, gp<Ctl> c, CollectLds& L, uint32_t target, bool first) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave's stores / atomics have left
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1224,14 +1299,15 @@ __device__ __forceinline__ int collect_grid_barrier(const Eng& E, Ctl* c, Collec
 
 // -> BAR_PASS: the batch's segments are collected; BAR_FAIL: the search failed; BAR_BROKEN: the launch is not fully resident,
 // nothing was touched — the caller collects the bins the ordinary way (k_rank then streams the giant bin on one workgroup)
-__device__ __noinline__ int collect_giant(const Eng& E, Ctl* c, CollectLds& L, const SelParams P) {
+// (inlined for the same reason as rank_item: L stays an LDS object, not a generic pointer)
+__device__ __forceinline__ int collect_giant(const Eng& E, gp<Ctl> c, CollectLds& L, const SelParams P) {
     const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const uint32_t n = P.n;
     const uint64_t bkmin = P.kmin;
     const uint32_t shift = P.shift, bstar = P.bstar, want = P.want;
     const uint32_t pre_b = P.pre_b;
-    uint64_t* __restrict__ keys = E.open_key[P.b];
-    const uint32_t* __restrict__ ids = E.open_id[P.b];
+    gp<uint64_t> __restrict__ keys = E.open_key[P.b];
+    gp<const uint32_t> __restrict__ ids = E.open_id[P.b];
     constexpr uint32_t ITEMS = 8, TILE = 256 * ITEMS;
     const uint32_t ntiles = (n + TILE - 1) / TILE;
     uint32_t phase = 0;
@@ -1323,7 +1399,7 @@ __device__ __noinline__ int collect_giant(const Eng& E, Ctl* c, CollectLds& L, c
             }
         }
         __syncthreads();
-        uint32_t* gh = E.subhist + (size_t)lvl * kSub;
+        gp<uint32_t> gh = E.subhist + (size_t)lvl * kSub;
         for (uint32_t i = t; i < (uint32_t)kSub; i += 256)
             if (lh[i]) atomicAdd(&gh[i], lh[i]);
         if (collect_grid_barrier(E, c, L, ++phase * gridDim.x, false) != BAR_PASS) return BAR_FAIL;
@@ -1507,7 +1583,7 @@ __device__ __noinline__ int collect_giant(const Eng& E, Ctl* c, CollectLds& L, c
 template <bool FUSED>
 __global__ __launch_bounds__(256) void k_sel_collect(const Eng* __restrict__ engs) {
     const Eng& E = engs[blockIdx.y];
-    Ctl* c = E.ctl;
+    gp<Ctl> c = E.ctl;
     if (c->done) return;
     Stamp stamp(E, P_SEL_COLLECT);
     extern __shared__ __attribute__((aligned(16))) uint8_t collect_lds[];
@@ -1569,7 +1645,7 @@ __global__ __launch_bounds__(256) void k_sel_collect(const Eng* __restrict__ eng
         P.bstar = L.bstar;
         P.pre_b = L.pre[P.bstar];
         P.cn_star = L.pre[P.bstar + 1] - P.pre_b;
-        P.giant = E.coop && !*E.coop_off && P.cn_star > kGiantBin;
+        P.giant = E.coop && !coop_is_off(E) && P.cn_star > kGiantBin;
         if (blockIdx.x == 0) {
             // the record k_rank (and the rest of the iteration) reads — what k_sel_scan writes in a rebase iteration
             for (uint32_t i = t; i <= (uint32_t)NBIN; i += 256) E.pre[i] = L.pre[i];
@@ -1640,8 +1716,8 @@ __global__ __launch_bounds__(256) void k_sel_collect(const Eng* __restrict__ eng
     const uint32_t n = P.n;
     const uint64_t kmin = P.kmin;
     const uint32_t shift = P.shift, bstar = P.bstar;
-    uint64_t* __restrict__ keys = E.open_key[P.b];
-    const uint32_t* __restrict__ ids = E.open_id[P.b];
+    gp<uint64_t> __restrict__ keys = E.open_key[P.b];
+    gp<const uint32_t> __restrict__ ids = E.open_id[P.b];
     constexpr uint32_t ITEMS = 8, TILE = 256 * ITEMS;
     const uint32_t ntiles = (n + TILE - 1) / TILE;
     uint64_t* st_key = L.u.n.st_key;
@@ -1783,7 +1859,7 @@ struct RankShared {
 };
 
 // one entry of the batch at its pop rank
-__device__ __forceinline__ void emit_pop(const Eng& E, Ctl* c, uint32_t rank, uint64_t key, uint32_t id) {
+__device__ __forceinline__ void emit_pop(const Eng& E, gp<Ctl> c, uint32_t rank, uint64_t key, uint32_t id) {
     E.pop_key[rank] = key;
     E.pop_id[rank] = id;  // flag included: k_expand masks it (and writes the parents' path costs, pop_g)
     if (id & ID_SOLVED) {  // rare: a goal among the popped — nothing else in the pop reads the node pool
@@ -1798,7 +1874,7 @@ __device__ __forceinline__ void emit_pop(const Eng& E, Ctl* c, uint32_t rank, ui
 // (E.tmp_idx[r]; any one-to-one assignment will do).  FRONT's physical size and key range do not change.
 // One ranked entry: into the batch (pop order) or back to FRONT.  Wave-collective (one returning global atomic per
 // wave) — fine once per thread (the small-bin pass), NOT inside a loop: the large-bin path uses ret_put.
-__device__ __forceinline__ void emit_ranked(const Eng& E, Ctl* c, uint32_t nf, bool live, uint32_t rank, uint32_t want,
+__device__ __forceinline__ void emit_ranked(const Eng& E, gp<Ctl> c, uint32_t nf, bool live, uint32_t rank, uint32_t want,
                                             uint64_t key, uint32_t id) {
     if (live && rank < want) emit_pop(E, c, rank, key, id);
     const bool back = live && rank >= want;
@@ -1818,7 +1894,7 @@ __device__ __forceinline__ void emit_ranked(const Eng& E, Ctl* c, uint32_t nf, b
 // The entries a work item hands back take return numbers of ONE reservation made for the whole item; their positions
 // inside it come from an LDS counter.  (A returning global atomic per wave and loop round, sixteen rounds deep, was what
 // made this path take 20-45 us.)
-__device__ __forceinline__ void ret_begin(Ctl* c, RankShared& S, uint32_t nf, uint32_t count) {
+__device__ __forceinline__ void ret_begin(gp<Ctl> c, RankShared& S, uint32_t nf, uint32_t count) {
     __syncthreads();
     if (threadIdx.x == 0) {
         S.ret_base = count ? atomicAdd(&c->ret_n.v, count) : 0u;
@@ -1829,7 +1905,7 @@ __device__ __forceinline__ void ret_begin(Ctl* c, RankShared& S, uint32_t nf, ui
 struct RetAcc {};  // (nothing to accumulate: an entry that goes back was inside FRONT's key range before)
 // wave-collective (call from wave-uniform control flow): the lanes with `pred` take consecutive return numbers, ONE LDS
 // atomic per wave and call.  (Per-entry atomics on the shared counter — all on one LDS address — cost 30-60 us.)
-__device__ __forceinline__ void ret_put(const Eng& E, Ctl* c, RankShared& S, uint32_t nf, bool pred, uint64_t key,
+__device__ __forceinline__ void ret_put(const Eng& E, gp<Ctl> c, RankShared& S, uint32_t nf, bool pred, uint64_t key,
                                         uint32_t id, RetAcc& acc) {
     const unsigned long long mask = __ballot(pred);
     if (mask == 0) return;
@@ -1844,7 +1920,7 @@ __device__ __forceinline__ void ret_put(const Eng& E, Ctl* c, RankShared& S, uin
         E.open_id[nf][slot] = id;
     }
 }
-__device__ __forceinline__ void ret_end(Ctl* c, uint32_t nf, RetAcc acc) {}
+__device__ __forceinline__ void ret_end(gp<Ctl> c, uint32_t nf, RetAcc acc) {}
 // NJ entries of one thread handed back at once (bit j of `preds`): one LDS atomic per wave for all of them, their slot
 // numbers fetched with unconditional (index-clamped) loads — all in flight together — then predicated stores.  A
 // ret_put per entry made every round wait for its own E.tmp_idx round trip.  Wave-collective.
@@ -1882,7 +1958,7 @@ __device__ __forceinline__ void ret_put_many(const Eng& E, RankShared& S, uint32
 // inside the bin.  A workgroup takes RT consecutive scratch positions; the bins they belong to form one contiguous
 // range of the scratch array (it is grouped by bin), which is staged into LDS once — together with the bins' offsets —
 // so the all-pairs loops run out of LDS.  Falls back to global loads when the range does not fit.
-__device__ __forceinline__ void rank_small_entries(const Eng& E, Ctl* c, RankShared& S, uint64_t* LK, uint32_t* LI,
+__device__ __forceinline__ void rank_small_entries(const Eng& E, gp<Ctl> c, RankShared& S, uint64_t* LK, uint32_t* LI,
                                                    uint32_t nf, uint32_t p0, uint32_t n_ord, uint32_t want) {
     const uint32_t t = threadIdx.x;
     const uint32_t plast = (p0 + RT - 1 < n_ord ? p0 + RT - 1 : n_ord - 1);
@@ -2048,7 +2124,9 @@ __device__ __forceinline__ void rank_push(RankShared& S, const RankItem& it, uin
 }
 
 // one work item of a bin's workgroup (see the banner above).  All RT threads.  LK / LI: 8192-entry LDS arrays.
-__device__ __noinline__ void rank_item(const Eng& E, Ctl* c, RankShared& S, uint64_t* LK, uint32_t* LI, uint32_t nf,
+// (Inlined into its one call site: as a call it received S / LK / LI as generic pointers, and every LDS access of the ranking
+// was a flat_* instruction; inlined the kernel has no scratch and the same 2 workgroups' worth of registers.)
+__device__ __forceinline__ void rank_item(const Eng& E, gp<Ctl> c, RankShared& S, uint64_t* LK, uint32_t* LI, uint32_t nf,
                                        uint32_t want, RankItem it) {
     const uint32_t t = threadIdx.x;
     const uint64_t* __restrict__ K = (it.src ? E.ord_key : E.tmp_key) + it.off;
@@ -2329,7 +2407,7 @@ __device__ __noinline__ void rank_item(const Eng& E, Ctl* c, RankShared& S, uint
 
 __global__ __launch_bounds__(RT) void k_rank(const Eng* __restrict__ engs) {
     const Eng& E = engs[blockIdx.y];
-    Ctl* c = E.ctl;
+    gp<Ctl> c = E.ctl;
     if (c->done) return;
     Stamp stamp(E, P_RANK);
     __shared__ RankShared S;
@@ -2392,7 +2470,7 @@ __global__ __launch_bounds__(RT) void k_rank(const Eng* __restrict__ engs) {
 // ---------------------------------------------------------------------------------------------
 // The pop's single-thread epilogue (thread 0 of the expansion's workgroup 0): goal bookkeeping and the state the rest
 // of the iteration — and the next one — starts from.
-__device__ __forceinline__ void close_pop(const Eng& E, Ctl* c, const IterState& S0, uint32_t it, uint32_t want,
+__device__ __forceinline__ void close_pop(const Eng& E, gp<Ctl> c, const IterState& S0, uint32_t it, uint32_t want,
                                           uint32_t npop, uint32_t base, bool fail) {
     IterState N = S0;
     if (E.sem == DCA_SEM_PY) {
@@ -2502,7 +2580,7 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
     constexpr int kTileParents = kEngTile;  // shadows the stand-alone kernels' 64 (32 / 64 parents per workgroup measured SLOWER
                                             // also for the launches that write one-hot rows: profiles/r06_engine_ab.txt)
     constexpr int TP = kEngTile;
-    Ctl* c = E.ctl;
+    gp<Ctl> c = E.ctl;
     if (c->done) return;
     Stamp stamp(E, P_EXPAND);
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -2555,11 +2633,11 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
             l_g[r] = (uint32_t)E.g[pid];
         }
         if (r < np && w < WPR) {
-            const uint8_t* row = E.state + (size_t)(E.pop_id[r0 + r] & ID_MASK) * EV::D;
+            gp<const uint8_t> row = E.state + (size_t)(E.pop_id[r0 + r] & ID_MASK) * EV::D;
             uint32_t v = 0;
             // rows start at id*D: read byte-wise only where a word would cross the row end
             if (4 * w + 4 <= EV::D) {
-                __builtin_memcpy(&v, row + 4 * w, 4);
+                v = load_word(row + 4 * w);
             } else {
                 for (int b = 0; 4 * w + b < EV::D; b++) v |= (uint32_t)row[4 * w + b] << (8 * b);
             }
@@ -2592,7 +2670,7 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
             constexpr uint32_t EPC = 16 / OH;
             const uint32_t te = nchild * ROW;
             const uint32_t one16 = E.oh_dtype == DCA_DT_F16 ? 0x3C00u : 0x3F80u;
-            uint8_t* goh = E.onehot + (size_t)j0 * ROW * OH;
+            gp<uint8_t> goh = E.onehot + (size_t)j0 * ROW * OH;
             const uint32_t nch = (te + EPC - 1) / EPC;
             // (one read of the staged row per position; a lane that runs one row past the tile reads the slack behind it — its
             // chunk is never stored)
@@ -2759,13 +2837,13 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
                                 break;
                             }
                             // exact key equality against the representative's state bytes (State.__eq__, cube3.py:23-24)
-                            const uint8_t* rrow = E.state + (size_t)rep * EV::D;
+                            gp<const uint8_t> rrow = E.state + (size_t)rep * EV::D;
                             uint32_t diff = 0;
 #pragma unroll
                             for (int k = 0; k < NWD; k++) {
                                 uint32_t v = 0;
                                 if (4 * k + 4 <= EV::D) {
-                                    __builtin_memcpy(&v, rrow + 4 * k, 4);
+                                    v = load_word(rrow + 4 * k);
                                 } else {
                                     for (int b = 0; 4 * k + b < EV::D; b++) v |= (uint32_t)rrow[4 * k + b] << (8 * b);
                                 }
@@ -2796,11 +2874,11 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
                     const uint32_t rrel = l_qrep[itc] - base;
                     const uint32_t rk = rrel / (uint32_t)EV::A, a2 = rrel - rk * (uint32_t)EV::A;
                     const uint32_t ppid = E.pop_id[rk] & ID_MASK;
-                    const uint8_t* prow = E.state + (size_t)ppid * EV::D;
+                    gp<const uint8_t> prow = E.state + (size_t)ppid * EV::D;
                     uint32_t pw = 0;
                     if (w < (uint32_t)NWD) {
                         if (4 * w + 4 <= (uint32_t)EV::D) {
-                            __builtin_memcpy(&pw, prow + 4 * w, 4);
+                            pw = load_word(prow + 4 * w);
                         } else {
                             for (uint32_t b = 0; 4 * w + b < (uint32_t)EV::D; b++) pw |= (uint32_t)prow[4 * w + b] << (8 * b);
                         }
@@ -2859,15 +2937,16 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
     __syncthreads();
     if (!write_nn) {
         const uint32_t tb = nchild * EV::D;
-        uint8_t* gpool = E.state + ((size_t)base + j0) * EV::D;
+        gp<uint8_t> gpool = E.state + ((size_t)base + j0) * EV::D;
         const uint32_t nfull = tb >> 4;
         for (uint32_t q = threadIdx.x; q < nfull; q += kThreads)
             reinterpret_cast<uint4*>(gpool)[q] = reinterpret_cast<const uint4*>(lst)[q];
+#pragma unroll 1  // (at most 15 bytes)
         for (uint32_t bq = (nfull << 4) + threadIdx.x; bq < tb; bq += kThreads) gpool[bq] = lst[bq];
     } else {
         const uint32_t tb = nchild * EV::D;
-        uint8_t* gpool = E.state + ((size_t)base + j0) * EV::D;
-        uint8_t* gnn = E.nnet_in + (size_t)j0 * EV::D;
+        gp<uint8_t> gpool = E.state + ((size_t)base + j0) * EV::D;
+        gp<uint8_t> gnn = E.nnet_in + (size_t)j0 * EV::D;
         const uint32_t nfull = tb >> 4;
         for (uint32_t q = threadIdx.x; q < nfull; q += kThreads) {
             const uint4 v = reinterpret_cast<const uint4*>(lst)[q];
@@ -2885,6 +2964,7 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
                 reinterpret_cast<uint4*>(gnn)[q] = v;
             }
         }
+#pragma unroll 1
         for (uint32_t bq = (nfull << 4) + threadIdx.x; bq < tb; bq += kThreads) {
             const uint32_t b = lst[bq];
             gpool[bq] = (uint8_t)b;
@@ -2934,11 +3014,11 @@ __device__ __forceinline__ void fix_representative(const Eng& E, uint32_t base, 
 // heuristic runs; the fused stepping decides inside k_commit
 __global__ __launch_bounds__(256) void k_decide(const Eng* __restrict__ engs) {
     const Eng& E = engs[blockIdx.y];
-    Ctl* c = E.ctl;
+    gp<Ctl> c = E.ctl;
     if (c->done) return;
     Stamp stamp(E, P_DECIDE);
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-    const IterState& S1 = st_next(c);
+    gr<const IterState> S1 = st_next(c);
     const uint32_t m = S1.m, base = S1.base;
     if (j >= m) return;
     const uint32_t slot = E.child_slot[j];
@@ -2960,7 +3040,7 @@ template <int ENV, int DIM, int OH>
 __global__ __launch_bounds__(256) void k_pack(const Eng* __restrict__ engs) {
     const Eng& E = engs[blockIdx.y];
     using EV = EnvT<ENV, DIM>;
-    Ctl* c = E.ctl;
+    gp<Ctl> c = E.ctl;
     if (c->done) {  // the host learns it with the packed row count it reads anyway: pk_n[1] = finished instances, [2] = failed ones
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             atomicAdd(&E.pk_n[1], 1u);
@@ -3006,7 +3086,7 @@ __global__ __launch_bounds__(256) void k_pack(const Eng* __restrict__ engs) {
         lrow[q] = (uint8_t)(ENV == DCA_ENV_CUBE3 ? (v * 57u) >> 9 : v);
     }
     __syncthreads();
-    uint8_t* gnn = E.pk_nnet + (size_t)gbase * EV::D;
+    gp<uint8_t> gnn = E.pk_nnet + (size_t)gbase * EV::D;
     for (uint32_t q = threadIdx.x; q < tb; q += 256) gnn[q] = lrow[q];
     if constexpr (OH != 0) {
         constexpr uint32_t ROW = EV::D * EV::DEPTH, EPC = 16 / OH;
@@ -3042,7 +3122,7 @@ __global__ __launch_bounds__(256) void k_pack(const Eng* __restrict__ engs) {
 // — and leaves what the next iteration's opening launch needs before it can look at FRONT (in all but the rebase
 // iterations that launch is k_sel_collect itself, whose workgroups all read these words and none may write them): the
 // size of the next batch, and the per-pop words reset.
-__device__ __forceinline__ void commit_ticket(const Eng& E, Ctl* c) {
+__device__ __forceinline__ void commit_ticket(const Eng& E, gp<Ctl> c) {
     // (FRONT's size and tombstone count only ever change through returning device-scope atomics, each waited for by its
     // workgroup before the barrier below: the last arrival reads them with device-scope loads — no fence needed, and a
     // release fence per workgroup costs microseconds on the launch's critical path)
@@ -3076,13 +3156,13 @@ __device__ __forceinline__ void commit_ticket(const Eng& E, Ctl* c) {
 template <bool FUSED>
 __global__ __launch_bounds__(1024) void k_commit(const Eng* __restrict__ engs, int packed) {
     const Eng& E = engs[blockIdx.y];
-    Ctl* c = E.ctl;
+    gp<Ctl> c = E.ctl;
     if (c->done) return;
     Stamp stamp(E, P_COMMIT);
     __shared__ uint32_t sh[3 * 16 + 3];
     __shared__ uint32_t lh[NBIN];  // this workgroup's pushes into FRONT per selection bin (FRONT's histogram is incremental)
     __shared__ uint64_t red[4][16];
-    const IterState& S1 = st_next(c);
+    gr<const IterState> S1 = st_next(c);
     const uint32_t m = S1.m, base = S1.base;
     const uint32_t fb = c->cur_f, bb = c->cur_b;
     const uint64_t T = c->T;
@@ -3184,7 +3264,7 @@ __global__ __launch_bounds__(1024) void k_commit(const Eng* __restrict__ engs, i
         if (f < hbin) atomicAdd(&lh[f], 1u);
     }
     const uint32_t cnt[3] = {tof ? 1u : 0u, tob ? 1u : 0u, is_new ? 1u : 0u};
-    uint32_t* const ctr[3] = {&c->open_n[fb].v, &c->open_n[bb].v, &c->closed_n.v};
+    const gp<uint32_t> ctr[3] = {&c->open_n[fb].v, &c->open_n[bb].v, &c->closed_n.v};
     uint32_t pos[3];
     block_reserveK<1024, 3>(cnt, ctr, pos, sh);
     // This workgroup's pushes per selection bin -> FRONT's histogram (block_reserveK's barriers have ordered the LDS counts).
@@ -3273,14 +3353,14 @@ __global__ void k_set_weights(Eng* __restrict__ engs, const double* __restrict__
 __global__ __launch_bounds__(256) void k_gather_popped(const Eng* __restrict__ engs, uint8_t* __restrict__ out_states,
                                                        uint8_t* __restrict__ out_flags) {
     const Eng& E = engs[blockIdx.y];
-    const Ctl* c = E.ctl;
+    gp<const Ctl> c = E.ctl;
     const uint32_t B = (uint32_t)E.B, D = (uint32_t)E.D;
     const uint32_t npop = c->done ? 0u : st_next(c).npop;
     for (uint32_t r = blockIdx.x; r < B; r += gridDim.x) {
         uint8_t* dst = out_states + ((size_t)blockIdx.y * B + r) * D;
         if (r < npop) {
             const uint32_t idf = E.pop_id[r];
-            const uint8_t* src = E.state + (size_t)(idf & ID_MASK) * D;
+            gp<const uint8_t> src = E.state + (size_t)(idf & ID_MASK) * D;
             for (uint32_t b = threadIdx.x; b < D; b += blockDim.x) dst[b] = src[b];
             if (threadIdx.x == 0) out_flags[(size_t)blockIdx.y * B + r] = (idf & ID_SOLVED) ? 2 : 1;
         } else {
@@ -3290,7 +3370,7 @@ __global__ __launch_bounds__(256) void k_gather_popped(const Eng* __restrict__ e
     }
 }
 
-__global__ void k_solution(Eng E, int32_t* out /*[0]=len, [1..]=moves root->goal*/, double* path_cost) {
+__global__ void k_solution(EngH E, int32_t* out /*[0]=len, [1..]=moves root->goal*/, double* path_cost) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     Ctl* c = E.ctl;
     out[0] = -1;
@@ -3301,8 +3381,8 @@ __global__ void k_solution(Eng E, int32_t* out /*[0]=len, [1..]=moves root->goal
         n = c->goal_id;
         *path_cost = (double)E.g[n];  // astar.py:229 node.path_cost
     } else {
-        if (!st_cur(c).has_best) return;
-        n = st_cur(c).best_id;
+        if (!st_cur((gp<const Ctl>)c).has_best) return;
+        n = st_cur((gp<const Ctl>)c).best_id;
     }
     int len = 0;
     // astar.py:218-223 walks parents to the root; cpp:337-341 walks while depth > 0
@@ -3335,8 +3415,8 @@ constexpr int kGraphSlots = 48, kGraphChunk = 64;
 
 struct dca_engine {
     int K;
-    Eng E[kMaxInstances];  // host copies; E[i].ctl etc. are device pointers
-    Eng* d_engs;           // device copy of E[0..K)
+    EngH E[kMaxInstances];  // host copies; E[i].ctl etc. are device pointers
+    Eng* d_engs;            // device copy of E[0..K)
     uint8_t* nnet_all;     // [K*M, D]   network-input rows of all instances, contiguous
     uint8_t* onehot_all;   // [K*M, D*depth] or null
     float* h_all;          // [K*M]
@@ -3408,7 +3488,7 @@ inline dim3 gxy(unsigned x, const dca_engine* e) { return dim3(x, (unsigned)e->K
 template <int ENV, int DIM>
 int launch_expand_env(const dca_engine* e, int heur_id, bool want_oh, bool want_nn, hipStream_t s) {
     using TL = Tile<ENV, DIM, kEngTile>;
-    const Eng& E = e->E[0];
+    const EngH& E = e->E[0];
     dim3 g = gxy((E.B + kEngTile - 1) / kEngTile, e), b(kThreads);
     // tile + tables, then the staged child rows (16 parents x A children x D bytes)
     const size_t lds = TL::LDS_BYTES + ((kEngTile * EnvT<ENV, DIM>::A * EnvT<ENV, DIM>::D + 15) / 16) * 16 + 64;  // (+ slack: the one-hot loop peeks one byte past the tile)
@@ -3423,7 +3503,7 @@ int launch_expand_env(const dca_engine* e, int heur_id, bool want_oh, bool want_
 }
 
 int launch_expand(const dca_engine* e, int heur_id, bool want_oh, bool want_nn, hipStream_t s) {
-    const Eng& E = e->E[0];
+    const EngH& E = e->E[0];
     if (E.env == DCA_ENV_CUBE3) return launch_expand_env<DCA_ENV_CUBE3, 0>(e, heur_id, want_oh, want_nn, s);
     if (E.env == DCA_ENV_LIGHTSOUT) return launch_expand_env<DCA_ENV_LIGHTSOUT, 7>(e, heur_id, want_oh, want_nn, s);
     switch (E.dim) {
@@ -3437,7 +3517,7 @@ int launch_expand(const dca_engine* e, int heur_id, bool want_oh, bool want_nn, 
 
 template <int ENV, int DIM>
 int launch_pack_env(const dca_engine* e, hipStream_t s) {
-    const Eng& E = e->E[0];
+    const EngH& E = e->E[0];
     const dim3 g = gxy((E.M + 255) / 256, e), b(256);
     if (E.pk_onehot == nullptr)
         hipLaunchKernelGGL((k_pack<ENV, DIM, 0>), g, b, 0, s, e->d_engs);
@@ -3449,7 +3529,7 @@ int launch_pack_env(const dca_engine* e, hipStream_t s) {
 }
 
 int launch_pack(const dca_engine* e, hipStream_t s) {
-    const Eng& E = e->E[0];
+    const EngH& E = e->E[0];
     if (E.env == DCA_ENV_CUBE3) return launch_pack_env<DCA_ENV_CUBE3, 0>(e, s);
     if (E.env == DCA_ENV_LIGHTSOUT) return launch_pack_env<DCA_ENV_LIGHTSOUT, 7>(e, s);
     switch (E.dim) {
@@ -3486,7 +3566,7 @@ int enqueue_first_half(dca_engine* e, int heur_id, bool with_refill, hipStream_t
 // packed: the dedup-first stepping (the keep flags come from k_decide, before the heuristic runs); otherwise k_commit<true>
 // decides while it pushes
 int enqueue_commit(dca_engine* e, bool packed, hipStream_t s) {
-    const Eng& E = e->E[0];
+    const EngH& E = e->E[0];
     const dim3 g = gxy((E.M + 1023) / 1024, e);
     if (packed)
         hipLaunchKernelGGL(k_commit<false>, g, dim3(1024), 0, s, e->d_engs, 1);
@@ -3511,12 +3591,12 @@ void drop_graphs(dca_engine* e) {
 
 // dca_engine_set_weights_dev writes w / wf of the DEVICE copy only (stream-ordered, no host involvement: ADVICE r05).  Before
 // the host mirror is used as a whole — any upload, any host-side weight setter — the device's weights are read back into it, so
-// that a later upload cannot revert them.  (Kernels that take an Eng by value from the mirror read w only as w * 0 at the root.)
+// that a later upload cannot revert them.  (Kernels that take an EngH by value from the mirror read w only as w * 0 at the root.)
 int pull_dev_weights(dca_engine* e) {
     if (!e->w_dev) return 0;
     DCA_HIP(hipDeviceSynchronize());
-    std::vector<Eng> tmp((size_t)e->K);
-    DCA_HIP(hipMemcpy(tmp.data(), e->d_engs, sizeof(Eng) * (size_t)e->K, hipMemcpyDeviceToHost));
+    std::vector<EngH> tmp((size_t)e->K);
+    DCA_HIP(hipMemcpy(tmp.data(), e->d_engs, sizeof(EngH) * (size_t)e->K, hipMemcpyDeviceToHost));
     for (int i = 0; i < e->K; i++) {
         e->E[i].w = tmp[(size_t)i].w;
         e->E[i].wf = tmp[(size_t)i].wf;
@@ -3527,7 +3607,7 @@ int pull_dev_weights(dca_engine* e) {
 
 int upload_engs(dca_engine* e) {
     if (int rc = pull_dev_weights(e)) return rc;
-    DCA_HIP(hipMemcpy(e->d_engs, e->E, sizeof(Eng) * (size_t)e->K, hipMemcpyHostToDevice));
+    DCA_HIP(hipMemcpy(e->d_engs, e->E, sizeof(EngH) * (size_t)e->K, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -3601,7 +3681,7 @@ int dca_engine_create_multi(dca_engine** out, int env, int dim, double weight, i
     if (!rc) rc = dev_alloc(e, &e->d_engs, K);
     if (!rc) rc = dev_alloc(e, &e->d_cost, 1);
     for (size_t i = 0; i < K && !rc; i++) {
-        Eng& E = e->E[i];
+        EngH& E = e->E[i];
         E.env = env;
         E.dim = dim;
         E.D = D;
@@ -3748,7 +3828,7 @@ int dca_engine_reset_instance(dca_engine* e, int inst, const uint8_t* root, void
     DCA_INST(e, inst);
     DCA_ARG(root != nullptr);
     hipStream_t s = (hipStream_t)stream;
-    Eng& E = e->E[inst];
+    EngH& E = e->E[inst];
     for (int i = 0; i < E.D; i++) DCA_ARG(root[i] < (E.env == DCA_ENV_CUBE3 ? 54 : E.env == DCA_ENV_LIGHTSOUT ? 2 : E.D));
     // the staging block is reused: make sure an earlier reset's copy has left it
     DCA_HIP(hipStreamSynchronize(s));
@@ -3830,7 +3910,7 @@ int dca_engine_enable_packed(dca_engine* e, int onehot_dtype, int64_t onehot_row
         set_error("dca_engine_enable_packed called twice");
         return DCA_E_STATE;
     }
-    const Eng& E0 = e->E[0];
+    const EngH& E0 = e->E[0];
     const int64_t row = (int64_t)E0.D * E0.depth;
     const int esz = onehot_dtype == DCA_DT_F32 ? 4 : 2;
     if (onehot_dtype >= 0) DCA_ARG(onehot_row_stride >= row && (onehot_row_stride * esz) % 16 == 0 && onehot_row_stride < (1 << 20));
@@ -3846,7 +3926,7 @@ int dca_engine_enable_packed(dca_engine* e, int onehot_dtype, int64_t onehot_row
     }
     DCA_HIP(hipHostMalloc((void**)&e->h_pk_n, 64, hipHostMallocDefault));
     for (int i = 0; i < e->K; i++) {
-        Eng& E = e->E[i];
+        EngH& E = e->E[i];
         if (int rc = dev_alloc(e, &E.kept_pos, (size_t)E.M)) return rc;
         E.pk_n = e->pk_n;
         E.pk_src = e->pk_src;
@@ -4138,7 +4218,7 @@ int dca_engine_reset_many(dca_engine* e, const uint8_t* roots_dev, int n, void* 
     if (e->phase != 0)  // (an abandoned half iteration: see dca_engine_reset_instance)
         for (int i = 0; i < e->K; i++) e->tab_cleared[i] = 0;
     for (int i = 0; i < e->K; i++) {
-        Eng& E = e->E[i];
+        EngH& E = e->E[i];
         if (i >= n) {  // parked: every launch of this instance is a no-op until it is reset again
             DCA_HIP(hipMemsetD32Async((hipDeviceptr_t)&E.ctl->done, 1, 1, s));
             continue;
@@ -4184,7 +4264,7 @@ int dca_engine_last_popped(dca_engine* e, uint8_t* states, uint8_t* flags, void*
         set_error("dca_engine_last_popped outside an iteration (call it between pop_expand and commit)");
         return DCA_E_STATE;
     }
-    const Eng& E = e->E[0];
+    const EngH& E = e->E[0];
     const unsigned gx = (unsigned)(E.B < 1024 ? E.B : 1024);
     hipLaunchKernelGGL(k_gather_popped, gxy(gx, e), dim3(64), 0, (hipStream_t)stream, e->d_engs, states, flags);
     return launch_check("k_gather_popped");
@@ -4281,7 +4361,7 @@ int dca_engine_solution_instance(dca_engine* e, int inst, int32_t* moves, int ca
     DCA_INST(e, inst);
     DCA_ARG(len != nullptr && cap >= 0 && (cap == 0 || moves != nullptr));
     hipStream_t s = (hipStream_t)stream;
-    const Eng& E = e->E[inst];
+    const EngH& E = e->E[inst];
     hipLaunchKernelGGL(k_solution, dim3(1), dim3(64), 0, s, E, E.d_moves, e->d_cost);
     if (int rc = launch_check("k_solution")) return rc;
     DCA_HIP(hipMemcpyAsync(e->h_moves, E.d_moves, kMaxMoves * sizeof(int32_t), hipMemcpyDeviceToHost, s));
