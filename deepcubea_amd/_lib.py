@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "dca_engine_reset_many", "dca_engine_root_commit_many", "dca_engine_set_weights_dev", "dca_debug_write_ceiling",
     "dca_l1_supported8", "dca_l1_kpad8", "dca_l1_onehot_gemm8", "dca_l1_embed_supported", "dca_l1_embed",
     "dca_gemm64", "dca_l1_embed64", "dca_head_gemv64",
+    "dca_l1_embed_wgrad_slice_rows", "dca_l1_embed_wgrad_workspace_bytes", "dca_l1_embed_wgrad",
 ]
 
 
@@ -77,11 +78,15 @@ def lib() -> C.CDLL:
         for name in ABI_SYMBOLS:
             fn = getattr(_lib, name)  # AttributeError here = stale build of libdca_hip.so
             if name not in ("dca_last_error", "dca_cube3_perm_table", "dca_cube4_perm_table", "dca_engine_destroy", "dca_bn_workspace_bytes",
-                            "dca_l1_kpad", "dca_l1_kpad8"):
+                            "dca_l1_kpad", "dca_l1_kpad8", "dca_l1_embed_wgrad_slice_rows", "dca_l1_embed_wgrad_workspace_bytes"):
                 fn.restype = C.c_int
         _lib.dca_l1_kpad.restype = C.c_int64
         _lib.dca_l1_kpad8.restype = C.c_int64
         _lib.dca_bn_workspace_bytes.restype = C.c_int64
+        _lib.dca_l1_embed_wgrad_slice_rows.restype = C.c_int64
+        _lib.dca_l1_embed_wgrad_slice_rows.argtypes = [C.c_int, C.c_int]
+        _lib.dca_l1_embed_wgrad_workspace_bytes.restype = C.c_int64
+        _lib.dca_l1_embed_wgrad_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int64]
         _lib.dca_bn_workspace_bytes.argtypes = [C.c_int64]
         _lib.dca_engine_destroy.restype = None
         if _lib.dca_abi_version() != 6:
@@ -568,6 +573,82 @@ def l1_embed(states_nnet: torch.Tensor, depth: int, w_t: torch.Tensor, bias: tor
     check(lib().dca_l1_embed(ptr(x), C.c_int64(m), int(d), int(depth), ptr(w_t), C.c_int64(n_pad), ptr(bias), int(relu), ptr(out),
                              code, ptr(overflow), stream_ptr()), "dca_l1_embed")
     return out
+
+
+def l1_embed_wgrad_slice_rows(state_dim: int, depth: int) -> int:
+    """Rows per slice of dca_l1_embed_wgrad's summation order (a property of the geometry; 0: one slice)."""
+    s = int(lib().dca_l1_embed_wgrad_slice_rows(int(state_dim), int(depth)))
+    check(min(s, 0), "dca_l1_embed_wgrad_slice_rows")
+    return s
+
+
+def l1_embed_wgrad(states_nnet: torch.Tensor, dy: torch.Tensor, depth: int, want_bias: bool = True):
+    """Weight gradient of layer 1 from the uint8 rows (dca_l1_embed_wgrad): dW[j, pos * depth + v] = the sum of dy[r, j] over
+    the rows with s[r, pos] == v, db[j] = the sum of dy[:, j] — fp32, in the fixed order include/dca.h states (bit-identical from
+    launch to launch).  dy: fp32 [m, n] of unit column stride (a column slice of a wider matrix is fine), n % 4 == 0.
+    -> (dW [n, state_dim * depth] in nn.Linear's layout, db [n] or None)."""
+    x = _u8(states_nnet)
+    assert dy.is_cuda and dy.dtype == torch.float32 and dy.dim() == 2 and dy.shape[0] == x.shape[0]
+    if dy.stride(1) != 1 or dy.stride(0) % 4 or dy.stride(0) < dy.shape[1] or dy.data_ptr() % 16:
+        dy = dy.contiguous()
+    m, d = x.shape
+    n = int(dy.shape[1])
+    dw = torch.empty((n, d * depth), dtype=torch.float32, device=x.device)
+    db = torch.empty(n, dtype=torch.float32, device=x.device) if want_bias else None
+    if m == 0 or n == 0:  # (an empty tensor has no address to hand over)
+        return dw.zero_(), (None if db is None else db.zero_())
+    need = int(lib().dca_l1_embed_wgrad_workspace_bytes(C.c_int64(m), int(d), int(depth), C.c_int64(n)))
+    check(min(need, 0), "dca_l1_embed_wgrad_workspace_bytes")
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None
+    check(lib().dca_l1_embed_wgrad(ptr(x), C.c_int64(m), int(d), int(depth), _raw(dy), C.c_int64(dy.stride(0) if m > 1 else n),
+                                   C.c_int64(n), ptr(dw), C.c_int64(d * depth), ptr(db), ptr(ws), C.c_int64(need), stream_ptr()),
+          "dca_l1_embed_wgrad")
+    return dw, db
+
+
+class _L1EmbedTrainFn(torch.autograd.Function):
+    """fc1 of the training step straight from the uint8 rows (reference: utils/pytorch_models.py:49-60 on the one-hot matrix,
+    differentiated by utils/nnet_utils.py:53-118): forward = the embedding sum dca_l1_embed (exact fp32, positions ascending),
+    backward = its scatter dca_l1_embed_wgrad.  The one-hot matrix never exists; the states get no gradient."""
+
+    @staticmethod
+    def forward(ctx, states, depth, weight, bias):
+        n, k = weight.shape
+        n_pad = _pad64(n)
+        # the forward kernel stages W^T [K, n_pad] (n_pad % 64 == 0): one padded transposing copy per step
+        w_t = torch.empty((k, n_pad), dtype=torch.float32, device=weight.device)
+        w_t[:, :n].copy_(weight.detach().t())
+        w_t[:, n:].zero_()
+        b = torch.zeros(n_pad, dtype=torch.float32, device=weight.device)
+        if bias is not None:
+            b[:n].copy_(bias.detach())
+        y = l1_embed(states, depth, w_t, b, relu=False)
+        ctx.save_for_backward(states)
+        ctx.depth, ctx.has_bias = int(depth), bias is not None
+        return y if n_pad == n else y[:, :n].contiguous()  # (bn_train wants a contiguous matrix)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (states,) = ctx.saved_tensors
+        want_w, want_b = ctx.needs_input_grad[2], ctx.has_bias and ctx.needs_input_grad[3]
+        dw = db = None
+        if want_w:
+            dw, db = l1_embed_wgrad(states, dy, ctx.depth, want_bias=want_b)
+        elif want_b:  # a frozen weight: no scatter, the bias gradient alone is a column sum
+            db = dy.sum(0)
+        return None, None, dw, db
+
+
+def l1_embed_train(states_nnet: torch.Tensor, lin: "torch.nn.Linear", depth: int) -> torch.Tensor:
+    """`lin(one_hot(states))` inside the training step without the one-hot matrix: uint8 [m, state_dim] -> fp32 [m, out_features]
+    (contiguous), differentiable in lin.weight and lin.bias.  A missing kernel is an error: the geometry must be one
+    dca_l1_embed_supported names and out_features % 4 == 0."""
+    x = _u8(states_nnet)
+    if not l1_embed_supported(x.shape[1], depth) or lin.in_features != x.shape[1] * depth or lin.out_features % 4:
+        raise DcaError("l1_embed_train: no kernel for state_dim %d, depth %d, %d -> %d units" %
+                       (x.shape[1], depth, lin.in_features, lin.out_features))
+    assert lin.weight.is_cuda and lin.weight.dtype == torch.float32
+    return _L1EmbedTrainFn.apply(x, int(depth), lin.weight, lin.bias)
 
 
 def act_split(y: torch.Tensor, bias: Optional[torch.Tensor], skip: Optional[torch.Tensor], alpha, relu: bool,

@@ -36,8 +36,12 @@ from ..utils import data_utils, env_utils, nnet_utils
 
 
 # (flag, type | "flag", default | REQUIRED, help) — names, types and defaults are the reference's (avi.py:21-97; pinned by
-# tests/golden/cli_flags.json); `--seed` and `--max_seconds` are the only additions
+# tests/golden/cli_flags.json); `--seed`, `--max_seconds` and `--l1_train` are the only additions
 REQUIRED = object()
+L1_TRAIN_CHOICES = ("gemm", "embed")
+L1_TRAIN_HELP = ("layer 1 of the training step: gemm = one-hot matrix + dense GEMMs (default); embed = straight from the uint8 states, "
+                 "embedding sum forward + scatter weight gradient, no one-hot matrix (one MI355X, batch 10000, whole step: puzzle48 "
+                 "11.0 -> 9.0 ms, puzzle24 8.4 -> 8.0, puzzle35 8.8 -> 8.7, puzzle15 even, cube3 7.5 -> 7.9: slower)")
 _OPTIONS = (
     ("env", str, REQUIRED, "Environment"),
     ("debug", "flag", False, ""),
@@ -61,6 +65,7 @@ _OPTIONS = (
     ("save_dir", str, "saved_models", "Director to which to save model"),
     ("seed", int, 0, "seed of the device state generator (shards are disjoint)"),
     ("max_seconds", float, 0.0, "stop after the update that crosses this much wall time (0 = run to --max_itrs)"),
+    ("l1_train", L1_TRAIN_CHOICES, "gemm", L1_TRAIN_HELP),
 )
 
 
@@ -69,6 +74,8 @@ def build_parser() -> ArgumentParser:
     for name, kind, default, text in _OPTIONS:
         if kind == "flag":
             parser.add_argument("--" + name, action="store_true", default=default, help=text)
+        elif isinstance(kind, tuple):
+            parser.add_argument("--" + name, type=str, choices=kind, default=default, help=text)
         elif default is REQUIRED:
             parser.add_argument("--" + name, type=kind, required=True, help=text)
         else:
@@ -164,6 +171,7 @@ def main(argv=None):
     nnet, itr, update_num = load_nnet(args_dict['curr_dir'], env)
     update_num = max(update_num, args_dict['update_num'])
     nnet.to(device)
+    nnet.set_l1_train(args_dict['l1_train'])  # (before the DDP wrap: the gradients land on the same parameters either way)
     model = nnet
     if world > 1:
         model = nn.parallel.DistributedDataParallel(nnet, device_ids=[device.index])

@@ -29,6 +29,7 @@ class ResnetModel(nn.Module):
         self.state_dim = state_dim
         self.num_resnet_blocks = num_resnet_blocks
         self.batch_norm = batch_norm
+        self.l1_train = "gemm"  # how training mode runs fc1 (set_l1_train); a plain attribute: no parameter, no buffer
         # registration order fixes the state-dict key order: blocks first (pytorch_models.py:12)
         self.blocks = nn.ModuleList()
         in_dim = state_dim * one_hot_depth if one_hot_depth > 0 else state_dim
@@ -45,6 +46,25 @@ class ResnetModel(nn.Module):
                                              + _dense_bn(resnet_dim, resnet_dim, batch_norm)))
         self.fc_out = nn.Linear(resnet_dim, out_dim)
 
+    L1_TRAIN_MODES = ("gemm", "embed")
+
+    def set_l1_train(self, mode: str) -> "ResnetModel":
+        """How the TRAINING step runs layer 1 on the HIP device.  "gemm" (default): the one-hot matrix is materialised and fc1 is a
+        dense GEMM in both directions.  "embed": fc1 straight from the uint8 rows — forward as the embedding sum dca_l1_embed,
+        weight gradient as its scatter dca_l1_embed_wgrad (`_lib.l1_embed_train`); the one-hot matrix never exists.  Eval mode, the
+        host and `forward_onehot` are the same in both modes."""
+        if mode not in self.L1_TRAIN_MODES:
+            raise ValueError("l1_train must be one of %s, not %r" % ("/".join(self.L1_TRAIN_MODES), mode))
+        if mode == "embed":
+            if self.one_hot_depth <= 0:
+                raise ValueError("l1_train='embed' needs a one-hot input (one_hot_depth %d)" % self.one_hot_depth)
+            from .. import _lib
+            if not _lib.l1_embed_supported(self.state_dim, self.one_hot_depth):
+                raise ValueError("l1_train='embed': no embedding kernel for state_dim %d, depth %d"
+                                 % (self.state_dim, self.one_hot_depth))
+        self.l1_train = mode
+        return self
+
     # -- pieces -------------------------------------------------------------------------------
     def encode(self, states_nnet: torch.Tensor) -> torch.Tensor:
         """uint8 [M, state_dim] -> float32 [M, state_dim*depth] (pytorch_models.py:49-52)."""
@@ -56,14 +76,14 @@ class ResnetModel(nn.Module):
         x = torch.nn.functional.one_hot(states_nnet.long(), self.one_hot_depth).float()
         return x.view(-1, self.state_dim * self.one_hot_depth)
 
-    def _trunk_train_dev(self, x: torch.Tensor) -> torch.Tensor:
+    def _trunk_train_dev(self, x: Optional[torch.Tensor], pre1: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Training mode on the HIP device: the BatchNorms (+ residual add + ReLU) run through the library's column
         reduction kernels (csrc/dca_train.hip) — same arithmetic as `trunk`, the framework's 2-D BatchNorm kernels
         were 41 % of the training step — and the Linears' forward / input-gradient GEMMs through dca_f16x3_gemm
-        (`_lib.linear_train`)."""
+        (`_lib.linear_train`).  `pre1`: fc1's output where the caller has it already (l1_train = "embed"); x is not used then."""
         from .. import _lib
         lin = _lib.linear_train  # forward + input gradient on dca_f16x3_gemm (fp32-accurate), weight gradient on the library
-        x = _lib.bn_train(lin(x, self.fc1), self.bn1, relu=True)
+        x = _lib.bn_train(lin(x, self.fc1) if pre1 is None else pre1, self.bn1, relu=True)
         x = _lib.bn_train(lin(x, self.fc2), self.bn2, relu=True)
         for blk in self.blocks:
             h = _lib.bn_train(lin(x, blk[0]), blk[1], relu=True)
@@ -89,6 +109,10 @@ class ResnetModel(nn.Module):
         return self.fc_out(x)
 
     def forward(self, states_nnet: torch.Tensor) -> torch.Tensor:
+        if (self.l1_train == "embed" and self.training and self.batch_norm and isinstance(self.bn1, nn.BatchNorm1d)
+                and states_nnet.is_cuda and states_nnet.dtype == torch.uint8 and self.fc1.weight.dtype == torch.float32):
+            from .. import _lib
+            return self._trunk_train_dev(None, _lib.l1_embed_train(states_nnet, self.fc1, self.one_hot_depth))
         return self.trunk(self.encode(states_nnet))
 
     def forward_onehot(self, onehot_rows: torch.Tensor) -> torch.Tensor:

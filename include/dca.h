@@ -364,6 +364,30 @@ int dca_l1_embed(const uint8_t* nnet_in /*[m, state_dim]*/, int64_t m, int state
                  const float* bias /*[n_pad]*/, int relu, void* out, int out_dtype, int* overflow /*device flag or NULL*/,
                  void* stream);
 
+/* The TRAINING step's layer 1 from the uint8 rows (csrc/dca_embed_train.hip): the reference's loss.backward()
+ * (utils/nnet_utils.py:53-118) computes fc1's weight gradient of utils/pytorch_models.py:49-60 as the GEMM dy^T . onehot(s); with
+ * one 1 per position that is a scatter, the gradient of the embedding sum above (whose fp32 output is the forward):
+ *   dW[j, pos * depth + v] = sum over the rows r with s[r, pos] == v of dy[r, j]          db[j] = sum over all rows r of dy[r, j]
+ * dW is WRITTEN (not accumulated into) in nn.Linear's own layout [n][K], K = state_dim * depth, row stride ldw >= K (elements
+ * K..ldw of a row are not touched); a column no row selects comes out as +0.0.  nnet_in: uint8 [m, state_dim]; dy: fp32 [m, n],
+ * row stride ld_dy >= n, 16-byte aligned, ld_dy % 4 == 0; n % 4 == 0; db: [n], or NULL to skip it.
+ * Summation order (part of the contract: a value has the same bits on every launch, and a host loop reproduces them): the rows
+ * are cut into consecutive slices of S = dca_l1_embed_wgrad_slice_rows(state_dim, depth) rows, the last one shorter — S depends
+ * on the geometry alone, never on m or n (0 would mean: one slice); within a slice every element of dW and db is a sequential
+ * fp32 sum over the rows in ascending order, starting from +0.0; the slices' sums are then added in ascending slice order, in
+ * fp32, again from +0.0.
+ * State bytes: the forward's contract is "< depth".  Here a position whose byte is >= depth contributes NOTHING to dW (a bad byte
+ * would otherwise be a write to another position's rows); its row still counts in db.
+ * workspace: dca_l1_embed_wgrad_workspace_bytes(m, state_dim, depth, n) bytes of device memory, 4-byte aligned (the slices'
+ * partial tables; 0 bytes — NULL is fine — while m <= S).  m == 0 writes zeros.  DCA_E_BADARG, with a message and without a
+ * launch, for: a geometry dca_l1_embed_supported() does not name, n % 4 != 0, m < 0, a NULL nnet_in / dy / dW, a misaligned dy
+ * or ld_dy, ldw < K, ld_dy < n, a workspace that is missing or too small (the two accessors return DCA_E_BADARG likewise). */
+int64_t dca_l1_embed_wgrad_slice_rows(int state_dim, int depth);
+int64_t dca_l1_embed_wgrad_workspace_bytes(int64_t m, int state_dim, int depth, int64_t n);
+int dca_l1_embed_wgrad(const uint8_t* nnet_in /*[m, state_dim]*/, int64_t m, int state_dim, int depth, const float* dy, int64_t ld_dy,
+                       int64_t n, float* dW, int64_t ldw, float* db /*[n] or NULL*/, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
 /* Glue in front of the fp32-accurate "f16x3" dense layers (csrc/dca_mlp.hip): v = relu?(y*alpha*col_scale + bias (+ skip)) over a
  * row-major fp32 GEMM output y [m, n] (layer 1 on materialised one-hot rows); writes dca_f16x3_gemm's operand `planes` — [m, n]
  * fp16 high halves vh = f16(v), then [m, n] low halves vl = f16(v - vh) — and / or, if x_out != NULL, v itself.  n % 4 == 0. */
