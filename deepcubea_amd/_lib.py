@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "dca_l1_supported8", "dca_l1_kpad8", "dca_l1_onehot_gemm8", "dca_l1_embed_supported", "dca_l1_embed",
     "dca_gemm64", "dca_l1_embed64", "dca_head_gemv64",
     "dca_l1_embed_wgrad_slice_rows", "dca_l1_embed_wgrad_workspace_bytes", "dca_l1_embed_wgrad",
+    "dca_wgrad_f16", "dca_wgrad_splits", "dca_wgrad_workspace_bytes",
 ]
 
 
@@ -78,7 +79,8 @@ def lib() -> C.CDLL:
         for name in ABI_SYMBOLS:
             fn = getattr(_lib, name)  # AttributeError here = stale build of libdca_hip.so
             if name not in ("dca_last_error", "dca_cube3_perm_table", "dca_cube4_perm_table", "dca_engine_destroy", "dca_bn_workspace_bytes",
-                            "dca_l1_kpad", "dca_l1_kpad8", "dca_l1_embed_wgrad_slice_rows", "dca_l1_embed_wgrad_workspace_bytes"):
+                            "dca_l1_kpad", "dca_l1_kpad8", "dca_l1_embed_wgrad_slice_rows", "dca_l1_embed_wgrad_workspace_bytes",
+                            "dca_wgrad_workspace_bytes"):
                 fn.restype = C.c_int
         _lib.dca_l1_kpad.restype = C.c_int64
         _lib.dca_l1_kpad8.restype = C.c_int64
@@ -88,6 +90,11 @@ def lib() -> C.CDLL:
         _lib.dca_l1_embed_wgrad_workspace_bytes.restype = C.c_int64
         _lib.dca_l1_embed_wgrad_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int64]
         _lib.dca_bn_workspace_bytes.argtypes = [C.c_int64]
+        _lib.dca_wgrad_splits.argtypes = [C.c_int64, C.c_int, C.c_int]
+        _lib.dca_wgrad_workspace_bytes.restype = C.c_int64
+        _lib.dca_wgrad_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
+        _lib.dca_wgrad_f16.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
         _lib.dca_engine_destroy.restype = None
         if _lib.dca_abi_version() != 6:
             raise DcaError("libdca_hip.so ABI version mismatch")
@@ -426,6 +433,13 @@ def fill_inv_pow2(amax: torch.Tensor, n: int, out: Optional[torch.Tensor] = None
     return out
 
 
+def _linear_from_planes(ap: torch.Tensor, amax: Optional[torch.Tensor], w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The GEMM of linear_f16x3 on planes of `a` that exist already (ap [2, m, pad64(k)], scaled by `amax`; None: unscaled)."""
+    wp, cs = split_rows_scaled(w, amax, k_pad=ap.shape[2])
+    _, out = f16x3_gemm(ap, wp[0], wp[1], cs, 1.0, None if bias is None else bias.contiguous(), None, False, False, True)
+    return out
+
+
 def linear_f16x3(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], scale_a: bool,
                  amax: Optional[torch.Tensor] = None) -> torch.Tensor:
     """a [m, k] fp32 . w [n, k]^T (+ bias) -> [m, n] fp32 through dca_f16x3_gemm (fp32-accurate on the f16 matrix pipes),
@@ -449,44 +463,115 @@ def linear_f16x3(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
     return out
 
 
+WGRAD_MODES = ("library", "f16x3", "f16")  # how the training step computes nn.Linear's weight gradient (linear_train)
+
+
+def wgrad_splits(m: int, n: int, k: int) -> int:
+    """Slices dca_wgrad_f16 cuts m batch rows into for an [n, k] weight gradient: a function of the three sizes alone."""
+    s = int(lib().dca_wgrad_splits(C.c_int64(m), int(n), int(k)))
+    check(min(s, 0), "dca_wgrad_splits")
+    return s
+
+
+def wgrad_workspace_bytes(m: int, n: int, k: int) -> int:
+    """Bytes of fp32 workspace dca_wgrad_f16 needs: 0 with one slice, else slices * n * k * 4."""
+    b = int(lib().dca_wgrad_workspace_bytes(C.c_int64(m), int(n), int(k)))
+    check(min(b, 0), "dca_wgrad_workspace_bytes")
+    return b
+
+
+def wgrad_f16(dy_planes: torch.Tensor, x_planes: torch.Tensor, n: int, k: int, amax_dy: Optional[torch.Tensor],
+              amax_x: Optional[torch.Tensor], products: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dW [n, k] fp32 = dy^T . x from the fp16 planes of dy [2, m, ld_dy] and x [2, m, ld_x] (split_planes_scaled's, widths
+    zero-padded to a multiple of 64; amax_dy / amax_x: the words they were scaled by, None = unscaled) on dca_wgrad_f16.
+    products = 3: fp32-accurate (dyh.xh + dyh.xl + dyl.xh); products = 1: the high planes alone (non-parity; a [1, m, ld] tensor
+    will do).  `out`: an fp32 [n, k] view of unit column stride to write into (its other columns are not touched)."""
+    for t in (dy_planes, x_planes):
+        assert t.is_cuda and t.dtype == torch.float16 and t.dim() == 3 and t.is_contiguous()
+    m = int(dy_planes.shape[1])
+    assert x_planes.shape[1] == m
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.float32, device=dy_planes.device)
+    assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, k) and out.stride(1) == 1
+    need = wgrad_workspace_bytes(m, n, k)
+    ws = torch.empty(need, dtype=torch.uint8, device=out.device) if need else None
+    lo = lambda t: _raw(t[1]) if (t.shape[0] > 1 and products != 1) else C.c_void_p(0)
+    check(lib().dca_wgrad_f16(_raw(dy_planes[0]), lo(dy_planes), C.c_int64(dy_planes.shape[2]), _raw(x_planes[0]), lo(x_planes),
+                              C.c_int64(x_planes.shape[2]), C.c_int64(m), int(n), int(k), _raw(amax_dy), _raw(amax_x), int(products),
+                              _raw(out), C.c_int64(out.stride(0) if n > 1 else k), ptr(ws), C.c_int64(need), stream_ptr()),
+          "dca_wgrad_f16")
+    return out
+
+
 class _LinearTrainFn(torch.autograd.Function):
     """nn.Linear for the training step (reference nnet_utils.py:53-118 runs it as the library's fp32 GEMMs): forward and input
     gradient on dca_f16x3_gemm (2/3 of the layer's flops, ~3x the library's fp32 rate at fp32 accuracy).  The weight gradient
-    dy^T . x contracts over the BATCH dimension and stays on the library's fp32 GEMM: a split-K form of the f16x3 kernel on
-    operands transposed while they are split was built in round 4, exact to the same level and only a draw on time (faster
-    GEMMs, but two transposes and the sum of the partials on top) — deleted in round 5."""
+    dy^T . x contracts over the BATCH dimension.  wgrad = "library" (default): the library's fp32 GEMM, as the reference.
+    "f16x3" / "f16": dca_wgrad_f16 on the fp16 planes the step has anyway — the forward keeps the planes of x and their amax
+    word instead of x, the backward makes the planes of dy once for the input gradient and the weight gradient — with three
+    products (fp32-accurate) or the high planes alone (non-parity).  The kernel reads the row-major planes with the transposing
+    LDS read: the two transposes that made round 4's split-K form a draw do not exist."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
-        ctx.save_for_backward(x, weight)
+    def forward(ctx, x, weight, bias, wgrad="library"):
         ctx.has_bias = bias is not None
+        ctx.wgrad = wgrad
         # scale_a: the activations get one power-of-two scale from their own magnitude, like the gradients (one extra pass
         # over x; without it a value beyond 65504 turns into inf in its fp16 plane and the loss into NaN without a word)
-        return linear_f16x3(x, weight, bias, scale_a=True)
+        if wgrad == "library":
+            ctx.save_for_backward(x, weight)
+            return linear_f16x3(x, weight, bias, scale_a=True)
+        x, w = x.contiguous(), weight.contiguous()
+        amax_x = absmax_bits(x)
+        xp = split_planes_scaled(x, amax_x, n_pad=_pad64(x.shape[1]))
+        ctx.save_for_backward(xp, amax_x, weight)
+        return _linear_from_planes(xp, amax_x, w, bias)
 
     @staticmethod
     def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
+        if ctx.wgrad == "library":
+            x, weight = ctx.saved_tensors
+            dy = dy.contiguous()
+            amax = absmax_bits(dy) if ctx.needs_input_grad[0] else None
+            dx = linear_f16x3(dy, weight.t().contiguous(), None, scale_a=True, amax=amax) if ctx.needs_input_grad[0] else None
+            dw = None
+            if ctx.needs_input_grad[1]:
+                dw = dy.t().mm(x)
+            db = dy.sum(0) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+            return dx, dw, db, None
+        xp, amax_x, weight = ctx.saved_tensors
         dy = dy.contiguous()
-        amax = absmax_bits(dy) if ctx.needs_input_grad[0] else None
-        dx = linear_f16x3(dy, weight.t().contiguous(), None, scale_a=True, amax=amax) if ctx.needs_input_grad[0] else None
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw = dy.t().mm(x)
+        n, k = weight.shape
+        dx = dw = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:  # (fc1 has no input gradient: the planes serve dW alone)
+            amax = absmax_bits(dy)
+            dyp = split_planes_scaled(dy, amax, n_pad=_pad64(n))
+            if ctx.needs_input_grad[0]:
+                dx = _linear_from_planes(dyp, amax, weight.t().contiguous(), None)
+            if ctx.needs_input_grad[1]:
+                dw = wgrad_f16(dyp, xp, n, k, amax, amax_x, 3 if ctx.wgrad == "f16x3" else 1)
         db = dy.sum(0) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        return dx, dw, db
+        return dx, dw, db, None
 
 
-def linear_train(x: torch.Tensor, lin: "torch.nn.Linear") -> torch.Tensor:
+def linear_train(x: torch.Tensor, lin: "torch.nn.Linear", wgrad: str = "library") -> torch.Tensor:
     """`lin(x)` inside the training step.  The f16x3 path needs the GPU, fp32, 4-element-aligned widths and enough rows to
-    fill a tile; anything else (the 1-wide output layer, the host) is F.linear."""
+    fill a tile; anything else (the 1-wide output layer, the host) is F.linear.  wgrad (WGRAD_MODES): where the f16x3 path
+    computes the weight gradient; the layers that go to F.linear are the same in every mode."""
+    if wgrad not in WGRAD_MODES:
+        raise ValueError("wgrad must be one of %s, not %r" % ("/".join(WGRAD_MODES), wgrad))
     if (x.is_cuda and x.dtype == torch.float32 and lin.weight.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 256
             and lin.in_features % 4 == 0 and lin.out_features % 4 == 0 and lin.in_features >= 64 and TRAIN_F16X3):
-        return _LinearTrainFn.apply(x, lin.weight, lin.bias)
+        if wgrad == "library":
+            return _LinearTrainFn.apply(x, lin.weight, lin.bias)
+        return _LinearTrainFn.apply(x, lin.weight, lin.bias, wgrad)
     return torch.nn.functional.linear(x, lin.weight, lin.bias)
 
 
 TRAIN_F16X3 = os.environ.get("DCA_TRAIN_GEMM", "f16x3") != "library"  # A/B switches (bench.py --workload train, tools/train_grad_check.py)
+TRAIN_WGRAD = os.environ.get("DCA_TRAIN_WGRAD", "library")  # initial weight-gradient mode of new models (ResnetModel.set_wgrad)
+if TRAIN_WGRAD not in WGRAD_MODES:
+    raise ValueError("DCA_TRAIN_WGRAD must be one of %s, not %r" % ("/".join(WGRAD_MODES), TRAIN_WGRAD))
 
 # ------------------------------------------------------------------------------ heuristic network, layer 1
 def l1_supported(state_dim: int, depth: int) -> bool:

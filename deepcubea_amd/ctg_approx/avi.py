@@ -36,12 +36,16 @@ from ..utils import data_utils, env_utils, nnet_utils
 
 
 # (flag, type | "flag", default | REQUIRED, help) — names, types and defaults are the reference's (avi.py:21-97; pinned by
-# tests/golden/cli_flags.json); `--seed`, `--max_seconds` and `--l1_train` are the only additions
+# tests/golden/cli_flags.json); `--seed`, `--max_seconds`, `--l1_train` and `--wgrad` are the only additions
 REQUIRED = object()
 L1_TRAIN_CHOICES = ("gemm", "embed")
 L1_TRAIN_HELP = ("layer 1 of the training step: gemm = one-hot matrix + dense GEMMs (default); embed = straight from the uint8 states, "
                  "embedding sum forward + scatter weight gradient, no one-hot matrix (one MI355X, batch 10000, whole step: puzzle48 "
                  "11.0 -> 9.0 ms, puzzle24 8.4 -> 8.0, puzzle35 8.8 -> 8.7, puzzle15 even, cube3 7.5 -> 7.9: slower)")
+WGRAD_CHOICES = ("library", "f16x3", "f16")
+WGRAD_HELP = ("weight gradients of the training step's dense layers: library = the library's fp32 GEMM (default); f16x3 = the "
+              "hand-written kernel on the fp16 planes the step already has, three products, fp32-accurate; f16 = the same kernel on "
+              "the high planes alone: 11-bit operands with fp32 accumulation, NOT a parity mode")
 _OPTIONS = (
     ("env", str, REQUIRED, "Environment"),
     ("debug", "flag", False, ""),
@@ -66,6 +70,7 @@ _OPTIONS = (
     ("seed", int, 0, "seed of the device state generator (shards are disjoint)"),
     ("max_seconds", float, 0.0, "stop after the update that crosses this much wall time (0 = run to --max_itrs)"),
     ("l1_train", L1_TRAIN_CHOICES, "gemm", L1_TRAIN_HELP),
+    ("wgrad", WGRAD_CHOICES, "library", WGRAD_HELP),
 )
 
 
@@ -172,6 +177,7 @@ def main(argv=None):
     update_num = max(update_num, args_dict['update_num'])
     nnet.to(device)
     nnet.set_l1_train(args_dict['l1_train'])  # (before the DDP wrap: the gradients land on the same parameters either way)
+    nnet.set_wgrad(args_dict['wgrad'])
     model = nnet
     if world > 1:
         model = nn.parallel.DistributedDataParallel(nnet, device_ids=[device.index])

@@ -30,6 +30,8 @@ class ResnetModel(nn.Module):
         self.num_resnet_blocks = num_resnet_blocks
         self.batch_norm = batch_norm
         self.l1_train = "gemm"  # how training mode runs fc1 (set_l1_train); a plain attribute: no parameter, no buffer
+        from .. import _lib
+        self.wgrad = _lib.TRAIN_WGRAD  # where training mode computes the Linears' weight gradients (set_wgrad); plain attribute too
         # registration order fixes the state-dict key order: blocks first (pytorch_models.py:12)
         self.blocks = nn.ModuleList()
         in_dim = state_dim * one_hot_depth if one_hot_depth > 0 else state_dim
@@ -65,6 +67,19 @@ class ResnetModel(nn.Module):
         self.l1_train = mode
         return self
 
+    WGRAD_MODES = ("library", "f16x3", "f16")  # (= _lib.WGRAD_MODES)
+
+    def set_wgrad(self, mode: str) -> "ResnetModel":
+        """Where the TRAINING step on the HIP device computes the weight gradients of the Linears `_lib.linear_train` runs on
+        dca_f16x3_gemm.  "library" (default): the library's fp32 GEMM dy^T . x.  "f16x3": dca_wgrad_f16 on the fp16 planes the step
+        has anyway, three products, fp32-accurate.  "f16": the same kernel on the high planes alone — 11-bit operands, fp32
+        accumulation, NOT a parity mode.  Layers that go to F.linear (the 1-wide head, the host) and fc1 under l1_train="embed"
+        are the same in every mode."""
+        if mode not in self.WGRAD_MODES:
+            raise ValueError("wgrad must be one of %s, not %r" % ("/".join(self.WGRAD_MODES), mode))
+        self.wgrad = mode
+        return self
+
     # -- pieces -------------------------------------------------------------------------------
     def encode(self, states_nnet: torch.Tensor) -> torch.Tensor:
         """uint8 [M, state_dim] -> float32 [M, state_dim*depth] (pytorch_models.py:49-52)."""
@@ -82,7 +97,11 @@ class ResnetModel(nn.Module):
         were 41 % of the training step — and the Linears' forward / input-gradient GEMMs through dca_f16x3_gemm
         (`_lib.linear_train`).  `pre1`: fc1's output where the caller has it already (l1_train = "embed"); x is not used then."""
         from .. import _lib
-        lin = _lib.linear_train  # forward + input gradient on dca_f16x3_gemm (fp32-accurate), weight gradient on the library
+        wgrad = self.wgrad
+
+        def lin(t, layer):  # forward + input gradient on dca_f16x3_gemm (fp32-accurate), weight gradient by `wgrad`
+            return _lib.linear_train(t, layer, wgrad)
+
         x = _lib.bn_train(lin(x, self.fc1) if pre1 is None else pre1, self.bn1, relu=True)
         x = _lib.bn_train(lin(x, self.fc2), self.bn2, relu=True)
         for blk in self.blocks:

@@ -473,6 +473,30 @@ int dca_split_rows_scaled(const float* w, int64_t n, int64_t k, int64_t ld, void
 /* dca_fill_inv_pow2: out[0..n) = 2^-e of the power-of-two scale dca_split_planes_scaled derives from amax_bits. */
 int dca_fill_inv_pow2(float* out, int64_t n, const uint32_t* amax_bits, void* stream);
 
+/* Weight gradient of a dense layer of the training step from the planes above (csrc/dca_wgrad.hip; `--wgrad f16x3 | f16`):
+ *   dw[j, c] = 2^-(e_dy + e_x) * sum over rows r < m of dy[r, j] * x[r, c]            j < n, c < k, fp32 accumulation
+ * Plane convention: dy_h / dy_l [m, ld_dy] and x_h / x_l [m, ld_x] fp16 as dca_split_planes_scaled writes them — vh = f16(v * 2^e),
+ * vl = f16(v * 2^e - vh), row = batch index — with columns n..pad64(n) and k..pad64(k) ZERO (pad64 = next multiple of 64; the
+ * kernel reads them).  amax_dy_bits / amax_x_bits: the device words the planes were scaled by (2^e as dca_split_planes_scaled
+ * derives it); NULL = scale 1.
+ * Arithmetic: products = 3: dyh.xh + dyh.xl + dyl.xh (no lo.lo term), fp32-accurate like dca_f16x3_gemm; products = 1: dyh.xh
+ * alone — 11-bit operands, fp32 accumulation, a NON-parity speed mode (the low planes may be NULL).  v_mfma_f32_16x16x32_f16 on
+ * row-major K-tiles read with ds_read_b64_tr_b16: nothing is transposed in memory.
+ * Slice rule: the rows are cut into S = dca_wgrad_splits(m, n, k) slices of equal length (a multiple of 32, the last one ragged),
+ * S a function of the three sizes alone.  S == 1: one kernel, no workspace.  S > 1: every slice's partial tile goes to the fp32
+ * workspace [S][n][k] (dca_wgrad_workspace_bytes = S * n * k * 4; 0 when S == 1) and a second kernel adds the slices in ascending
+ * slice order, then applies the power-of-two scale.  No atomics: the same input gives the same bits on every launch.
+ * Only dw[0..n, 0..k) is written (row stride ld_dw >= k).  Refused with DCA_E_BADARG before any HIP call: products not 1 or 3;
+ * n or k not a positive multiple of 4; m < 1; ld_dy < pad64(n) or ld_x < pad64(k); a plane stride not a multiple of 8; ld_dw < k;
+ * NULL operands (products = 3: a NULL low plane) or planes off the 16-byte grid (dw, workspace, amax words: 4 bytes); a workspace
+ * that is too small. */
+int dca_wgrad_splits(int64_t m, int n, int k);
+int64_t dca_wgrad_workspace_bytes(int64_t m, int n, int k);
+int dca_wgrad_f16(const void* dy_h, const void* dy_l /*or NULL*/, int64_t ld_dy, const void* x_h, const void* x_l /*or NULL*/,
+                  int64_t ld_x, int64_t m, int n, int k, const uint32_t* amax_dy_bits /*device or NULL*/,
+                  const uint32_t* amax_x_bits /*device or NULL*/, int products, float* dw, int64_t ld_dw, void* workspace,
+                  int64_t workspace_bytes, void* stream);
+
 /* Output layer of the cost-to-go network (utils/pytorch_models.py:83-86, fc_out: res_dim -> out_dim, out_dim = 1 for every
  * environment of the reference): out[m, n_out] = x[m, k] . w[n_out, k]^T + bias, float64 accumulation in a FIXED order (one wave
  * per row, lane-strided FMA chains, xor-butterfly fold, one rounding to fp32): a row's value does not depend on its position, on m or on the launch
