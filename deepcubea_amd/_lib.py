@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "dca_gemm64", "dca_l1_embed64", "dca_head_gemv64",
     "dca_l1_embed_wgrad_slice_rows", "dca_l1_embed_wgrad_workspace_bytes", "dca_l1_embed_wgrad",
     "dca_wgrad_f16", "dca_wgrad_splits", "dca_wgrad_workspace_bytes",
+    "dca_f16_gemm", "dca_cast_planes_scaled", "dca_cast_rows_scaled",
 ]
 
 
@@ -95,6 +96,12 @@ def lib() -> C.CDLL:
         _lib.dca_wgrad_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
         _lib.dca_wgrad_f16.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+        _lib.dca_f16_gemm.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_double,
+                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        _lib.dca_cast_planes_scaled.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                C.c_void_p]
+        _lib.dca_cast_rows_scaled.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
         _lib.dca_engine_destroy.restype = None
         if _lib.dca_abi_version() != 6:
             raise DcaError("libdca_hip.so ABI version mismatch")
@@ -433,6 +440,66 @@ def fill_inv_pow2(amax: torch.Tensor, n: int, out: Optional[torch.Tensor] = None
     return out
 
 
+def cast_planes_scaled(x: torch.Tensor, amax: Optional[torch.Tensor] = None, n_pad: Optional[int] = None,
+                       ldo: Optional[int] = None, out: Optional[torch.Tensor] = None, m: Optional[int] = None,
+                       n: Optional[int] = None, ld: Optional[int] = None) -> torch.Tensor:
+    """The HIGH plane alone of split_planes_scaled, bit for bit, as a [1, m, ldo] fp16 tensor (dca_cast_planes_scaled): what the
+    one-product kernels read (f16_gemm; wgrad_f16 with products = 1 takes the tensor as it is).  Same arguments and padding."""
+    m, n, ld = _rows_cols_ld(x, m, n, ld)
+    n_pad = n if n_pad is None else int(n_pad)
+    ldo = n_pad if ldo is None else int(ldo)
+    if out is None:
+        out = torch.empty((1, m, ldo), dtype=torch.float16, device=x.device)
+    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (1, m, ldo)
+    check(lib().dca_cast_planes_scaled(_raw(x), C.c_int64(m), C.c_int64(n), C.c_int64(ld), _raw(amax), _raw(out), C.c_int64(ldo),
+                                       C.c_int64(n_pad), stream_ptr()), "dca_cast_planes_scaled")
+    return out
+
+
+def cast_rows_scaled(w: torch.Tensor, other_amax: Optional[torch.Tensor] = None, k_pad: Optional[int] = None,
+                     ldo: Optional[int] = None, out: Optional[torch.Tensor] = None, col_scale: Optional[torch.Tensor] = None,
+                     n: Optional[int] = None, k: Optional[int] = None, ld: Optional[int] = None):
+    """The HIGH plane alone of split_rows_scaled, bit for bit, as a [1, n, ldo] fp16 tensor, and the same col_scale
+    (dca_cast_rows_scaled).  -> (out, col_scale)."""
+    n, k, ld = _rows_cols_ld(w, n, k, ld)
+    k_pad = k if k_pad is None else int(k_pad)
+    ldo = k_pad if ldo is None else int(ldo)
+    if out is None:
+        out = torch.empty((1, n, ldo), dtype=torch.float16, device=w.device)
+    if col_scale is None:
+        col_scale = torch.empty(n, dtype=torch.float32, device=w.device)
+    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (1, n, ldo)
+    assert col_scale.dtype == torch.float32 and col_scale.is_contiguous() and col_scale.numel() >= n
+    check(lib().dca_cast_rows_scaled(_raw(w), C.c_int64(n), C.c_int64(k), C.c_int64(ld), _raw(out), C.c_int64(ldo), C.c_int64(k_pad),
+                                     _raw(col_scale), _raw(other_amax), stream_ptr()), "dca_cast_rows_scaled")
+    return out, col_scale
+
+
+def f16_gemm(a_h: torch.Tensor, w_h: torch.Tensor, col_scale: Optional[torch.Tensor], alpha: float,
+             bias: Optional[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(a_h . w_h^T) * alpha * col_scale + bias -> fp32 [m, n] on the one-product kernel dca_f16_gemm: 11-bit operands, fp32
+    accumulation, NOT a parity mode.  a_h [m, k] / w_h [n, k] fp16 of unit column stride (row views of wider matrices welcome),
+    k % 64 == 0; `out`: an fp32 [m, n] view of unit column stride to write into (its other columns are not touched)."""
+    for t in (a_h, w_h):
+        assert t.is_cuda and t.dtype == torch.float16 and t.dim() == 2 and t.stride(1) == 1
+    m, k = a_h.shape
+    n = w_h.shape[0]
+    assert w_h.shape[1] == k
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float32, device=a_h.device)
+    assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (m, n) and out.stride(1) == 1
+    check(lib().dca_f16_gemm(_raw(a_h), C.c_int64(m), int(k), C.c_int64(a_h.stride(0) if m > 1 else k), _raw(w_h), int(n),
+                             C.c_int64(w_h.stride(0) if n > 1 else k), ptr(col_scale), C.c_double(alpha), ptr(bias), _raw(out),
+                             C.c_int64(out.stride(0) if m > 1 else (n + 3) // 4 * 4), stream_ptr()), "dca_f16_gemm")
+    return out
+
+
+def _linear_f16_from_plane(ah: torch.Tensor, amax: Optional[torch.Tensor], w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The GEMM of the one-product mode on a high plane of `a` that exists already (ah [m, pad64(k)], scaled by `amax`)."""
+    wh, cs = cast_rows_scaled(w, amax, k_pad=ah.shape[1])
+    return f16_gemm(ah, wh[0], cs, 1.0, None if bias is None else bias.contiguous())
+
+
 def _linear_from_planes(ap: torch.Tensor, amax: Optional[torch.Tensor], w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
     """The GEMM of linear_f16x3 on planes of `a` that exist already (ap [2, m, pad64(k)], scaled by `amax`; None: unscaled)."""
     wp, cs = split_rows_scaled(w, amax, k_pad=ap.shape[2])
@@ -554,14 +621,68 @@ class _LinearTrainFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
-def linear_train(x: torch.Tensor, lin: "torch.nn.Linear", wgrad: str = "library") -> torch.Tensor:
+TRAIN_GEMM_MODES = ("f16x3", "f16")  # how the training step runs nn.Linear's forward and input-gradient GEMMs (linear_train)
+
+
+class _LinearTrainF16Fn(torch.autograd.Function):
+    """nn.Linear for the training step in the NON-parity GEMM mode (gemm = "f16"): forward y = x . W^T + b and input gradient
+    dx = dy . W on dca_f16_gemm — the scaled HIGH fp16 planes alone, 11-bit operands, one product instead of three, fp32
+    accumulation and output.  The weight gradient goes by `wgrad` as in _LinearTrainFn: "library" keeps fp32 x for dy^T . x;
+    "f16" keeps only the high plane of x and its amax word (cast_planes_scaled writes half the bytes of the split) and hands
+    [1, m, ld] tensors to wgrad_f16(..., products = 1); "f16x3" makes both planes of x and dy with the existing split — the GEMM
+    reads plane 0, wgrad_f16(..., 3) reads both."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, wgrad):
+        ctx.has_bias = bias is not None
+        ctx.wgrad = wgrad
+        x, w = x.contiguous(), weight.contiguous()
+        amax_x = absmax_bits(x)
+        prep = split_planes_scaled if wgrad == "f16x3" else cast_planes_scaled
+        xp = prep(x, amax_x, n_pad=_pad64(x.shape[1]))
+        if wgrad == "library":
+            ctx.save_for_backward(x, weight)
+        else:
+            ctx.save_for_backward(xp, amax_x, weight)
+        return _linear_f16_from_plane(xp[0], amax_x, w, bias)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        weight = ctx.saved_tensors[-1]
+        n, k = weight.shape
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dx = dw = None
+        if need_dx or (need_dw and ctx.wgrad != "library"):
+            amax = absmax_bits(dy)
+            prep = split_planes_scaled if ctx.wgrad == "f16x3" else cast_planes_scaled
+            dyp = prep(dy, amax, n_pad=_pad64(n))
+            if need_dx:
+                dx = _linear_f16_from_plane(dyp[0], amax, weight.t().contiguous(), None)
+        if need_dw:
+            if ctx.wgrad == "library":
+                dw = dy.t().mm(ctx.saved_tensors[0])
+            else:
+                xp, amax_x = ctx.saved_tensors[0], ctx.saved_tensors[1]
+                dw = wgrad_f16(dyp, xp, n, k, amax, amax_x, 3 if ctx.wgrad == "f16x3" else 1)
+        db = dy.sum(0) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        return dx, dw, db, None
+
+
+def linear_train(x: torch.Tensor, lin: "torch.nn.Linear", wgrad: str = "library", gemm: str = "f16x3") -> torch.Tensor:
     """`lin(x)` inside the training step.  The f16x3 path needs the GPU, fp32, 4-element-aligned widths and enough rows to
     fill a tile; anything else (the 1-wide output layer, the host) is F.linear.  wgrad (WGRAD_MODES): where the f16x3 path
-    computes the weight gradient; the layers that go to F.linear are the same in every mode."""
+    computes the weight gradient; the layers that go to F.linear are the same in every mode.  gemm (TRAIN_GEMM_MODES): "f16x3"
+    (default) = forward and input gradient fp32-accurate on dca_f16x3_gemm; "f16" = the same layers on dca_f16_gemm, the high
+    planes alone — 11-bit operands, NOT a parity mode."""
     if wgrad not in WGRAD_MODES:
         raise ValueError("wgrad must be one of %s, not %r" % ("/".join(WGRAD_MODES), wgrad))
+    if gemm not in TRAIN_GEMM_MODES:
+        raise ValueError("gemm must be one of %s, not %r" % ("/".join(TRAIN_GEMM_MODES), gemm))
     if (x.is_cuda and x.dtype == torch.float32 and lin.weight.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 256
             and lin.in_features % 4 == 0 and lin.out_features % 4 == 0 and lin.in_features >= 64 and TRAIN_F16X3):
+        if gemm == "f16":
+            return _LinearTrainF16Fn.apply(x, lin.weight, lin.bias, wgrad)
         if wgrad == "library":
             return _LinearTrainFn.apply(x, lin.weight, lin.bias)
         return _LinearTrainFn.apply(x, lin.weight, lin.bias, wgrad)
@@ -569,6 +690,8 @@ def linear_train(x: torch.Tensor, lin: "torch.nn.Linear", wgrad: str = "library"
 
 
 TRAIN_F16X3 = os.environ.get("DCA_TRAIN_GEMM", "f16x3") != "library"  # A/B switches (bench.py --workload train, tools/train_grad_check.py)
+# initial GEMM mode of new models (ResnetModel.set_train_gemm): exactly "f16" selects the non-parity one-product mode
+TRAIN_GEMM = "f16" if os.environ.get("DCA_TRAIN_GEMM") == "f16" else "f16x3"
 TRAIN_WGRAD = os.environ.get("DCA_TRAIN_WGRAD", "library")  # initial weight-gradient mode of new models (ResnetModel.set_wgrad)
 if TRAIN_WGRAD not in WGRAD_MODES:
     raise ValueError("DCA_TRAIN_WGRAD must be one of %s, not %r" % ("/".join(WGRAD_MODES), TRAIN_WGRAD))

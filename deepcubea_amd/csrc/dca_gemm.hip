@@ -469,6 +469,95 @@ __global__ __launch_bounds__(HTHREADS, 2) void k_f16x3_gemm_v3(const GemmArgs p)
     f16x3_epilogue(p, lds, acc, m0, n0, w, wm, wn, lane, l31, h);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// One-product kernel of the training step's NON-parity mode (`--train_gemm f16`): the high planes alone, 11-bit operands,
+// fp32 accumulation — v2's tile, tile map, DMA map, swizzle, schedule (two whole-K-step stages, one wait + barrier per
+// step) and epilogue, without the low images and without two of the three MFMAs per accumulator.  With a third of the
+// MFMAs between two barriers a 32-deep step would be mostly barrier, so a K-step is 64 deep here (the entry point wants
+// k % 64 == 0 anyway): a stage keeps v2's 64 KB and its four 16 KB images, which are now A[k0, k0+32) | A[k0+32, k0+64)
+// | W[k0, k0+32) | W[k0+32, k0+64) — 64 MFMAs per wave and barrier instead of 32, the same eight DMA instructions per
+// wave and step, and every image still a 256 x 64 B block that swz64 reads without bank conflicts.  Two stages = the
+// 128 KB the epilogue's transposes need anyway.  Sums run over q ascending within an accumulator: no split-K, no atomics.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(HTHREADS, 2) void k_f16_gemm(const GemmArgs p) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, l31 = lane & 31, h = lane >> 5;
+    const int wm = w >> 2, wn = w & 3;
+    const int nNt = (p.n + HBN_T - 1) / HBN_T;
+    const int64_t nMt = (p.m + HBM_T - 1) / HBM_T;
+    const int64_t bid = blockIdx.x;
+    const int64_t slot = bid >> 3;
+    const int64_t mt = (slot / nNt) * 8 + (bid & 7);  // the N tiles of one M tile sit on one XCD
+    const int nt = (int)(slot % nNt);
+    if (mt >= nMt) return;
+    const int64_t m0 = mt * HBM_T;
+    const int n0 = nt * HBN_T;
+
+    // LDS-DMA map (v2's): instruction q of wave w fills rows [rb*16, rb*16+16) of image q >> 1, rb = (q & 1) * 8 + w; lane i
+    // lands on row i >> 2, physical chunk i & 3, and fetches logical chunk (i & 3) ^ swz64_key(row) of the image's 32 columns
+    // (images 1 and 3 start 32 columns into the K-step).  Rows past the matrix edge are clamped: their products are never stored.
+    const _Float16* src[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const int img = q >> 1;
+        const uint32_t r = (uint32_t)(((q & 1) * 8 + w) * 16 + (lane >> 2));
+        const uint32_t c = (uint32_t)(lane & 3) ^ swz64_key(r);
+        if (img < 2) {
+            int64_t gr = m0 + r;
+            gr = gr < p.m ? gr : p.m - 1;
+            src[q] = p.ah + gr * p.lda + (img & 1) * HBK + c * 8;
+        } else {
+            int gn = n0 + (int)r;
+            gn = gn < p.n ? gn : p.n - 1;
+            src[q] = p.wh + (int64_t)gn * p.ldw + (img & 1) * HBK + c * 8;
+        }
+    }
+    auto issue = [&](int stage, int k0) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            uint8_t* dst = lds + stage * HSTAGE + (q >> 1) * HIMG + ((q & 1) * 8 + w) * 1024;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[q] + k0),
+                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+        }
+    };
+
+    f32x4 acc[8][4];
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+#pragma unroll
+        for (int jn = 0; jn < 4; jn++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) acc[i][jn][e] = 0.f;
+    const int g4 = lane >> 4, j16 = lane & 15;
+
+    const int nk = p.k / GBK;
+    issue(0, 0);
+    for (int kt = 0; kt < nk; kt++) {
+        // as in v2: this wave's DMA of step kt has landed and its fragment reads of step kt-1 have returned; behind the barrier
+        // that is true of every wave, so the other stage may be overwritten
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (kt + 1 < nk) issue((kt + 1) & 1, (kt + 1) * GBK);
+        const uint8_t* base = lds + (kt & 1) * HSTAGE;
+#pragma unroll
+        for (int s = 0; s < 2; s++) {  // the two 32-deep halves of the step, each one instruction deep
+            const uint32_t c = (uint32_t)g4;
+            f16x8 ah[8], wh[4];
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                ah[i] = *reinterpret_cast<const f16x8*>(base + s * HIMG + swz64((uint32_t)(wm * 128 + i * 16 + j16), c));
+#pragma unroll
+            for (int jn = 0; jn < 4; jn++)
+                wh[jn] = *reinterpret_cast<const f16x8*>(base + (2 + s) * HIMG + swz64((uint32_t)(wn * 64 + jn * 16 + j16), c));
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+#pragma unroll
+                for (int jn = 0; jn < 4; jn++) acc[i][jn] = mma16h(ah[i], wh[jn], acc[i][jn]);
+        }
+    }
+
+    f16x3_epilogue(p, lds, acc, m0, n0, w, wm, wn, lane, l31, h);
+}
+
 // fp32 [m, n] (row stride ld) -> its two fp16 planes (and the overflow flag): the entry into an f16x3 layer for
 // activations that did not come out of an f16x3 epilogue
 __global__ __launch_bounds__(256) void k_split_planes(const float* __restrict__ x, int64_t m, int64_t n, int64_t ld,
@@ -585,6 +674,53 @@ __global__ __launch_bounds__(256) void k_split_rows_scaled(const float* __restri
     }
 }
 
+// The HIGH planes alone of the two kernels above (the one-product GEMM and products = 1 of dca_wgrad_f16 read nothing else):
+// the same scale, the same rounding (bit for bit their plane 0), the same zero pad, half the bytes written.
+__global__ __launch_bounds__(256) void k_cast_planes_scaled(const float* __restrict__ x, int64_t m, int64_t n, int64_t ld,
+                                                            const uint32_t* __restrict__ amax_bits, _Float16* __restrict__ oh,
+                                                            int64_t ldo, int64_t n_pad) {
+    const float s = amax_bits ? pow2_scale_of(*amax_bits) : 1.0f;
+    const int64_t n4 = n_pad / 4, total = m * n4;
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / n4, c = (i - r * n4) * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < n) v = *reinterpret_cast<const float4*>(x + r * ld + c);
+        const h4 hi = {(_Float16)(v.x * s), (_Float16)(v.y * s), (_Float16)(v.z * s), (_Float16)(v.w * s)};
+        *reinterpret_cast<h4*>(oh + r * ldo + c) = hi;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_cast_rows_scaled(const float* __restrict__ w, int64_t k, int64_t ld,
+                                                          _Float16* __restrict__ oh, int64_t ldo, int64_t k_pad,
+                                                          float* __restrict__ col_scale,
+                                                          const uint32_t* __restrict__ other_amax_bits) {
+    const int64_t r = blockIdx.x;
+    const float* row = w + r * ld;
+    const int64_t k4 = k / 4;
+    uint32_t mx = 0;
+    for (int64_t i = threadIdx.x; i < k4; i += 256) {
+        const float4 v = *reinterpret_cast<const float4*>(row + i * 4);
+        mx = max(max(mx, __float_as_uint(fabsf(v.x))), max(__float_as_uint(fabsf(v.y)), max(__float_as_uint(fabsf(v.z)), __float_as_uint(fabsf(v.w)))));
+    }
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+    __shared__ uint32_t sh[4];
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    const float s = pow2_scale_of(max(max(sh[0], sh[1]), max(sh[2], sh[3])));
+    if (threadIdx.x == 0) {
+        const float so = other_amax_bits ? pow2_scale_of(*other_amax_bits) : 1.0f;
+        col_scale[r] = (1.0f / s) * (1.0f / so);
+    }
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    for (int64_t i = threadIdx.x; i < k_pad / 4; i += 256) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < k4) v = *reinterpret_cast<const float4*>(row + i * 4);
+        const h4 hi = {(_Float16)(v.x * s), (_Float16)(v.y * s), (_Float16)(v.z * s), (_Float16)(v.w * s)};
+        *reinterpret_cast<h4*>(oh + r * ldo + i * 4) = hi;
+    }
+}
+
 __global__ void k_fill_inv_pow2(float* __restrict__ out, int64_t n, const uint32_t* __restrict__ amax_bits) {
     const float v = 1.0f / pow2_scale_of(*amax_bits);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = v;
@@ -660,6 +796,77 @@ int dca_f16x3_gemm(const void* a_h, const void* a_l, int64_t m, int k, int64_t l
     else
         hipLaunchKernelGGL(k_f16x3_gemm_v3, dim3((unsigned)blocks), dim3(HTHREADS), HLDS, (hipStream_t)stream, p);
     return launch_check("k_f16x3_gemm");
+}
+
+int dca_f16_gemm(const void* a_h, int64_t m, int k, int64_t lda, const void* w_h, int n, int64_t ldw, const float* col_scale,
+                 double alpha, const float* bias, float* x_out, int64_t ldo, void* stream) {
+    DCA_ARG(a_h && w_h && x_out && m >= 0 && n >= 1 && k >= GBK && k % GBK == 0);
+    DCA_ARG(lda >= k && ldw >= k && lda % 8 == 0 && ldw % 8 == 0 && ldo >= n && ldo % 4 == 0);
+    DCA_ARG(((uintptr_t)a_h | (uintptr_t)w_h | (uintptr_t)x_out) % 16 == 0);
+    if (m == 0) return 0;
+    {   // the dynamic-LDS limit is a per-device function attribute: set it once for every device this process uses
+        static std::atomic<uint64_t> attr_devs{0};
+        int dev = 0;
+        DCA_HIP(hipGetDevice(&dev));
+        const uint64_t bit = 1ull << (dev & 63);
+        if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
+            DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_f16_gemm), hipFuncAttributeMaxDynamicSharedMemorySize, HLDS));
+            attr_devs.fetch_or(bit, std::memory_order_release);
+        }
+    }
+    GemmArgs p;
+    p.ah = reinterpret_cast<const _Float16*>(a_h);
+    p.al = nullptr;
+    p.wh = reinterpret_cast<const _Float16*>(w_h);
+    p.wl = nullptr;
+    p.col_scale = col_scale;
+    p.bias = bias;
+    p.skip = nullptr;
+    p.alpha = (float)alpha;
+    p.relu = 0;
+    p.m = m;
+    p.n = n;
+    p.k = k;
+    p.lda = lda;
+    p.ldw = ldw;
+    p.ldo = ldo;
+    p.oh = nullptr;
+    p.ol = nullptr;
+    p.x_out = x_out;
+    p.overflow = nullptr;
+    const int64_t nMt = (m + HBM_T - 1) / HBM_T;
+    const int64_t nNt = (n + HBN_T - 1) / HBN_T;
+    const int64_t blocks = ((nMt + 7) / 8) * 8 * nNt;
+    if (blocks > 0x7FFFFFFFll) {
+        set_error("dca_f16_gemm: too many tiles");
+        return DCA_E_BADARG;
+    }
+    hipLaunchKernelGGL(k_f16_gemm, dim3((unsigned)blocks), dim3(HTHREADS), HLDS, (hipStream_t)stream, p);
+    return launch_check("k_f16_gemm");
+}
+
+int dca_cast_planes_scaled(const float* x, int64_t m, int64_t n, int64_t ld, const uint32_t* amax_bits, void* out_h, int64_t ldo,
+                           int64_t n_pad, void* stream) {
+    DCA_ARG(x && out_h && m >= 0 && n >= 4 && n % 4 == 0 && ld >= n && ld % 4 == 0 && n_pad >= n && n_pad % 4 == 0 &&
+            ldo >= n_pad && ldo % 4 == 0);
+    DCA_ARG((uintptr_t)x % 16 == 0 && (uintptr_t)out_h % 8 == 0);
+    if (m == 0) return 0;
+    int64_t blocks = (m * (n_pad / 4) + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_cast_planes_scaled, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, m, n, ld, amax_bits,
+                       reinterpret_cast<_Float16*>(out_h), ldo, n_pad);
+    return launch_check("k_cast_planes_scaled");
+}
+
+int dca_cast_rows_scaled(const float* w, int64_t n, int64_t k, int64_t ld, void* out_h, int64_t ldo, int64_t k_pad, float* col_scale,
+                         const uint32_t* other_amax_bits, void* stream) {
+    DCA_ARG(w && out_h && col_scale && n >= 0 && n < (1ll << 31) && k >= 4 && k % 4 == 0 && ld >= k && ld % 4 == 0 &&
+            k_pad >= k && k_pad % 4 == 0 && ldo >= k_pad && ldo % 4 == 0);
+    DCA_ARG((uintptr_t)w % 16 == 0 && (uintptr_t)out_h % 8 == 0);
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_cast_rows_scaled, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, w, k, ld,
+                       reinterpret_cast<_Float16*>(out_h), ldo, k_pad, col_scale, other_amax_bits);
+    return launch_check("k_cast_rows_scaled");
 }
 
 int dca_split_planes(const float* x, int64_t m, int64_t n, int64_t ld, void* out_h, void* out_l, int64_t ldo, int* overflow,

@@ -36,7 +36,7 @@ from ..utils import data_utils, env_utils, nnet_utils
 
 
 # (flag, type | "flag", default | REQUIRED, help) — names, types and defaults are the reference's (avi.py:21-97; pinned by
-# tests/golden/cli_flags.json); `--seed`, `--max_seconds`, `--l1_train` and `--wgrad` are the only additions
+# tests/golden/cli_flags.json); `--seed`, `--max_seconds`, `--l1_train`, `--wgrad` and `--train_gemm` are the only additions
 REQUIRED = object()
 L1_TRAIN_CHOICES = ("gemm", "embed")
 L1_TRAIN_HELP = ("layer 1 of the training step: gemm = one-hot matrix + dense GEMMs (default); embed = straight from the uint8 states, "
@@ -46,6 +46,11 @@ WGRAD_CHOICES = ("library", "f16x3", "f16")
 WGRAD_HELP = ("weight gradients of the training step's dense layers: library = the library's fp32 GEMM (default); f16x3 = the "
               "hand-written kernel on the fp16 planes the step already has, three products, fp32-accurate; f16 = the same kernel on "
               "the high planes alone: 11-bit operands with fp32 accumulation, NOT a parity mode")
+TRAIN_GEMM_CHOICES = ("f16x3", "f16")
+TRAIN_GEMM_HELP = ("forward and input-gradient GEMMs of the training step's dense layers: f16x3 = three products on two fp16 planes, "
+                   "fp32-accurate (default); f16 = the high planes alone on a one-product kernel: 11-bit operands with fp32 "
+                   "accumulation, NOT a parity mode (one MI355X, batch 10000, whole step: cube3 7.65 -> 6.82 ms, with --wgrad f16 "
+                   "6.27 -> 5.48; puzzle48 with --l1_train embed 9.04 -> 8.29 and 7.77 -> 7.03)")
 _OPTIONS = (
     ("env", str, REQUIRED, "Environment"),
     ("debug", "flag", False, ""),
@@ -71,6 +76,7 @@ _OPTIONS = (
     ("max_seconds", float, 0.0, "stop after the update that crosses this much wall time (0 = run to --max_itrs)"),
     ("l1_train", L1_TRAIN_CHOICES, "gemm", L1_TRAIN_HELP),
     ("wgrad", WGRAD_CHOICES, "library", WGRAD_HELP),
+    ("train_gemm", TRAIN_GEMM_CHOICES, "f16x3", TRAIN_GEMM_HELP),
 )
 
 
@@ -178,6 +184,7 @@ def main(argv=None):
     nnet.to(device)
     nnet.set_l1_train(args_dict['l1_train'])  # (before the DDP wrap: the gradients land on the same parameters either way)
     nnet.set_wgrad(args_dict['wgrad'])
+    nnet.set_train_gemm(args_dict['train_gemm'])
     model = nnet
     if world > 1:
         model = nn.parallel.DistributedDataParallel(nnet, device_ids=[device.index])

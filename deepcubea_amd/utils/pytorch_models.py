@@ -32,6 +32,7 @@ class ResnetModel(nn.Module):
         self.l1_train = "gemm"  # how training mode runs fc1 (set_l1_train); a plain attribute: no parameter, no buffer
         from .. import _lib
         self.wgrad = _lib.TRAIN_WGRAD  # where training mode computes the Linears' weight gradients (set_wgrad); plain attribute too
+        self.train_gemm = _lib.TRAIN_GEMM  # how training mode runs the Linears' forward / input-gradient GEMMs (set_train_gemm); plain too
         # registration order fixes the state-dict key order: blocks first (pytorch_models.py:12)
         self.blocks = nn.ModuleList()
         in_dim = state_dim * one_hot_depth if one_hot_depth > 0 else state_dim
@@ -80,6 +81,19 @@ class ResnetModel(nn.Module):
         self.wgrad = mode
         return self
 
+    TRAIN_GEMM_MODES = ("f16x3", "f16")  # (= _lib.TRAIN_GEMM_MODES)
+
+    def set_train_gemm(self, mode: str) -> "ResnetModel":
+        """How the TRAINING step on the HIP device runs the forward and input-gradient GEMMs of the Linears that go through
+        `_lib.linear_train`.  "f16x3" (default): dca_f16x3_gemm, three products on two fp16 planes, fp32-accurate.  "f16":
+        dca_f16_gemm on the high planes alone — 11-bit operands, one product, fp32 accumulation and output, NOT a parity mode.
+        Independent of set_wgrad and set_l1_train; layers that go to F.linear (the 1-wide head, the host) and fc1 under
+        l1_train="embed" are the same in both modes."""
+        if mode not in self.TRAIN_GEMM_MODES:
+            raise ValueError("train_gemm must be one of %s, not %r" % ("/".join(self.TRAIN_GEMM_MODES), mode))
+        self.train_gemm = mode
+        return self
+
     # -- pieces -------------------------------------------------------------------------------
     def encode(self, states_nnet: torch.Tensor) -> torch.Tensor:
         """uint8 [M, state_dim] -> float32 [M, state_dim*depth] (pytorch_models.py:49-52)."""
@@ -97,9 +111,11 @@ class ResnetModel(nn.Module):
         were 41 % of the training step — and the Linears' forward / input-gradient GEMMs through dca_f16x3_gemm
         (`_lib.linear_train`).  `pre1`: fc1's output where the caller has it already (l1_train = "embed"); x is not used then."""
         from .. import _lib
-        wgrad = self.wgrad
+        wgrad, gemm = self.wgrad, self.train_gemm
 
         def lin(t, layer):  # forward + input gradient on dca_f16x3_gemm (fp32-accurate), weight gradient by `wgrad`
+            if gemm == "f16":  # ... or on dca_f16_gemm, the high planes alone (non-parity); the default call keeps its three arguments
+                return _lib.linear_train(t, layer, wgrad, gemm=gemm)
             return _lib.linear_train(t, layer, wgrad)
 
         x = _lib.bn_train(lin(x, self.fc1) if pre1 is None else pre1, self.bn1, relu=True)

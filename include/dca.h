@@ -473,6 +473,26 @@ int dca_split_rows_scaled(const float* w, int64_t n, int64_t k, int64_t ld, void
 /* dca_fill_inv_pow2: out[0..n) = 2^-e of the power-of-two scale dca_split_planes_scaled derives from amax_bits. */
 int dca_fill_inv_pow2(float* out, int64_t n, const uint32_t* amax_bits, void* stream);
 
+/* The NON-parity mode of the training step's forward and input-gradient GEMMs (`--train_gemm f16`; csrc/dca_gemm.hip): the
+ * scaled HIGH fp16 planes alone — 11-bit operands, one product per K-step instead of three, fp32 accumulation on
+ * v_mfma_f32_16x16x32_f16, fp32 output:
+ *   x_out[r, c] = (alpha * col_scale[c]) * sum over q < k of a_h[r, q] * w_h[c, q] + bias[c]            r < m, c < n
+ * a_h [m, lda] / w_h [n, ldw] fp16, rows = output units: plane 0 of dca_split_planes_scaled / dca_split_rows_scaled, or what
+ * the two casts below write.  No low planes, no skip, no ReLU, no plane outputs.  Same tile, tile map and epilogue as
+ * dca_f16x3_gemm; no split-K and no atomics: the same input gives the same bits on every launch.  Only x_out[0..m, 0..n) is
+ * written (row stride ldo).  Argument rules as dca_f16x3_gemm: k >= 64 and k % 64 == 0; lda, ldw >= k and % 8 == 0; ldo >= n
+ * and % 4 == 0; a_h, w_h, x_out 16-byte aligned; n >= 1; m >= 0 (m == 0: returns 0, writes nothing).  Anything else is refused
+ * with DCA_E_BADARG before a launch.
+ *   dca_cast_planes_scaled / dca_cast_rows_scaled: dca_split_planes_scaled / dca_split_rows_scaled without the low plane —
+ *   the same argument rules, scale, zero padding and col_scale; out_h bit for bit their high plane; half the bytes written. */
+int dca_f16_gemm(const void* a_h, int64_t m, int k, int64_t lda, const void* w_h, int n, int64_t ldw,
+                 const float* col_scale /*[n] or NULL*/, double alpha, const float* bias /*[n] or NULL*/, float* x_out, int64_t ldo,
+                 void* stream);
+int dca_cast_planes_scaled(const float* x, int64_t m, int64_t n, int64_t ld, const uint32_t* amax_bits /*device or NULL*/,
+                           void* out_h, int64_t ldo, int64_t n_pad, void* stream);
+int dca_cast_rows_scaled(const float* w, int64_t n, int64_t k, int64_t ld, void* out_h, int64_t ldo, int64_t k_pad,
+                         float* col_scale /*[n]*/, const uint32_t* other_amax_bits /*device or NULL*/, void* stream);
+
 /* Weight gradient of a dense layer of the training step from the planes above (csrc/dca_wgrad.hip; `--wgrad f16x3 | f16`):
  *   dw[j, c] = 2^-(e_dy + e_x) * sum over rows r < m of dy[r, j] * x[r, c]            j < n, c < k, fp32 accumulation
  * Plane convention: dy_h / dy_l [m, ld_dy] and x_h / x_l [m, ld_x] fp16 as dca_split_planes_scaled writes them — vh = f16(v * 2^e),
