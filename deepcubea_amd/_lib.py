@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "dca_l1_embed_wgrad_slice_rows", "dca_l1_embed_wgrad_workspace_bytes", "dca_l1_embed_wgrad",
     "dca_wgrad_f16", "dca_wgrad_splits", "dca_wgrad_workspace_bytes",
     "dca_f16_gemm", "dca_cast_planes_scaled", "dca_cast_rows_scaled",
+    "dca_hcache_bytes", "dca_hcache_clear", "dca_hcache_lookup", "dca_hcache_finish",
 ]
 
 
@@ -81,7 +82,7 @@ def lib() -> C.CDLL:
             fn = getattr(_lib, name)  # AttributeError here = stale build of libdca_hip.so
             if name not in ("dca_last_error", "dca_cube3_perm_table", "dca_cube4_perm_table", "dca_engine_destroy", "dca_bn_workspace_bytes",
                             "dca_l1_kpad", "dca_l1_kpad8", "dca_l1_embed_wgrad_slice_rows", "dca_l1_embed_wgrad_workspace_bytes",
-                            "dca_wgrad_workspace_bytes"):
+                            "dca_wgrad_workspace_bytes", "dca_hcache_bytes"):
                 fn.restype = C.c_int
         _lib.dca_l1_kpad.restype = C.c_int64
         _lib.dca_l1_kpad8.restype = C.c_int64
@@ -102,6 +103,12 @@ def lib() -> C.CDLL:
                                                 C.c_void_p]
         _lib.dca_cast_rows_scaled.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
+        _lib.dca_hcache_bytes.restype = C.c_int64
+        _lib.dca_hcache_bytes.argtypes = [C.c_int, C.c_int64]
+        _lib.dca_hcache_clear.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+        _lib.dca_hcache_lookup.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
+        _lib.dca_hcache_finish.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.dca_engine_destroy.restype = None
         if _lib.dca_abi_version() != 6:
             raise DcaError("libdca_hip.so ABI version mismatch")
@@ -306,6 +313,76 @@ def bellman_backup(h_children: torch.Tensor, solved_parent: Optional[torch.Tenso
     check(lib().dca_bellman_backup(ptr(h), ptr(solved_parent), C.c_int64(n), int(num_moves), int(clip_zero), ptr(ctg),
                                    ptr(am), stream_ptr()), "dca_bellman_backup")
     return ctg, am
+
+
+# ------------------------------------------------------------------------------ heuristic cache (update step)
+HCACHE_HIT, HCACHE_EVAL_STORE, HCACHE_DUP, HCACHE_EVAL_ONLY = 0, 1, 2, 3
+
+
+def hcache_bytes(row_bytes: int, slots: int) -> int:
+    """Bytes of a heuristic-cache table: a pure function of its arguments (include/dca.h)."""
+    b = int(lib().dca_hcache_bytes(int(row_bytes), C.c_int64(int(slots))))
+    check(min(b, 0), "dca_hcache_bytes")
+    return b
+
+
+class HeuristicCache:
+    """Owns the device table of dca_hcache_* (include/dca.h "heuristic cache"): rows uint8 [n, row_bytes] -> float32 values,
+    exact for a heuristic that is a function of the row alone.  lookup() / finish() are the two halves around the caller's
+    evaluation of the EVAL_STORE and EVAL_ONLY rows."""
+
+    def __init__(self, row_bytes: int, slots: int, device: Optional[torch.device] = None):
+        row_bytes, slots = int(row_bytes), int(slots)
+        if not 1 <= row_bytes <= 64:
+            raise ValueError("HeuristicCache: row_bytes must be 1..64, not %d" % row_bytes)
+        if slots < 2 or slots > (1 << 30) or slots & (slots - 1):
+            raise ValueError("HeuristicCache: slots must be a power of two in 2..2^30, not %d" % slots)
+        self.row_bytes, self.slots = row_bytes, slots
+        self.nbytes = hcache_bytes(row_bytes, slots)
+        dev = device if device is not None else require_gpu()
+        self.table = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        self.clear()
+
+    def clear(self) -> None:
+        check(lib().dca_hcache_clear(ptr(self.table), self.row_bytes, C.c_int64(self.slots), stream_ptr()), "dca_hcache_clear")
+
+    def used(self) -> int:
+        """Slots in use (synchronises)."""
+        return int(self.table[:4].view(torch.int32).item())
+
+    def _rows(self, rows: torch.Tensor):
+        if rows.dtype != torch.uint8 or not rows.is_cuda or rows.dim() != 2:
+            raise ValueError("HeuristicCache: rows must be a uint8 device tensor [n, row_bytes]")
+        n, rb = rows.shape
+        if rb != self.row_bytes:
+            raise ValueError("HeuristicCache: rows are %d bytes wide, the table was built for %d" % (rb, self.row_bytes))
+        if n > 0 and rows.stride(1) != 1:
+            rows = rows.contiguous()
+        ld = rows.stride(0) if n > 1 else max(rows.stride(0), rb)
+        if ld < rb:
+            rows, ld = rows.contiguous(), rb
+        return rows, n, ld
+
+    def lookup(self, rows: torch.Tensor, h: Optional[torch.Tensor] = None, slot: Optional[torch.Tensor] = None,
+               status: Optional[torch.Tensor] = None):
+        """-> (h f32 [n], slot i32 [n], status u8 [n]); h is written for HIT rows only.  rows may be a strided view (row stride
+        >= row_bytes, unit byte stride)."""
+        rows, n, ld = self._rows(rows)
+        dev = rows.device
+        h = torch.empty(n, dtype=torch.float32, device=dev) if h is None else h
+        slot = torch.empty(n, dtype=torch.int32, device=dev) if slot is None else slot
+        status = torch.empty(n, dtype=torch.uint8, device=dev) if status is None else status
+        assert h.dtype == torch.float32 and slot.dtype == torch.int32 and status.dtype == torch.uint8
+        assert h.numel() >= n and slot.numel() >= n and status.numel() >= n
+        check(lib().dca_hcache_lookup(ptr(self.table), self.row_bytes, C.c_int64(self.slots), C.c_void_p(rows.data_ptr()), C.c_int64(n),
+                                      C.c_int64(ld), ptr(h), ptr(slot), ptr(status), stream_ptr()), "dca_hcache_lookup")
+        return h, slot, status
+
+    def finish(self, h: torch.Tensor, slot: torch.Tensor, status: torch.Tensor, n: Optional[int] = None) -> torch.Tensor:
+        n = int(status.numel() if n is None else n)
+        check(lib().dca_hcache_finish(ptr(self.table), self.row_bytes, C.c_int64(self.slots), C.c_int64(n), ptr(slot), ptr(status),
+                                      ptr(h), stream_ptr()), "dca_hcache_finish")
+        return h
 
 
 # ------------------------------------------------------------------------------ training step

@@ -36,7 +36,8 @@ from ..utils import data_utils, env_utils, nnet_utils
 
 
 # (flag, type | "flag", default | REQUIRED, help) — names, types and defaults are the reference's (avi.py:21-97; pinned by
-# tests/golden/cli_flags.json); `--seed`, `--max_seconds`, `--l1_train`, `--wgrad` and `--train_gemm` are the only additions
+# tests/golden/cli_flags.json); `--seed`, `--max_seconds`, `--l1_train`, `--wgrad`, `--train_gemm` and `--update_cache` are the only
+# additions
 REQUIRED = object()
 L1_TRAIN_CHOICES = ("gemm", "embed")
 L1_TRAIN_HELP = ("layer 1 of the training step: gemm = one-hot matrix + dense GEMMs (default); embed = straight from the uint8 states, "
@@ -51,6 +52,12 @@ TRAIN_GEMM_HELP = ("forward and input-gradient GEMMs of the training step's dens
                    "fp32-accurate (default); f16 = the high planes alone on a one-product kernel: 11-bit operands with fp32 "
                    "accumulation, NOT a parity mode (one MI355X, batch 10000, whole step: cube3 7.65 -> 6.82 ms, with --wgrad f16 "
                    "6.27 -> 5.48; puzzle48 with --l1_train embed 9.04 -> 8.29 and 7.77 -> 7.03)")
+UPDATE_CACHE_HELP = ("heuristic cache of the update step: off (default) | auto | <slots, a power of two>.  The target network then "
+                     "evaluates every distinct child state once (a device-resident table keyed by the uint8 network-input row, kept "
+                     "for the whole update); auto sizes the table from the shard's row count, capped by free HBM.  EXACT only for a "
+                     "batch-invariant heuristic - a row's value has the same bits in any batch: the fp32 parity network (what avi "
+                     "uses) and the fp64 mode; a network that calibrates on its batch (fp8) is refused.  No cache is built while "
+                     "there is no target network (the all-zeros heuristic)")
 _OPTIONS = (
     ("env", str, REQUIRED, "Environment"),
     ("debug", "flag", False, ""),
@@ -77,6 +84,7 @@ _OPTIONS = (
     ("l1_train", L1_TRAIN_CHOICES, "gemm", L1_TRAIN_HELP),
     ("wgrad", WGRAD_CHOICES, "library", WGRAD_HELP),
     ("train_gemm", TRAIN_GEMM_CHOICES, "f16x3", TRAIN_GEMM_HELP),
+    ("update_cache", str, "off", UPDATE_CACHE_HELP),
 )
 
 
@@ -135,7 +143,9 @@ def target_heuristic(targ_dir: str, env, device, batch_size: int):
     """The update's heuristic (avi.py:215-224): the target network with clip_zero=True, or all zeros while there is none."""
     targ_file = "%s/model_state_dict.pt" % targ_dir
     if not os.path.isfile(targ_file):
-        return lambda x, is_onehot=False: torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
+        zeros = lambda x, is_onehot=False: torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
+        zeros.all_zeros = True  # (do_update builds no heuristic cache for it)
+        return zeros
     from ..utils.pytorch_models import FastResnet
     targ = nnet_utils.load_nnet(targ_file, env.get_nnet_model(), device=torch.device("cpu"))
     fast = FastResnet(targ).to(device)
@@ -145,7 +155,7 @@ def target_heuristic(targ_dir: str, env, device, batch_size: int):
 
 
 def do_update(back_max: int, update_num: int, env, max_update_steps: int, update_method: str, num_states: int,
-              eps_max: float, heuristic_fn_dev, seed: int, update_batch_size: int):
+              eps_max: float, heuristic_fn_dev, seed: int, update_batch_size: int, update_cache="off"):
     """avi.py:129-159 -> (states_nnet u8 [T,D] device, outputs f32 [T,1] device) for this rank."""
     update_steps = min(update_num + 1, max_update_steps)
     num_states = int(np.ceil(num_states / update_steps))
@@ -155,8 +165,14 @@ def do_update(back_max: int, update_num: int, env, max_update_steps: int, update
         print("Using %s with %i step(s) to add extra states to training set" % (update_method.upper(), update_steps))
     updater = Updater(env, num_states, back_max, heuristic_fn_dev, update_steps, update_method,
                       update_batch_size=update_batch_size, eps_max=eps_max, seed=seed,
-                      onehot_dtype=getattr(heuristic_fn_dev, "onehot_dtype", None))
+                      onehot_dtype=getattr(heuristic_fn_dev, "onehot_dtype", None),
+                      cache="off" if getattr(heuristic_fn_dev, "all_zeros", False) else update_cache)
     states_nnet, outputs, is_solved = updater.update_dev()
+    counters = updater.cache_counters()
+    if counters is not None and counters["rows"]:
+        print("Heuristic cache: %s of %s network rows evaluated (%.1f%%; %s hits, %s repeats within a call, %s uncached)" % (
+            format(counters["evaluated"], ","), format(counters["rows"], ","), 100.0 * counters["evaluated"] / counters["rows"],
+            format(counters["hits"], ","), format(counters["dups"], ","), format(counters["uncached"], ",")))
     if max_update_steps > 1:
         print("%s produced %s states, %.2f%% solved (%.2f seconds)" % (
             update_method.upper(), format(outputs.shape[0], ","), 100.0 * float(is_solved.float().mean()),
@@ -170,6 +186,8 @@ def main(argv=None):
     # nccl = RCCL over xGMI (one GPU per rank); DCA_DIST_BACKEND=gloo lets several ranks share one GPU (tests)
     world, rank = sharding.init_from_env(os.environ.get("DCA_DIST_BACKEND", "nccl" if torch.cuda.is_available() else "gloo"))
     args_dict = parse_arguments(build_parser(), argv, rank)
+    from ..updaters.updater import parse_update_cache
+    parse_update_cache(args_dict['update_cache'])  # a bad value is refused before anything is built
     if not args_dict["debug"] and rank == 0:
         sys.stdout = data_utils.Logger(args_dict["output_save_loc"], "a")
     env = env_utils.get_environment(args_dict['env'])
@@ -204,7 +222,8 @@ def main(argv=None):
         hfn = target_heuristic(args_dict['targ_dir'], env, device, args_dict['update_nnet_batch_size'])
         states_nnet, outputs = do_update(args_dict["back_max"], update_num, env, args_dict['max_update_steps'],
                                          args_dict['update_method'], args_dict['states_per_update'], args_dict['eps_max'],
-                                         hfn, args_dict['seed'] + 7919 * (itr + 1), max(args_dict['update_nnet_batch_size'], 1) * 10)
+                                         hfn, args_dict['seed'] + 7919 * (itr + 1), max(args_dict['update_nnet_batch_size'], 1) * 10,
+                                         update_cache=args_dict['update_cache'])
         del hfn
         # train.  Under DDP every rank must run the SAME number of steps (each one is a gradient all-reduce), but the
         # shards differ in size: GBFS trajectories end early where an instance solves (--max_update_steps > 1) and

@@ -14,7 +14,8 @@ line uses, train.sh:65) run on the multi-instance BWAS engine: `astar_update_dev
 """
 from __future__ import annotations
 
-from typing import Callable, List, Optional, Tuple
+import os
+from typing import Callable, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -216,6 +217,39 @@ def astar_update_dev(states: torch.Tensor, env, num_steps: int, heuristic_fn_dev
     return su[order], cg[order], found
 
 
+def parse_update_cache(value) -> Union[None, str, int]:
+    """`--update_cache` / DCA_UPDATE_CACHE: "off" -> None, "auto" -> "auto", a power-of-two slot count -> int.  Anything else is a
+    ValueError (like DCA_TRAIN_WGRAD)."""
+    if value is None or value is False:
+        return None
+    if isinstance(value, (int, np.integer)) and not isinstance(value, bool):
+        slots = int(value)
+    else:
+        text = str(value).strip()
+        if text == "off":
+            return None
+        if text == "auto":
+            return "auto"
+        if not text.isdigit():
+            raise ValueError("DCA_UPDATE_CACHE / --update_cache must be off, auto or a slot count (a power of two), not %r" % (value,))
+        slots = int(text)
+    if slots < 2 or slots > (1 << 30) or slots & (slots - 1):
+        raise ValueError("DCA_UPDATE_CACHE / --update_cache: the slot count must be a power of two in 2..2^30, not %r" % (value,))
+    return slots
+
+
+def auto_cache_slots(rows: int, row_bytes: int, free_bytes: int) -> int:
+    """What "auto" means: the power of two that holds every row of the shard below the table's fill limit (slots / 2), no more
+    than a quarter of the free device memory, at least 1024 slots."""
+    slots = 1024
+    while slots < 2 * max(int(rows), 1) and slots < (1 << 30):
+        slots *= 2
+    per_slot = 24 + 8 * ((int(row_bytes) + 7) // 8)  # dca_hcache_bytes
+    while slots > 1024 and 64 + slots * per_slot > free_bytes // 4:
+        slots //= 2
+    return slots
+
+
 class Updater:
     """Drop-in for updaters/updater.py:84-165: same constructor meaning and `update()` triple, but
     `heur_fn_i_q / heur_fn_o_qs` become a device heuristic closure and the worker processes become ranks:
@@ -223,9 +257,15 @@ class Updater:
 
     def __init__(self, env, num_states: int, back_max: int, heuristic_fn_dev: Callable, num_steps: int,
                  update_method: str = "GBFS", update_batch_size: int = 1_000_000, eps_max: float = 0.0, seed: int = 0,
-                 onehot_dtype=None):
+                 onehot_dtype=None, cache=None):
         if update_method.upper() not in ("GBFS", "ASTAR"):
             raise ValueError("Unknown update method %s" % update_method)  # updater.py:73
+        # heuristic cache of the target network (include/dca.h): None reads DCA_UPDATE_CACHE (off | auto | slots; default off)
+        self.cache_spec = parse_update_cache(os.environ.get("DCA_UPDATE_CACHE", "off") if cache is None else cache)
+        self.cached_fn = None  # built at the first update_dev(): one table for the life of this Updater
+        if self.cache_spec is not None and getattr(getattr(heuristic_fn_dev, "nnet", None), "takes_valid_rows", False):
+            raise ValueError("Updater: the heuristic cache needs a batch-invariant heuristic; this network calibrates on the rows "
+                             "it sees (fp8) and cannot be cached")
         self.method = update_method.upper()
         self.env, self.num_states, self.back_max = env, int(num_states), int(back_max)
         self.hfn, self.num_steps, self.eps_max = heuristic_fn_dev, int(num_steps), float(eps_max)
@@ -235,9 +275,30 @@ class Updater:
         self.local_n = per[self.rank]  # misc_utils.split_evenly (misc_utils.py:29-36)
         self.index0 = sum(per[:self.rank])
 
+    def _heuristic(self) -> Callable:
+        """The update's heuristic: `heuristic_fn_dev` itself, or — cache on — the same closure behind ONE heuristic cache that
+        lives as long as this Updater (the target network is fixed for that long).  EXACT only for a batch-invariant heuristic
+        (nnet_utils.cached_heuristic_fn_dev); a closure that takes one-hot rows passes through uncached."""
+        if self.cache_spec is None:
+            return self.hfn
+        if self.cached_fn is None:
+            from ..utils import nnet_utils
+            D = _lib.env_geometry(self.env._env_id, self.env._dim)[0]
+            slots = self.cache_spec
+            if slots == "auto":
+                rows = self.local_n * self.env.get_num_moves() * max(self.num_steps, 1) + self.local_n
+                slots = auto_cache_slots(rows, D, torch.cuda.mem_get_info()[0])
+            self.cached_fn = nnet_utils.cached_heuristic_fn_dev(self.hfn, D, slots)
+        return self.cached_fn
+
+    def cache_counters(self) -> Optional[dict]:
+        """rows / hits / dups / evaluated / uncached of the heuristic cache so far (None: cache off or not yet used)."""
+        return self.cached_fn.counters() if self.cached_fn is not None else None
+
     def update_dev(self):
         """This rank's shard, on device: (states_nnet u8 [T,D], ctg f32 [T,1], is_solved bool [local_n])."""
         env = self.env
+        hfn = self._heuristic()
         gen = torch.Generator(device="cuda")
         gen.manual_seed(self.seed * 1000003 + self.rank)
         sn, cg, sv = [], [], []
@@ -248,9 +309,9 @@ class Updater:
                                                 self.index0 + start)  # updater.py:66 env.generate_states(n,(0,back_max))
             if self.method == "ASTAR":
                 wts = np.random.default_rng([self.seed, self.rank, start]).random(m)  # updater.py:37 np.random.rand
-                su, ctg, solved = astar_update_dev(states, env, self.num_steps, self.hfn, wts, onehot_dtype=self.onehot_dtype)
+                su, ctg, solved = astar_update_dev(states, env, self.num_steps, hfn, wts, onehot_dtype=self.onehot_dtype)
             else:
-                su, ctg, solved = gbfs_update_dev(states, env, self.num_steps, self.hfn, self.eps_max, gen,
+                su, ctg, solved = gbfs_update_dev(states, env, self.num_steps, hfn, self.eps_max, gen,
                                                   self.onehot_dtype)
             sn.append(_lib.nnet_input(env._env_id, env._dim, su))  # updater.py:75 state_to_nnet_input
             cg.append(ctg)

@@ -77,7 +77,52 @@ def get_heuristic_fn_dev(nnet: nn.Module, clip_zero: bool = False, batch_size: O
         return torch.clamp_min(y, 0.0) if clip_zero else y
 
     heuristic_fn_dev.valid_rows = None
+    heuristic_fn_dev.nnet = nnet  # (cached_heuristic_fn_dev refuses a model that calibrates on its input)
     return heuristic_fn_dev
+
+
+HCACHE_COUNTERS = ("rows", "hits", "dups", "evaluated", "uncached")
+
+
+def cached_heuristic_fn_dev(fn, row_bytes: int, slots: int):
+    """`fn` (a closure of get_heuristic_fn_dev's call form) behind a device-resident heuristic cache keyed by the uint8
+    network-input row (include/dca.h "heuristic cache", _lib.HeuristicCache): lookup, compaction of the rows to evaluate, ONE
+    call of `fn` on them, scatter, finish.  EXACT only when `fn` is batch-invariant — a row's value has the same bits in any
+    batch, row position or chunking: the fp32 parity FastResnet and the fp64 mode.  A network that calibrates on the rows it
+    sees (Fp8Resnet) is refused.  The one-hot call form (is_onehot=True) and empty inputs pass straight through to `fn`.
+    `counters()` reads the device counters (rows in, hits, dups, evaluated, uncached; evaluated = rows handed to `fn`,
+    uncached = the EVAL_ONLY rows among them) — one synchronisation, on demand only.  `cache` is the table's owner."""
+    from .. import _lib
+    nnet = getattr(fn, "nnet", None)
+    if getattr(fn, "calibrates_on_input", False) or bool(getattr(nnet, "takes_valid_rows", False)):
+        raise ValueError("cached_heuristic_fn_dev: the heuristic calibrates on the rows it sees (fp8): its values depend on the "
+                         "batch, a cache would change them")
+    cache = _lib.HeuristicCache(row_bytes, slots)
+    counts = torch.zeros(len(HCACHE_COUNTERS), dtype=torch.int64, device=cache.table.device)
+
+    @torch.no_grad()
+    def cached_fn_dev(x: torch.Tensor, is_onehot: bool = False) -> torch.Tensor:
+        if is_onehot or x.shape[0] == 0:
+            return fn(x, is_onehot)
+        n = x.shape[0]
+        h, slot, status = cache.lookup(x)
+        todo = ((status == _lib.HCACHE_EVAL_STORE) | (status == _lib.HCACHE_EVAL_ONLY)).nonzero().view(-1)
+        if todo.numel():
+            h[todo] = fn(x[todo]).to(torch.float32).view(-1)
+            cache.finish(h, slot, status)
+        per = torch.bincount(status.to(torch.int64), minlength=4)
+        counts.add_(torch.stack([per.sum(), per[_lib.HCACHE_HIT], per[_lib.HCACHE_DUP],
+                                 per[_lib.HCACHE_EVAL_STORE] + per[_lib.HCACHE_EVAL_ONLY], per[_lib.HCACHE_EVAL_ONLY]]))
+        assert h.shape[0] == n
+        return h
+
+    cached_fn_dev.cache = cache
+    cached_fn_dev.inner = fn
+    cached_fn_dev.valid_rows = None
+    cached_fn_dev.counters = lambda: dict(zip(HCACHE_COUNTERS, (int(v) for v in counts.tolist())))
+    if hasattr(fn, "onehot_dtype"):
+        cached_fn_dev.onehot_dtype = fn.onehot_dtype
+    return cached_fn_dev
 
 
 def get_heuristic_fn(nnet: nn.Module, device: torch.device, env, clip_zero: bool = False,

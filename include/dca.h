@@ -160,6 +160,50 @@ int dca_generate_states(int env, int dim, int64_t n, int back_lo, int back_hi, u
 int dca_bellman_backup(const float* h_children /*[n*A]*/, const uint8_t* solved_parent /*[n] or NULL*/, int64_t n,
                        int num_moves, int clip_zero, float* ctg_backup /*[n]*/, int32_t* argmin /*[n]*/, void* stream);
 
+/* Heuristic cache of the update step (csrc/dca_hcache.hip; `--update_cache`, DCA_UPDATE_CACHE): updaters/updater.py:11-54 hands
+ * all n x moves children of a batch to the target network although many are the same state.  This is a device-resident table
+ * keyed by the uint8 network-input row so that every distinct row is evaluated once.  It is EXACT only for a batch-invariant
+ * heuristic — a row's value has the same bits in any batch, row position or chunking: the fp32 parity network and the fp64
+ * mode; a network that calibrates on the batch it sees (fp8) must not be cached.
+ * The table is caller-owned device memory, 16-byte aligned, dca_hcache_bytes(row_bytes, slots) bytes (a pure function of its
+ * arguments: 64 + slots * (24 + 8 * ceil(row_bytes / 8)); DCA_E_BADARG unless row_bytes is 1..64 and slots a power of two in
+ * 2..2^30); all zero bytes = empty (dca_hcache_clear).  The rule:
+ *   tag       a slot's tag is dca_hash64 of the row (the hash defined below, D = row_bytes); tag 0 means empty, so a row that
+ *             hashes to 0 is never cached (EVAL_ONLY).
+ *   probing   the start slot is hash & (slots - 1); linear probing, at most 32 probes; an empty slot is claimed by one 64-bit
+ *             compare-and-swap of the tag.
+ *   fill limit  no slot is claimed once slots / 2 are in use; after that the table only answers.  A claim takes its place in
+ *             the count before the compare-and-swap and gives it back when it loses, so the count never passes slots / 2; a
+ *             row may therefore be turned away early (EVAL_ONLY, still correct) while the stored keys plus the rows of the
+ *             call in flight exceed slots / 2.
+ *   equality is the bytes, not the hash: a row whose tag matches is compared byte for byte with the slot's stored row before
+ *             it may share its value.
+ * dca_hcache_lookup sets one status per row (rows [n, row_bytes], row stride ld >= row_bytes bytes, any byte alignment):
+ *   DCA_HCACHE_HIT         h[i] is filled from the table;
+ *   DCA_HCACHE_EVAL_STORE  the first row of a new key in this call: the caller evaluates it and writes h[i];
+ *   DCA_HCACHE_DUP         the same bytes as an EVAL_STORE row of this call;
+ *   DCA_HCACHE_EVAL_ONLY   the row cannot be cached; the caller evaluates it and nothing is stored: the probe limit or the fill
+ *                          limit was reached, the tag matched but the bytes differ, or the key was claimed by an earlier call
+ *                          that never stored a value.
+ * slot[i] = the row's slot, -1 for EVAL_ONLY; h[i] is written for HIT rows only.  Which of several equal rows becomes the
+ * EVAL_STORE one is left to the race; no output depends on it, because a value is a function of the row alone.
+ * dca_hcache_finish (after the caller wrote h[i] of every EVAL_STORE and EVAL_ONLY row) first stores the EVAL_STORE values,
+ * then fills the DUP rows; every slot index it reads back is range-checked.  One lookup / finish pair at a time per table.
+ * No thread ever waits for another thread's write (what one must see of another is separated by a kernel boundary: lookup
+ * and finish are two launches each), there are no spin loops, every loop has a fixed bound.  n == 0 launches nothing; n < 2^31.
+ * DCA_E_BADARG before any device call: row_bytes outside 1..64, slots not a power of two, n < 0, ld < row_bytes, then a NULL
+ * or misaligned table / output. */
+#define DCA_HCACHE_HIT 0
+#define DCA_HCACHE_EVAL_STORE 1
+#define DCA_HCACHE_DUP 2
+#define DCA_HCACHE_EVAL_ONLY 3
+int64_t dca_hcache_bytes(int row_bytes, int64_t slots);
+int dca_hcache_clear(void* table, int row_bytes, int64_t slots, void* stream);
+int dca_hcache_lookup(void* table, int row_bytes, int64_t slots, const uint8_t* rows /*[n, ld]*/, int64_t n, int64_t ld,
+                      float* h /*[n]*/, int32_t* slot /*[n]*/, uint8_t* status /*[n]*/, void* stream);
+int dca_hcache_finish(void* table, int row_bytes, int64_t slots, int64_t n, const int32_t* slot /*[n]*/,
+                      const uint8_t* status /*[n]*/, float* h /*[n]*/, void* stream);
+
 /* state hash (a9).  The reference's hash VALUES are process-randomised SipHash (cube3.py:17-21)
  * or unpinned boost::hash_range (parallel_weighted_astar.cpp:104-111); what is pinned is key
  * equality.  This library defines, for a D-byte state split in little-endian 8-byte words
