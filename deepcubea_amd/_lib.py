@@ -149,7 +149,7 @@ def env_ids(env_name: str):
     m = re.search(r"puzzle(\d+)", name)
     if m:
         dim = int(math.sqrt(int(m.group(1)) + 1))
-        if 4 <= dim <= 7:
+        if 3 <= dim <= 7:
             return ENV_NPUZZLE, dim, dim * dim, 4, dim * dim
     m = re.search(r"lightsout(\d+)", name)
     if m and int(m.group(1)) == 7:

@@ -12,7 +12,7 @@
 //
 //   * a workgroup (16 waves; 12 where the weights leave no room for more) owns NT output columns; their fp32 weights, transposed
 //     — [K][NT], one 4 * NT-byte row per one-hot column — sit in LDS for the workgroup's whole life (NT = 64: cube3 83 KB, puzzle15
-//     66 KB, puzzle24 160 KB; NT = 16: puzzle35 83 KB, puzzle48 154 KB); after staging them the workgroup never meets at a barrier again;
+//     66 KB, puzzle24 160 KB, puzzle8 20 KB; NT = 16: puzzle35 83 KB, puzzle48 154 KB); after staging them the workgroup never meets at a barrier again;
 //   * each WAVE walks over steps of 64 / (NT / 4) * T states on its own: the step's state bytes come in as one 16-byte load per lane
 //     (issued three steps ahead) into a wave-private LDS slice; a lane owns (state, 4 consecutive columns): it pulls its state's
 //     bytes out of the slice as aligned dwords + v_alignbyte, then per position one row address, one ds_read_b128 and four adds —
@@ -273,7 +273,7 @@ using namespace dca;
 extern "C" {
 
 int dca_l1_embed_supported(int state_dim, int depth) {
-    return (state_dim == 54 && depth == 6) || (state_dim == depth && (depth == 16 || depth == 25 || depth == 36 || depth == 49)) ||
+    return (state_dim == 54 && depth == 6) || (state_dim == depth && (depth == 9 || depth == 16 || depth == 25 || depth == 36 || depth == 49)) ||
            (state_dim == 49 && depth == 6);
 }
 
@@ -289,6 +289,7 @@ int dca_l1_embed(const uint8_t* nnet_in, int64_t m, int state_dim, int depth, co
     if (m == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     if (state_dim == 54) return launch_embed<54, 6, 64, 16, 4>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);
+    if (state_dim == 9) return launch_embed<9, 9, 64, 16, 16>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);
     if (state_dim == 16) return launch_embed<16, 16, 64, 16, 8>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);
     if (state_dim == 25) return launch_embed<25, 25, 64, 12, 2>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);
     if (state_dim == 36) return launch_embed<36, 36, 16, 16, 1>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);

@@ -214,6 +214,7 @@ int launch_wgrad(const uint8_t* nn, int64_t m, const float* dy, int64_t ld_dy, i
 
 //                     D  DEPTH NT CW  R    S
 using WgCube3 = WgradGeo<54, 6, 64, 4, 32, 1024>;
+using WgPuzzle8 = WgradGeo<9, 9, 64, 1, 32, 1024>;
 using WgPuzzle15 = WgradGeo<16, 16, 64, 1, 32, 1024>;
 using WgPuzzle24 = WgradGeo<25, 25, 32, 1, 64, 2048>;
 using WgPuzzle35 = WgradGeo<36, 36, 16, 1, 64, 2048>;
@@ -223,6 +224,7 @@ using WgLights7 = WgradGeo<49, 6, 64, 4, 32, 1024>;
 static int64_t wgrad_slice_rows(int state_dim, int depth) {
     if (!dca_l1_embed_supported(state_dim, depth)) return -1;
     if (state_dim == 54) return WgCube3::S;
+    if (state_dim == 9) return WgPuzzle8::S;
     if (state_dim == 16) return WgPuzzle15::S;
     if (state_dim == 25) return WgPuzzle24::S;
     if (state_dim == 36) return WgPuzzle35::S;
@@ -274,6 +276,7 @@ int dca_l1_embed_wgrad(const uint8_t* nnet_in, int64_t m, int state_dim, int dep
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     if (state_dim == 54) return launch_wgrad<WgCube3>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);
+    if (state_dim == 9) return launch_wgrad<WgPuzzle8>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);
     if (state_dim == 16) return launch_wgrad<WgPuzzle15>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);
     if (state_dim == 25) return launch_wgrad<WgPuzzle24>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);
     if (state_dim == 36) return launch_wgrad<WgPuzzle35>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);

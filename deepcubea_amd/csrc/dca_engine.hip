@@ -3507,6 +3507,7 @@ int launch_expand(const dca_engine* e, int heur_id, bool want_oh, bool want_nn, 
     if (E.env == DCA_ENV_CUBE3) return launch_expand_env<DCA_ENV_CUBE3, 0>(e, heur_id, want_oh, want_nn, s);
     if (E.env == DCA_ENV_LIGHTSOUT) return launch_expand_env<DCA_ENV_LIGHTSOUT, 7>(e, heur_id, want_oh, want_nn, s);
     switch (E.dim) {
+        case 3: return launch_expand_env<DCA_ENV_NPUZZLE, 3>(e, heur_id, want_oh, want_nn, s);
         case 4: return launch_expand_env<DCA_ENV_NPUZZLE, 4>(e, heur_id, want_oh, want_nn, s);
         case 5: return launch_expand_env<DCA_ENV_NPUZZLE, 5>(e, heur_id, want_oh, want_nn, s);
         case 6: return launch_expand_env<DCA_ENV_NPUZZLE, 6>(e, heur_id, want_oh, want_nn, s);
@@ -3533,6 +3534,7 @@ int launch_pack(const dca_engine* e, hipStream_t s) {
     if (E.env == DCA_ENV_CUBE3) return launch_pack_env<DCA_ENV_CUBE3, 0>(e, s);
     if (E.env == DCA_ENV_LIGHTSOUT) return launch_pack_env<DCA_ENV_LIGHTSOUT, 7>(e, s);
     switch (E.dim) {
+        case 3: return launch_pack_env<DCA_ENV_NPUZZLE, 3>(e, s);
         case 4: return launch_pack_env<DCA_ENV_NPUZZLE, 4>(e, s);
         case 5: return launch_pack_env<DCA_ENV_NPUZZLE, 5>(e, s);
         case 6: return launch_pack_env<DCA_ENV_NPUZZLE, 6>(e, s);
@@ -3634,7 +3636,11 @@ int dca_engine_create_multi(dca_engine** out, int env, int dim, double weight, i
                             int semantics, int onehot_dtype, int num_instances) {
     DCA_ARG(out != nullptr);
     *out = nullptr;
-    DCA_ARG(env == DCA_ENV_CUBE3 || (env == DCA_ENV_NPUZZLE && dim >= 4 && dim <= 7) || (env == DCA_ENV_LIGHTSOUT && dim == 7));
+    if (env == DCA_ENV_NPUZZLE && (dim < 3 || dim > 7)) {
+        set_error("unsupported puzzle dim %d (3..7)", dim);
+        return DCA_E_BADARG;
+    }
+    DCA_ARG(env == DCA_ENV_CUBE3 || env == DCA_ENV_NPUZZLE || (env == DCA_ENV_LIGHTSOUT && dim == 7));
     DCA_ARG(batch_size >= 1 && batch_size <= (1 << 22));
     DCA_ARG(semantics == DCA_SEM_PY || semantics == DCA_SEM_CPP);
     DCA_ARG(onehot_dtype >= -1 && onehot_dtype <= DCA_DT_BF16);

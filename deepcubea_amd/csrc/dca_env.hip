@@ -281,7 +281,7 @@ __global__ void state_scan_kernel(int env, const uint8_t* __restrict__ st, int64
     const uint8_t* s = st + i * D;
     uint64_t h = hash_init(D), sum = 0;
     uint32_t manh = 0;
-    const int pdim = D == 16 ? 4 : D == 25 ? 5 : D == 36 ? 6 : D == 49 ? 7 : 0;  // sliding-puzzle side (0: cube3)
+    const int pdim = D == 9 ? 3 : D == 16 ? 4 : D == 25 ? 5 : D == 36 ? 6 : D == 49 ? 7 : 0;  // sliding-puzzle side (0: cube3)
     bool ok = true;
     uint32_t first = 0;
     for (int k = 0; k < D; k += 8) {
@@ -389,12 +389,13 @@ int expand_dispatch(int env, int dim, const uint8_t* parents, int64_t n, uint8_t
         return DCA_E_BADARG;
     }
     switch (dim) {
+        case 3: return launch_expand<DCA_ENV_NPUZZLE, 3>(parents, n, children, nnet_in, onehot, onehot_dtype, solved, hash, s);
         case 4: return launch_expand<DCA_ENV_NPUZZLE, 4>(parents, n, children, nnet_in, onehot, onehot_dtype, solved, hash, s);
         case 5: return launch_expand<DCA_ENV_NPUZZLE, 5>(parents, n, children, nnet_in, onehot, onehot_dtype, solved, hash, s);
         case 6: return launch_expand<DCA_ENV_NPUZZLE, 6>(parents, n, children, nnet_in, onehot, onehot_dtype, solved, hash, s);
         case 7: return launch_expand<DCA_ENV_NPUZZLE, 7>(parents, n, children, nnet_in, onehot, onehot_dtype, solved, hash, s);
     }
-    set_error("unsupported puzzle dim %d (4..7)", dim);
+    set_error("unsupported puzzle dim %d (3..7)", dim);
     return DCA_E_BADARG;
 }
 
@@ -410,7 +411,11 @@ const char* dca_last_error(void) { return g_err; }
 const uint8_t* dca_cube3_perm_table(void) { return &kCube3Perm.p[0][0]; }
 
 int dca_npuzzle_swap_table(int dim, uint8_t* out) {
-    DCA_ARG(dim >= 4 && dim <= 7 && out != nullptr);
+    if (dim < 3 || dim > 7) {
+        set_error("unsupported puzzle dim %d (3..7)", dim);
+        return DCA_E_BADARG;
+    }
+    DCA_ARG(out != nullptr);
     for (int z = 0; z < dim * dim; z++)
         for (int a = 0; a < 4; a++) out[z * 4 + a] = (uint8_t)npuzzle_swap(dim, z, a);
     return 0;
@@ -429,12 +434,13 @@ int dca_npuzzle_next_state(const uint8_t* in, int64_t n, int dim, int action, ui
     DCA_ARG(n >= 0 && action >= 0 && action < 4 && (n == 0 || (in && out)));
     hipStream_t s = (hipStream_t)stream;
     switch (dim) {
+        case 3: return launch_next<DCA_ENV_NPUZZLE, 3>(in, n, action, out, s);
         case 4: return launch_next<DCA_ENV_NPUZZLE, 4>(in, n, action, out, s);
         case 5: return launch_next<DCA_ENV_NPUZZLE, 5>(in, n, action, out, s);
         case 6: return launch_next<DCA_ENV_NPUZZLE, 6>(in, n, action, out, s);
         case 7: return launch_next<DCA_ENV_NPUZZLE, 7>(in, n, action, out, s);
     }
-    set_error("unsupported puzzle dim %d (4..7)", dim);
+    set_error("unsupported puzzle dim %d (3..7)", dim);
     return DCA_E_BADARG;
 }
 int dca_npuzzle_prev_state(const uint8_t* in, int64_t n, int dim, int action, uint8_t* out, void* stream) {
@@ -503,11 +509,14 @@ static int state_dim_of(int env, int dim, int* D) {
         *D = 96;
         return 0;
     }
-    if ((env == DCA_ENV_NPUZZLE && dim >= 4 && dim <= 7) || (env == DCA_ENV_LIGHTSOUT && dim == 7)) {
+    if ((env == DCA_ENV_NPUZZLE && dim >= 3 && dim <= 7) || (env == DCA_ENV_LIGHTSOUT && dim == 7)) {
         *D = dim * dim;
         return 0;
     }
-    set_error("unknown env %d / dim %d", env, dim);
+    if (env == DCA_ENV_NPUZZLE)
+        set_error("unsupported puzzle dim %d (3..7)", dim);
+    else
+        set_error("unknown env %d / dim %d", env, dim);
     return DCA_E_BADARG;
 }
 

@@ -579,7 +579,7 @@ using namespace dca;
 extern "C" {
 
 int dca_l1_supported(int state_dim, int depth) {
-    return (state_dim == 54 && depth == 6) || (state_dim == depth && (depth == 16 || depth == 25 || depth == 36 || depth == 49));
+    return (state_dim == 54 && depth == 6) || (state_dim == depth && (depth == 9 || depth == 16 || depth == 25 || depth == 36 || depth == 49));
 }
 
 int64_t dca_l1_kpad(int state_dim, int depth) { return (((int64_t)state_dim * depth + 15) / 16) * 16; }
@@ -600,6 +600,7 @@ int dca_l1_onehot_gemm(const uint8_t* nnet_in, int64_t m, int state_dim, int dep
     const uint8_t* wt = reinterpret_cast<const uint8_t*>(w_tiles);
     hipStream_t s = (hipStream_t)stream;
     switch (state_dim) {
+        case 9: return launch_l1<9, 9>(planes, nnet_in, m, wt, bias, relu, out, out_dtype, n_pad, overflow, s);
         case 54: return launch_l1<54, 6>(planes, nnet_in, m, wt, bias, relu, out, out_dtype, n_pad, overflow, s);
         case 16: return launch_l1<16, 16>(planes, nnet_in, m, wt, bias, relu, out, out_dtype, n_pad, overflow, s);
         case 25: return launch_l1<25, 25>(planes, nnet_in, m, wt, bias, relu, out, out_dtype, n_pad, overflow, s);
@@ -620,6 +621,7 @@ int dca_l1_onehot_gemm_mx(const uint8_t* nnet_in, int64_t m, int state_dim, int 
     uint8_t* sc = reinterpret_cast<uint8_t*>(out_scale);
     hipStream_t s = (hipStream_t)stream;
     switch (state_dim) {
+        case 9: return launch_l1<9, 9>(1, nnet_in, m, wt, bias, relu, out8, DCA_DT_E4M3, n_pad, nullptr, s, sc, ld_sc);
         case 54: return launch_l1<54, 6>(1, nnet_in, m, wt, bias, relu, out8, DCA_DT_E4M3, n_pad, nullptr, s, sc, ld_sc);
         case 16: return launch_l1<16, 16>(1, nnet_in, m, wt, bias, relu, out8, DCA_DT_E4M3, n_pad, nullptr, s, sc, ld_sc);
         case 25: return launch_l1<25, 25>(1, nnet_in, m, wt, bias, relu, out8, DCA_DT_E4M3, n_pad, nullptr, s, sc, ld_sc);

@@ -259,9 +259,9 @@ using namespace dca;
 extern "C" {
 
 // geometries whose whole weight tile (128 columns x KPAD bytes) fits LDS next to the waves' slices: cube3 (384: 48 KB),
-// puzzle15 (256: 32 KB), puzzle24 (640: 80 KB), lightsout7 (320: 40 KB)
+// puzzle8 (128: 16 KB), puzzle15 (256: 32 KB), puzzle24 (640: 80 KB), lightsout7 (320: 40 KB)
 int dca_l1_supported8(int state_dim, int depth) {
-    return (state_dim == 54 && depth == 6) || (state_dim == 16 && depth == 16) || (state_dim == 25 && depth == 25) ||
+    return (state_dim == 54 && depth == 6) || (state_dim == 9 && depth == 9) || (state_dim == 16 && depth == 16) || (state_dim == 25 && depth == 25) ||
            (state_dim == 49 && depth == 6);
 }
 
@@ -280,6 +280,7 @@ int dca_l1_onehot_gemm8(const uint8_t* nnet_in, int64_t m, int state_dim, int de
     uint8_t* o = reinterpret_cast<uint8_t*>(out8);
     hipStream_t s = (hipStream_t)stream;
     if (state_dim == 54) return launch_l1_8<54, 6>(nnet_in, m, wt, scale, bias, relu, o, n_pad, s);
+    if (state_dim == 9) return launch_l1_8<9, 9>(nnet_in, m, wt, scale, bias, relu, o, n_pad, s);
     if (state_dim == 16) return launch_l1_8<16, 16>(nnet_in, m, wt, scale, bias, relu, o, n_pad, s);
     if (state_dim == 25) return launch_l1_8<25, 25>(nnet_in, m, wt, scale, bias, relu, o, n_pad, s);
     return launch_l1_8<49, 6>(nnet_in, m, wt, scale, bias, relu, o, n_pad, s);

@@ -117,12 +117,16 @@ int dca_generate_states(int env, int dim, int64_t n, int back_lo, int back_hi, u
         return launch_scramble<DCA_ENV_LIGHTSOUT, 7>(n, back_lo, back_hi, seed, index0, out_states, out_num_back, out_moves,
                                                      moves_stride, s);
     switch (env == DCA_ENV_NPUZZLE ? dim : -1) {
+        case 3: return launch_scramble<DCA_ENV_NPUZZLE, 3>(n, back_lo, back_hi, seed, index0, out_states, out_num_back, out_moves, moves_stride, s);
         case 4: return launch_scramble<DCA_ENV_NPUZZLE, 4>(n, back_lo, back_hi, seed, index0, out_states, out_num_back, out_moves, moves_stride, s);
         case 5: return launch_scramble<DCA_ENV_NPUZZLE, 5>(n, back_lo, back_hi, seed, index0, out_states, out_num_back, out_moves, moves_stride, s);
         case 6: return launch_scramble<DCA_ENV_NPUZZLE, 6>(n, back_lo, back_hi, seed, index0, out_states, out_num_back, out_moves, moves_stride, s);
         case 7: return launch_scramble<DCA_ENV_NPUZZLE, 7>(n, back_lo, back_hi, seed, index0, out_states, out_num_back, out_moves, moves_stride, s);
     }
-    set_error("unknown env %d / dim %d", env, dim);
+    if (env == DCA_ENV_NPUZZLE)
+        set_error("unsupported puzzle dim %d (3..7)", dim);
+    else
+        set_error("unknown env %d / dim %d", env, dim);
     return DCA_E_BADARG;
 }
 

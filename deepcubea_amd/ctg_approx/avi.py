@@ -59,7 +59,7 @@ UPDATE_CACHE_HELP = ("heuristic cache of the update step: off (default) | auto |
                      "uses) and the fp64 mode; a network that calibrates on its batch (fp8) is refused.  No cache is built while "
                      "there is no target network (the all-zeros heuristic)")
 _OPTIONS = (
-    ("env", str, REQUIRED, "Environment"),
+    ("env", str, REQUIRED, "Environment: cube3, puzzle8, puzzle15, puzzle24, puzzle35, puzzle48, lightsout7"),
     ("debug", "flag", False, ""),
     ("lr", float, 0.001, "Initial learning rate"),
     ("lr_d", float, 0.9999993, "Learning rate decay: lr * (lr_d ^ itr)"),

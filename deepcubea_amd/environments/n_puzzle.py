@@ -1,4 +1,4 @@
-"""NPuzzle — mirror of the reference `environments/n_puzzle.py` ((n^2-1)-puzzle, n = 4..7) behind the
+"""NPuzzle — mirror of the reference `environments/n_puzzle.py` ((n^2-1)-puzzle, n = 3..7) behind the
 same Environment API; batched operations run on the MI355X (libdca_hip.so)."""
 from __future__ import annotations
 
@@ -42,8 +42,8 @@ class NPuzzle(Environment):
 
     def __init__(self, dim: int):
         super().__init__()
-        if not (4 <= dim <= 7):
-            raise ValueError("NPuzzle dim must be 4..7 (puzzle15/24/35/48), got %d" % dim)
+        if not (3 <= dim <= 7):
+            raise ValueError("NPuzzle dim must be 3..7 (puzzle8/15/24/35/48), got %d" % dim)
         self.dim: int = dim
         self._dim = dim
         self.state_dim = dim * dim

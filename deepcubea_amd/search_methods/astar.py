@@ -218,7 +218,8 @@ def build_parser() -> ArgumentParser:
     parser.add_argument('--states', type=str, required=True, help="File containing states to solve")
     parser.add_argument('--model_dir', type=str, required=True,
                         help="Directory of nnet model, or synthetic:SEED, or builtin:manhattan / builtin:zero")
-    parser.add_argument('--env', type=str, required=True, help="Environment: cube3, puzzle15, puzzle24, ...")
+    parser.add_argument('--env', type=str, required=True, help="Environment: cube3, puzzle8, puzzle15, puzzle24, puzzle35, puzzle48, lightsout7 "
+                                                                      "(puzzle8 has every layer-1 kernel puzzle15 has: no --nnet_dtype mode is on a fall-back there)")
     parser.add_argument('--batch_size', type=int, default=1, help="Batch size for BWAS")
     parser.add_argument('--weight', type=float, default=1.0, help="Weight of path cost")
     parser.add_argument('--language', type=str, default="hip", help="hip (the MI355X engine)")

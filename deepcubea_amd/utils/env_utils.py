@@ -1,9 +1,9 @@
 """Environment registry of the path (names as in the reference's `utils/env_utils.py:6-28`): `cube3` and
-`puzzle<N>` for N in {15, 24, 35, 48}, and `lightsout7` (the remaining environment of the reference's C++ core
+`puzzle<N>` for N in {8, 15, 24, 35, 48}, and `lightsout7` (the remaining environment of the reference's C++ core
 that its Python harness can drive).  Sokoban is outside the hot-path scope and not built."""
 import re
 
-_PUZZLE_DIMS = {15: 4, 24: 5, 35: 6, 48: 7}
+_PUZZLE_DIMS = {8: 3, 15: 4, 24: 5, 35: 6, 48: 7}
 
 
 def get_environment(env_name: str):

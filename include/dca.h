@@ -34,6 +34,8 @@
 extern "C" {
 #endif
 
+/* Still 6 with puzzle8: no signature changed; only the accepted range of every puzzle `dim` argument grew from 4..7 to 3..7
+ * (a refusal names the range: "unsupported puzzle dim %d (3..7)"), and the layer-1 geometry (9, 9) joined the instantiated ones. */
 #define DCA_ABI_VERSION 6
 
 /* library error codes (negative; positive values are hipError_t) */
@@ -45,7 +47,7 @@ extern "C" {
 
 /* environments (utils/env_utils.py:6-28 registry names) */
 #define DCA_ENV_CUBE3 0   /* "cube3": 54 stickers, 12 moves */
-#define DCA_ENV_NPUZZLE 1 /* "puzzle15/24/35/48": dim 4..7, 4 moves U D L R */
+#define DCA_ENV_NPUZZLE 1 /* "puzzle8/15/24/35/48": dim 3..7, 4 moves U D L R */
 #define DCA_ENV_LIGHTSOUT 2 /* "lightsout7": dim 7, 49 cells in {0,1}, 49 moves (press cell a: it and its 4-neighbours flip) */
 #define DCA_ENV_CUBE4 3   /* the 4x4x4 cube of the reference's C++ core (cpp/environments.cpp:263-370): 96 stickers, 24 moves
                            * (12 outer-layer turns, then 12 inner-slice turns; move a^1 is the inverse of move a); solved =
@@ -370,7 +372,7 @@ int dca_bn_train_backward(const float* dy, const float* x, const float* y /*need
  * pytorch_models.py:l1_weight_tiles builds it).  out: [m, n_pad] in out_dtype (DCA_DT_*), row stride n_pad; DCA_DT_F16_PLANES
  * writes the next layer's dca_f16x3_gemm operand directly ([m, n_pad] fp16 high halves, then [m, n_pad] low halves).
  * K is walked in LDS-sized chunks (cube3: one piece; the sliding puzzles, K up to 2401: 320 one-hot columns at a time).
- * Instantiated for cube3 (54, 6) and the sliding puzzles (16/25/36/49): dca_l1_supported(state_dim, depth) != 0.
+ * Instantiated for cube3 (54, 6) and the sliding puzzles (9/16/25/36/49): dca_l1_supported(state_dim, depth) != 0.
  * ------------------------------------------------------------------------------------------------------------------ */
 int dca_l1_supported(int state_dim, int depth);
 int64_t dca_l1_kpad(int state_dim, int depth);
@@ -386,7 +388,7 @@ int dca_l1_onehot_gemm(const uint8_t* nnet_in /*[m, state_dim]*/, int64_t m, int
  * w_tiles: [n_pad/128][k_pad/16][128][16] e4m3 bytes, k_pad = dca_l1_kpad8(state_dim, depth) (K zero padded to a multiple of 64;
  * deepcubea_amd/utils/pytorch_models.py:l1_weight_tiles8 builds it); n_pad % 128 == 0; nnet_in and out8 16-byte aligned;
  * out8: [m, n_pad] bytes.  Instantiated where the 128-column weight tile fits LDS: dca_l1_supported8() != 0 (cube3,
- * puzzle15, puzzle24, lightsout7); other geometries keep the bf16-pipe kernel. */
+ * puzzle8, puzzle15, puzzle24, lightsout7); other geometries keep the bf16-pipe kernel. */
 int dca_l1_supported8(int state_dim, int depth);
 int64_t dca_l1_kpad8(int state_dim, int depth);
 int dca_l1_onehot_gemm8(const uint8_t* nnet_in /*[m, state_dim]*/, int64_t m, int state_dim, int depth, const void* w_tiles,
@@ -402,7 +404,7 @@ int dca_l1_onehot_gemm8(const uint8_t* nnet_in /*[m, state_dim]*/, int64_t m, in
  * out_dtype: DCA_DT_F32 [m, n_pad], DCA_DT_BF16 [m, n_pad], or DCA_DT_F16_PLANES (dca_f16x3_gemm's operand: [m, n_pad] fp16
  * high halves, then [m, n_pad] low halves; *overflow set to 1 if a value exceeds fp16), or DCA_DT_E4M3 [m, n_pad] bytes,
  * saturating (the caller has folded the activation scale into w_t and bias).  State bytes must be < depth.
- * Instantiated for the geometries dca_l1_embed_supported() names (cube3, puzzle15/24/35/48, lightsout7). */
+ * Instantiated for the geometries dca_l1_embed_supported() names (cube3, puzzle8/15/24/35/48, lightsout7). */
 int dca_l1_embed_supported(int state_dim, int depth);
 int dca_l1_embed(const uint8_t* nnet_in /*[m, state_dim]*/, int64_t m, int state_dim, int depth, const float* w_t, int64_t n_pad,
                  const float* bias /*[n_pad]*/, int relu, void* out, int out_dtype, int* overflow /*device flag or NULL*/,
@@ -419,7 +421,8 @@ int dca_l1_embed(const uint8_t* nnet_in /*[m, state_dim]*/, int64_t m, int state
  * are cut into consecutive slices of S = dca_l1_embed_wgrad_slice_rows(state_dim, depth) rows, the last one shorter — S depends
  * on the geometry alone, never on m or n (0 would mean: one slice); within a slice every element of dW and db is a sequential
  * fp32 sum over the rows in ascending order, starting from +0.0; the slices' sums are then added in ascending slice order, in
- * fp32, again from +0.0.
+ * fp32, again from +0.0.  S today: 1024 for cube3 (54, 6), puzzle8 (9, 9), puzzle15 (16, 16) and lightsout7 (49, 6); 2048 for
+ * puzzle24 (25, 25), puzzle35 (36, 36) and puzzle48 (49, 49) — read it from the accessor, these are the values the order rule has.
  * State bytes: the forward's contract is "< depth".  Here a position whose byte is >= depth contributes NOTHING to dW (a bad byte
  * would otherwise be a write to another position's rows); its row still counts in db.
  * workspace: dca_l1_embed_wgrad_workspace_bytes(m, state_dim, depth, n) bytes of device memory, 4-byte aligned (the slices'
