@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "dca_wgrad_f16", "dca_wgrad_splits", "dca_wgrad_workspace_bytes",
     "dca_f16_gemm", "dca_cast_planes_scaled", "dca_cast_rows_scaled",
     "dca_hcache_bytes", "dca_hcache_clear", "dca_hcache_lookup", "dca_hcache_finish",
+    "dca_engine_known_duplicate",
 ]
 
 
@@ -109,6 +110,7 @@ def lib() -> C.CDLL:
         _lib.dca_hcache_lookup.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
         _lib.dca_hcache_finish.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.dca_engine_known_duplicate.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int]
         _lib.dca_engine_destroy.restype = None
         if _lib.dca_abi_version() != 6:
             raise DcaError("libdca_hip.so ABI version mismatch")
@@ -181,6 +183,13 @@ def npuzzle_swap_table(dim: int) -> np.ndarray:
     out = np.zeros((dim * dim, 4), np.uint8)
     check(lib().dca_npuzzle_swap_table(dim, out.ctypes.data_as(C.c_void_p)), "dca_npuzzle_swap_table")
     return out
+
+
+def engine_known_duplicate(env: int, dim: int, g_parent: int, move_parent: int, action: int, blank: int = 0) -> bool:
+    """Does the engine's expansion skip the CLOSED probe for this child (include/dca_debug.h)?  Host only."""
+    rc = lib().dca_engine_known_duplicate(int(env), int(dim), int(g_parent), int(move_parent), int(action), int(blank))
+    check(min(rc, 0), "dca_engine_known_duplicate")
+    return rc == 1
 
 
 # ------------------------------------------------------------------------------ device ops

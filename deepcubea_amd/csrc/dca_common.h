@@ -112,6 +112,20 @@ __host__ __device__ inline uint32_t lightsout_flip(int dim, int a, int i) {
                       (y > 0 && i == a - 1));
 }
 
+// A child whose state CLOSED is known to hold at a smaller path cost, told from its parent's node fields alone:
+// the search never keeps it, so the engine's expansion does not probe CLOSED for it.  Parent P: path cost g_parent, made by move
+// mv_parent (0xFF: the root); child: move a, `noop` = the move leaves P's state as it is (sliding puzzles: an ineligible
+// move, npuzzle_swap == the blank).
+//   undo child  (a inverts mv_parent: a ^ 1 on the cubes and the sliding puzzles, a itself on LightsOut): the state of P's own
+//               parent G, which went through the CLOSED check before P existed — from g_parent >= 2 on: in PY semantics the
+//               root is never put into CLOSED (astar.py:55, 64-90), so the undo child of a depth-1 node is a NEW state there;
+//   no-op child: P's own state, in CLOSED since P was kept — from g_parent >= 1 on (not for the root, as above).
+// (a node with g >= 2 was never made by a no-op move: such a child is only ever kept at the root.)
+__host__ __device__ inline bool known_duplicate(int env, uint32_t g_parent, uint32_t mv_parent, uint32_t a, bool noop) {
+    const uint32_t inv = env == DCA_ENV_LIGHTSOUT ? a : (a ^ 1u);
+    return (g_parent >= 2u && mv_parent == inv) || (g_parent >= 1u && noop);
+}
+
 // byte i of the goal state: cube3 arange(54) (cube3.py:62-69), puzzles 1..n^2-1,0 (n_puzzle.py:69-76), lightsout zeros
 // (lights_out.py:55-63)
 __host__ __device__ inline uint32_t goal_byte(int env, int D, int i) {

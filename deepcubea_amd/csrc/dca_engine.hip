@@ -2587,7 +2587,7 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
     uint8_t* lpar = smem;
     uint8_t* ltab = smem + TL::PAR_BYTES;
     uint8_t* lst = smem + TL::LDS_BYTES;  // child rows of the tile, laid out exactly like their HBM destination
-    __shared__ uint32_t l_pid[TP], l_g[TP];
+    __shared__ uint32_t l_pid[TP], l_g[TP], l_mv[TP];
     __shared__ uint32_t l_qn, l_qcc[kThreads], l_qrep[kThreads], l_qres[kThreads];
     __shared__ uint32_t l_ohq;  // one-hot rows: next 1 KiB piece (one wave-wide 16-byte store) nobody has claimed yet
     static_assert((EV::D + 3) / 4 < 16, "no spare lane per row for the parent's path cost");
@@ -2624,13 +2624,15 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
         static_assert(WPR <= 16, "row wider than 64 bytes");
         const uint32_t w = threadIdx.x & 15;  // 16 lanes per row, 16 rows per round
         // (a spare lane of every row fetches the parent's path cost in the same round trip as the row itself: the
-        // per-child loop below used to wait for it — a dependent random access — before it could write anything)
+        // per-child loop below used to wait for it — a dependent random access — before it could write anything; and the
+        // move that made the parent, same dependent level: what tells the children that need no CLOSED probe)
 #pragma unroll
         for (uint32_t r = threadIdx.x >> 4; r < (uint32_t)TP; r += 16) {
         if (r < np && w == WPR) {
             const uint32_t pid = E.pop_id[r0 + r] & ID_MASK;
             l_pid[r] = pid;
             l_g[r] = (uint32_t)E.g[pid];
+            l_mv[r] = (uint32_t)E.move[pid];
         }
         if (r < np && w < WPR) {
             gp<const uint8_t> row = E.state + (size_t)(E.pop_id[r0 + r] & ID_MASK) * EV::D;
@@ -2751,6 +2753,7 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
         const bool cvalid = cc < nchild;
         uint64_t h = 0;
         uint64_t roww[(EV::D + 7) / 8];  // the child's row, 8 bytes a word (compared against representatives' rows)
+        bool known = false;  // a duplicate by its parent's node fields alone (known_duplicate, dca_common.h): never probed
         if (cvalid) {
         uint32_t r = cc / EV::A, a = cc - r * EV::A;
         uint64_t sum = 0;
@@ -2788,6 +2791,9 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
         h = hash_final(h);
         const uint32_t j = j0 + cc, id = base + j, pid = l_pid[r];
         const uint32_t gp = l_g[r];
+        bool noop = false;  // sliding puzzles: an ineligible move (swap target == the blank, from the tile's staged table)
+        if constexpr (ENV == DCA_ENV_NPUZZLE) noop = ltab[r * 8 + 1 + a] == ltab[r * 8];
+        known = known_duplicate(ENV, gp, l_mv[r], a, noop);
         if (a == 0) E.pop_g[r0 + r] = gp;  // the parents' path costs in pop order: what the dedup / push kernels read
         // (the chain marks child_multi are cleared by k_commit after it has read them, not here: another workgroup of this
         // launch may set this child's mark before or after this point)
@@ -2802,8 +2808,12 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
             constexpr int NWD = (EV::D + 3) / 4;
             const uint32_t j = j0 + cc, id = base + j;
             const uint64_t tag = h >> 32;
-            bool active = cvalid, inserted = false, paused = false;
-            uint32_t slot = (uint32_t)h & E.tab_mask, v0 = GINF, rep_id = 0, probes = 0, qi = 0;
+            // A known duplicate never enters the loop: no slot load, no row compare, no exchange on the slot's head.  It leaves the
+            // record that k_commit / k_decide read as "alone on its chain, not kept, not new": no link, flags 0, v0 = 0 (g < v0 is
+            // false) and its home slot (valid; the slot of a child that is neither kept nor new is never used).  The chain of its
+            // state goes without it — it would neither be kept nor dominate a kept member nor be the minimum beside one.
+            bool active = cvalid && !known, inserted = false, paused = false;
+            uint32_t slot = (uint32_t)h & E.tab_mask, v0 = known ? 0u : GINF, rep_id = 0, probes = 0, qi = 0;
             __syncthreads();  // the round's rows are staged (lst) — and l_qn is zero
             for (;;) {
                 if (active && !paused) {
@@ -2911,7 +2921,7 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
             // which spares most children (new states are ~85 % on cube3) their second atomic.
             if (cvalid) {
                 uint32_t prev = NIL;  // the child chained in front of this one (batch-relative index)
-                if (!inserted) {
+                if (!inserted && !known) {
                     const uint32_t old_head = atomicExch(&E.tab[slot].head, id);
                     if (old_head >= base)
                         prev = old_head - base;
@@ -4027,6 +4037,17 @@ int dca_engine_plan_chunk(int64_t host_iter, int remaining, int* n, uint64_t* re
     plan_chunk((long)host_iter, remaining, n, &m);
     *rebase_mask = (uint64_t)m;
     return 0;
+}
+
+int dca_engine_known_duplicate(int env, int dim, int64_t g_parent, int move_parent, int action, int blank) {
+    // the very function k_expand calls, on the host; the geometry checks are those of the engine's instantiations
+    const bool puzzle = env == DCA_ENV_NPUZZLE && dim >= 3 && dim <= 7;
+    DCA_ARG((env == DCA_ENV_CUBE3 && dim == 0) || (env == DCA_ENV_LIGHTSOUT && dim == 7) || puzzle);
+    const int A = env == DCA_ENV_CUBE3 ? 12 : puzzle ? 4 : dim * dim;
+    DCA_ARG(g_parent >= 0 && g_parent < (int64_t)GINF && move_parent >= 0 && move_parent <= 0xFF && action >= 0 && action < A);
+    DCA_ARG(!puzzle || (blank >= 0 && blank < dim * dim));
+    const bool noop = puzzle && npuzzle_swap(dim, blank, action) == blank;
+    return known_duplicate(env, (uint32_t)g_parent, (uint32_t)move_parent, (uint32_t)action, noop) ? 1 : 0;
 }
 
 int dca_engine_run_builtin(dca_engine* e, int heur_id, int iters, int use_graph, void* stream) {

@@ -18,6 +18,13 @@ extern "C" {
  * whole periods) and which of its iterations are rebase iterations (bit i of rebase_mask).  For tests of the cutting rule. */
 int dca_engine_plan_chunk(int64_t host_iter, int remaining, int* n, uint64_t* rebase_mask);
 
+/* Host-only (no device needed): does the engine's expansion skip the CLOSED probe for the child by move `action` of a node with
+ * path cost g_parent that was made by move move_parent (0xFF: the root)?  1 = yes (a known duplicate: the undo child from
+ * g_parent >= 2, a sliding puzzle's ineligible move from g_parent >= 1), 0 = no.  The rule the kernel evaluates, for tests.
+ * env / dim as the engine instantiates them (cube3 / 0, lightsout / 7, sliding puzzles / 3..7); blank = position of the
+ * puzzle's blank in the parent (ignored for the other environments).  DCA_E_BADARG for anything out of range.            */
+int dca_engine_known_duplicate(int env, int dim, int64_t g_parent, int move_parent, int action, int blank);
+
 /* Device-side profile of `iters` iterations of run_builtin (use_graph as there): every workgroup stamps the device wall
  * clock at entry and exit, per launch the host takes max(end) - min(start) as the launch's busy span and the distance to
  * the previous launch's end as the gap in front of it — measured INSIDE the replayed hipGraph, which HIP events between
