@@ -200,10 +200,11 @@ int hip_fail(hipError_t e, const char* what);
         if (_e != hipSuccess) return ::dca::hip_fail(_e, #call); \
     } while (0)
 
+// (the text names the refusing entry point in front of the condition, so that a truncated message still says who refused)
 #define DCA_ARG(cond)                                        \
     do {                                                     \
         if (!(cond)) {                                       \
-            ::dca::set_error("bad argument: %s", #cond);     \
+            ::dca::set_error("bad argument: %s: %s", __func__, #cond); \
             return DCA_E_BADARG;                             \
         }                                                    \
     } while (0)

@@ -872,6 +872,7 @@ int dca_cast_rows_scaled(const float* w, int64_t n, int64_t k, int64_t ld, void*
 int dca_split_planes(const float* x, int64_t m, int64_t n, int64_t ld, void* out_h, void* out_l, int64_t ldo, int* overflow,
                      void* stream) {
     DCA_ARG(x && out_h && out_l && m >= 0 && n >= 4 && n % 4 == 0 && ld >= n && ld % 4 == 0 && ldo >= n && ldo % 4 == 0);
+    DCA_ARG((uintptr_t)x % 16 == 0 && ((uintptr_t)out_h | (uintptr_t)out_l) % 8 == 0);  // float4 loads, 8-byte plane stores
     if (m == 0) return 0;
     int64_t blocks = (m * (n / 4) + 255) / 256;
     if (blocks > 8192) blocks = 8192;

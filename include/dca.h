@@ -20,7 +20,9 @@
  *     asynchronous unless documented otherwise; the library never frees or
  *     reallocates caller memory.
  *   - return value: 0 = ok, >0 = hipError_t, <0 = library error (DCA_E_*);
- *     dca_last_error() returns a thread-local message for the last failure.
+ *     dca_last_error() returns a thread-local message for the last failure.  An
+ *     argument check that fails returns DCA_E_BADARG before any device call, and the
+ *     message is "bad argument: <entry point>: <the condition that failed>".
  *   - state rows are row-major uint8: cube3 [n,54] sticker ids 0..53; puzzles
  *     [n,dim*dim] tile ids 0..dim*dim-1 (0 = blank) — the reference's own numpy layout.
  */
@@ -454,6 +456,9 @@ int dca_act_split(const float* y, const float* bias /*[n] or NULL*/, const float
  * Outputs (row stride ldo): out_h / out_l — the result's planes, i.e. the NEXT layer's operand — and / or x_out, the fp32
  * result (the next residual block's skip, or the input of the 1-wide output layer).  overflow: device flag set when a value
  * does not fit fp16 (|v| > 60000; the caller then redoes the batch with fp32 GEMMs), or NULL.
+ * Any m >= 0, any n >= 1 (m == 0 returns 0 without a launch); lda, ldw >= k; ldo >= n and ldo % 4 == 0; out_h / out_l: both or
+ * neither, 8-byte aligned; x_out / skip 16-byte aligned; at least one output.  a_h / a_l may start at any 16-byte aligned column
+ * of wider matrices.  Only [0, m) x [0, n) of an output is written (row stride ldo): columns n..ldo and rows from m keep their bytes.
  * ------------------------------------------------------------------------------------------------------------------ */
 int dca_f16x3_gemm(const void* a_h, const void* a_l, int64_t m, int k, int64_t lda, const void* w_h, const void* w_l, int n,
                    int64_t ldw, const float* col_scale /*[n] or NULL*/, double alpha, const float* bias /*[n] or NULL*/,
@@ -465,7 +470,9 @@ int dca_f16x3_gemm(const void* a_h, const void* a_l, int64_t m, int k, int64_t l
  * (DCA_DT_BF16 or DCA_DT_F16), fp32 accumulation on the 16-bit MFMA pipes, bias fp32, the residual `skip` [m, ldo] in
  * `dtype`, result rounded to nearest even — bias, residual add, ReLU and rounding ride in the epilogue (csrc/dca_gemm16.hip).
  * a [m, lda], w [n, ldw] (rows = output units); k % 64 == 0; lda, ldw % 8 == 0; ldo % 4 == 0; a / w 16-byte, out / skip
- * 8-byte aligned.  `out` may not alias `a`; it may alias `skip`. */
+ * 8-byte aligned.  `out` may not alias `a` — a byte range [out, out + ((m - 1) ldo + n) elements) that meets a's is refused with
+ * DCA_E_BADARG —; it may be `skip` itself (the in-place residual).  Any m >= 0, n >= 1; only [0, m) x [0, n) of `out` is
+ * written.  out / skip that are 8- but not 16-byte aligned, or ldo % 8 != 0, are served by the general tail: same bits. */
 int dca_gemm16(const void* a, int64_t m, int k, int64_t lda, const void* w, int n, int64_t ldw, int dtype,
                const float* bias /*[n] or NULL*/, const void* skip /*[m, ldo] or NULL*/, int relu, void* out, int64_t ldo,
                void* stream);
@@ -475,7 +482,10 @@ int dca_gemm16(const void* a, int64_t m, int k, int64_t lda, const void* w, int 
  *   v = relu?( (a . w^T)[m,n] * scale[n] + bias[n] (+ skip[m,n]) )        scale[n] = activation scale x weight scale of unit n
  * leaving as bf16 (out16 [m, ldo16], the residual stream; may be `skip` itself) and / or quantised for the next layer:
  * out8 [m, ldo8] = e4m3(sat(v * out8_scale)).  skip is bf16 with out16's row stride.  Replaces utils/pytorch_models.py:57-86
- * (BatchNorm folded) as PyTorch runs it, at fp8 operand precision: never a parity mode. */
+ * (BatchNorm folded) as PyTorch runs it, at fp8 operand precision: never a parity mode.
+ * a / w 16-byte aligned; out16 / skip 8-byte aligned, ldo16 >= n and % 4 == 0 (wanted whenever out16 or skip is given); out8
+ * 4-byte aligned, ldo8 >= n and % 4 == 0, out8_scale > 0; at least one output.  An out16 or out8 whose bytes meet a's is refused
+ * with DCA_E_BADARG.  Any m >= 0, n >= 1; only [0, m) x [0, n) of an output is written. */
 int dca_gemm8(const void* a, int64_t m, int k, int64_t lda, const void* w, int n, int64_t ldw, const float* scale /*[n]*/,
               const float* bias /*[n] or NULL*/, const void* skip /*bf16 [m, ldo16] or NULL*/, int relu, void* out16 /*or NULL*/,
               int64_t ldo16, void* out8 /*or NULL*/, int64_t ldo8, double out8_scale, void* stream);
@@ -487,6 +497,9 @@ int dca_gemm8(const void* a, int64_t m, int k, int64_t lda, const void* w, int n
  *   v = relu?( (sum_blocks 2^(sa - 127) * a8 . w8^T)[m,n] * w_scale[n] + bias[n] (+ skip[m,n]) )
  * a_scale [m, ld_asc] (k / 64 bytes per row; k % 256 == 0, k <= 8192); out8 / out8_scale [m, ld_osc] (n / 64 bytes per row,
  * n % 64 == 0) = the next layer's operand and its block scales, or both NULL; out16 / skip as in dca_gemm8.
+ * a_scale 4-byte aligned, ld_asc >= k / 64 and % 4 == 0; ld_osc >= n / 64.  Refused with DCA_E_BADARG: one of out8 / out8_scale
+ * without the other, an output whose bytes meet a's, out8_scale == a_scale.  Only [0, m) x [0, n) of out16 / out8 and
+ * [0, m) x [0, n / 64) of out8_scale are written.
  * dca_l1_onehot_gemm_mx: layer 1 (one bf16 weight plane, dca_l1_onehot_gemm's tiles) leaving in the same form. */
 int dca_gemm8_mx(const void* a, const void* a_scale, int64_t m, int k, int64_t lda, int64_t ld_asc, const void* w, int n,
                  int64_t ldw, const float* w_scale /*[n]*/, const float* bias /*[n] or NULL*/,
@@ -496,9 +509,11 @@ int dca_l1_onehot_gemm_mx(const uint8_t* nnet_in /*[m, state_dim]*/, int64_t m, 
                           int64_t n_pad, const float* bias /*[n_pad]*/, int relu, void* out8 /*[m, n_pad] e4m3*/,
                           void* out_scale /*[m, ld_sc] E8M0*/, int64_t ld_sc, void* stream);
 /* x [m, n] (row stride ld; DCA_DT_F32 or DCA_DT_BF16) -> e4m3(sat(x * scale)) bytes [m, ldo]: the entry into an fp8 layer for
- * activations that did not come out of an fp8 epilogue.  n % 4 == 0. */
+ * activations that did not come out of an fp8 epilogue.  n % 4 == 0, ld % 4 == 0, ldo % 4 == 0, scale > 0; x 16-byte (fp32) or
+ * 8-byte (bf16), out 4-byte aligned; only [0, m) x [0, n) of out is written. */
 int dca_quant_e4m3(const void* x, int dtype, int64_t m, int64_t n, int64_t ld, double scale, void* out, int64_t ldo, void* stream);
-/* fp32 [m, n] (row stride ld) -> its fp16 planes (row stride ldo); n % 4 == 0 */
+/* fp32 [m, n] (row stride ld) -> its fp16 planes (row stride ldo); n % 4 == 0, ld % 4 == 0, ldo % 4 == 0, x 16-byte and the
+ * planes 8-byte aligned; only [0, m) x [0, n) of a plane is written. */
 int dca_split_planes(const float* x, int64_t m, int64_t n, int64_t ld, void* out_h, void* out_l, int64_t ldo,
                      int* overflow /*or NULL*/, void* stream);
 
