@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "dca_f16_gemm", "dca_cast_planes_scaled", "dca_cast_rows_scaled",
     "dca_hcache_bytes", "dca_hcache_clear", "dca_hcache_lookup", "dca_hcache_finish",
     "dca_engine_known_duplicate",
+    "dca_pdb_bytes", "dca_pdb_build", "dca_pdb_eval",
 ]
 
 
@@ -83,7 +84,7 @@ def lib() -> C.CDLL:
             fn = getattr(_lib, name)  # AttributeError here = stale build of libdca_hip.so
             if name not in ("dca_last_error", "dca_cube3_perm_table", "dca_cube4_perm_table", "dca_engine_destroy", "dca_bn_workspace_bytes",
                             "dca_l1_kpad", "dca_l1_kpad8", "dca_l1_embed_wgrad_slice_rows", "dca_l1_embed_wgrad_workspace_bytes",
-                            "dca_wgrad_workspace_bytes", "dca_hcache_bytes"):
+                            "dca_wgrad_workspace_bytes", "dca_hcache_bytes", "dca_pdb_bytes"):
                 fn.restype = C.c_int
         _lib.dca_l1_kpad.restype = C.c_int64
         _lib.dca_l1_kpad8.restype = C.c_int64
@@ -110,6 +111,11 @@ def lib() -> C.CDLL:
         _lib.dca_hcache_lookup.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
         _lib.dca_hcache_finish.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.dca_pdb_bytes.restype = C.c_int64
+        _lib.dca_pdb_bytes.argtypes = [C.c_int, C.c_int]
+        _lib.dca_pdb_build.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.dca_pdb_eval.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
         _lib.dca_engine_known_duplicate.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int]
         _lib.dca_engine_destroy.restype = None
         if _lib.dca_abi_version() != 6:
@@ -392,6 +398,55 @@ class HeuristicCache:
         check(lib().dca_hcache_finish(ptr(self.table), self.row_bytes, C.c_int64(self.slots), C.c_int64(n), ptr(slot), ptr(status),
                                       ptr(h), stream_ptr()), "dca_hcache_finish")
         return h
+
+
+# ------------------------------------------------------------------------------ pattern databases (sliding puzzles)
+PDB_MAX_PATTERNS = 24
+PDB_NO_STATE, PDB_UNREACHABLE = 0xFF, 0xFE  # table bytes: two digits equal / a state the goal cannot be reached from
+
+
+def pdb_bytes(dim: int, k: int) -> int:
+    """Bytes of one pattern's table, N^(k+1) with N = dim * dim: a pure function (include/dca.h); DcaError outside its limits."""
+    b = int(lib().dca_pdb_bytes(int(dim), int(k)))
+    check(min(b, 0), "dca_pdb_bytes")
+    return b
+
+
+def pdb_build(dim: int, tiles, table: Optional[torch.Tensor] = None):
+    """Fill (or allocate and fill) the device table of the pattern `tiles` -> (table u8 [N^(k+1)], sweeps).  Synchronises."""
+    tiles = np.ascontiguousarray(list(tiles), dtype=np.uint8)
+    nbytes = pdb_bytes(dim, len(tiles))
+    if table is None:
+        table = torch.empty(nbytes, dtype=torch.uint8, device=require_gpu())
+    assert table.dtype == torch.uint8 and table.numel() == nbytes
+    sweeps = C.c_int(0)
+    check(lib().dca_pdb_build(int(dim), tiles.ctypes.data_as(C.c_void_p), int(len(tiles)), ptr(table), C.byref(sweeps), stream_ptr()),
+          "dca_pdb_build")
+    return table, int(sweeps.value)
+
+
+def pdb_eval(dim: int, states: torch.Tensor, partition, tables, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sum of the patterns' table bytes per row -> f32 [n].  states: uint8 device rows [n, >= dim * dim] with unit byte stride
+    (a strided view is fine); ANY bytes are in bounds (include/dca.h, the any-bytes rule)."""
+    if states.dtype != torch.uint8 or not states.is_cuda or states.dim() != 2:
+        raise ValueError("pdb_eval: states must be a uint8 device tensor [n, >= dim * dim]")
+    n, N = states.shape[0], dim * dim
+    if n > 0 and states.stride(1) != 1:
+        states = states.contiguous()
+    ld = states.stride(0) if n > 1 else max(states.stride(0), states.shape[1])
+    if ld < states.shape[1]:
+        states, ld = states.contiguous(), states.shape[1]
+    if states.shape[1] < N:
+        ld = states.shape[1]  # too narrow for this board: the library refuses ld < N
+    ks = np.ascontiguousarray([len(g) for g in partition], dtype=np.int32)
+    flat = np.ascontiguousarray([t for g in partition for t in g], dtype=np.uint8)
+    ptrs = (C.c_void_p * max(len(tables), 1))(*[ptr(t) for t in tables])
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=states.device)
+    assert out.dtype == torch.float32 and out.numel() >= n
+    check(lib().dca_pdb_eval(int(dim), C.c_void_p(states.data_ptr()), C.c_int64(n), C.c_int64(ld), int(len(partition)),
+                             flat.ctypes.data_as(C.c_void_p), ks.ctypes.data_as(C.c_void_p), ptrs, ptr(out), stream_ptr()), "dca_pdb_eval")
+    return out
 
 
 # ------------------------------------------------------------------------------ training step

@@ -45,13 +45,28 @@ def _nnet_rows(args):
     return None if n is None else max(int(n), _MIN_NNET_ROWS)
 
 
+def _is_pdb(args) -> bool:
+    return str(getattr(args, "model_dir", "")).startswith("pdb:")
+
+
 def _load_heuristic(args, env):
     """Device heuristic closure.  `--model_dir synthetic:SEED` builds the environment's network with
     deterministic synthetic weights (the reference checkpoints are not redistributable here)."""
+    if _is_pdb(args):
+        # no network: additive pattern databases (utils/pattern_db.py).  The spec is checked before any device work; the closure
+        # reads the packed uint8 rows of the dedup-first path (stride 0 = no one-hot rows)
+        from ..utils.pattern_db import PatternDatabase, parse_pdb_spec
+        partition = parse_pdb_spec(args.env, str(args.model_dir).split(":", 1)[1])
     device, devices, on_gpu = nnet_utils.get_device()
     print("device: %s, devices: %s, on_gpu: %s" % (device, devices, on_gpu))
     if not on_gpu:
         raise _lib.DcaError("--language hip needs an MI355X: no HIP device visible")
+    if _is_pdb(args):
+        start = time.time()
+        pdb = PatternDatabase(args.env, partition).build()
+        print("pattern database %s: %d bytes, sweeps %s, built in %.2f s"
+              % ("/".join(",".join(str(t) for t in g) for g in pdb.partition), pdb.bytes, pdb.sweeps, time.time() - start))
+        return pdb.heuristic_fn_dev(), 0
     nnet = env.get_nnet_model()
     if str(args.model_dir).startswith("synthetic:"):
         from ..utils.synthetic_weights import load_synthetic_weights
@@ -108,11 +123,12 @@ def auto_instances(args, env, n_states: int, builtin) -> int:
     chip — _AUTO_CHILDREN_BUILTIN per launch for a built-in heuristic, _MIN_NNET_ROWS per network call otherwise —
     never more than the states this rank can draw, _AUTO_MAX_INSTANCES, or what `--max_nodes` leaves room for.
     Integer-valued built-ins (manhattan, zero) make every f-level ONE cost tie of up to millions of entries, which only a
-    single-instance engine refines with its whole grid: those searches stay at K = 1."""
+    single-instance engine refines with its whole grid: those searches stay at K = 1, and so does a
+    `pdb:` model, whose values are integers too."""
     v = str(getattr(args, "instances_per_gpu", "auto")).lower()
     if v != "auto":
         return max(1, int(v))
-    if builtin in (_lib.HEUR_MANHATTAN, _lib.HEUR_ZERO):
+    if builtin in (_lib.HEUR_MANHATTAN, _lib.HEUR_ZERO) or _is_pdb(args):
         return 1
     per = max(1, int(args.batch_size) * env.get_num_moves())
     want = _AUTO_CHILDREN_BUILTIN if builtin is not None else _MIN_NNET_ROWS
@@ -217,7 +233,11 @@ def build_parser() -> ArgumentParser:
     # reference flags (astar.py:346-362)
     parser.add_argument('--states', type=str, required=True, help="File containing states to solve")
     parser.add_argument('--model_dir', type=str, required=True,
-                        help="Directory of nnet model, or synthetic:SEED, or builtin:manhattan / builtin:zero")
+                        help="Directory of nnet model, or synthetic:SEED, or builtin:manhattan / builtin:zero, or pdb:SPEC — "
+                             "additive pattern databases on the sliding puzzles, built on the GPU at start-up: SPEC is a preset "
+                             "(puzzle8 4-4; puzzle15 5-5-5, 6-6-3; puzzle24 6-6-6-6; auto = the first of these) or explicit "
+                             "groups of tiles such as 1,2,3,4/5,6,7,8.  Admissible and consistent: with --weight 1 --semantics cpp "
+                             "the solutions are optimal")
     parser.add_argument('--env', type=str, required=True, help="Environment: cube3, puzzle8, puzzle15, puzzle24, puzzle35, puzzle48, lightsout7 "
                                                                       "(puzzle8 has every layer-1 kernel puzzle15 has: no --nnet_dtype mode is on a fall-back there)")
     parser.add_argument('--batch_size', type=int, default=1, help="Batch size for BWAS")

@@ -208,6 +208,45 @@ int dca_hcache_lookup(void* table, int row_bytes, int64_t slots, const uint8_t* 
 int dca_hcache_finish(void* table, int row_bytes, int64_t slots, int64_t n, const int32_t* slot /*[n]*/,
                       const uint8_t* status /*[n]*/, float* h /*[n]*/, void* stream);
 
+/* Pattern databases for the sliding puzzles (csrc/dca_pdb.hip; `--model_dir pdb:<spec>`): additive disjoint pattern databases,
+ * the exact admissible heuristic the paper measures its network against.  For a dim x dim board (dim 3..7, N = dim * dim) a
+ * PATTERN is an ordered list of k distinct tiles from 1..N-1; its table is caller-owned device memory of dca_pdb_bytes(dim, k) =
+ * N^(k+1) bytes (a pure function; DCA_E_BADARG unless dim is 3..7, k is 1..N-1 and the result is <= 2^34).
+ *   index rule   index = blank_pos + N * (pos(tiles[0]) + N * (pos(tiles[1]) + ...)): the blank is the lowest digit, tiles[j] is
+ *                digit j + 1.
+ *   cost rule    table[index] = the smallest number of moves OF THE PATTERN'S TILES that takes the abstract state (the positions
+ *                of these tiles and of the blank, every other tile invisible) to the goal — tile t at position t - 1, the blank
+ *                at N - 1.  A blank move that swaps with a pattern tile costs 1, with an invisible tile 0.
+ *   0xFF rule    an index with two digits equal is not a state and holds 0xFF.  A state the goal cannot be reached from holds
+ *                0xFE; there are such states only where the pattern leaves at most one tile out (k >= N - 2: the visible tiles
+ *                then fix the permutation's parity).  Every distance is far below 0xFE.
+ * The blank stays in the index on purpose: the sum over DISJOINT patterns is then admissible (each move moves one tile, which
+ * belongs to at most one pattern) and consistent (a move changes one pattern's abstract state along one of its edges, by at
+ * most that edge's cost, and every other pattern's along a 0-cost edge of its own graph: |h(s) - h(s')| <= 1); the usual
+ * minimum over blank positions is smaller and can be inconsistent.  One-tile patterns give exactly the Manhattan distance.
+ * dca_pdb_build fills `table` by relaxation sweeps (one thread per entry pulls from its blank-move neighbours and writes only its
+ * own byte; the fixed point has the same bits on every run) and SYNCHRONISES the stream once per sweep to read a "changed" word;
+ * *sweeps (host, or NULL) = the sweeps it took, the last, unchanged one included.  tiles: host [k].
+ * dca_pdb_eval: out[i] = sum over the set's patterns of table_p[index_p(row i)], an integer <= 24 * 255, exact in fp32.  states:
+ * device rows [n, ld], ld >= N, any byte alignment; tiles: host, the patterns' tile lists one after another; ks: host
+ * [num_patterns]; tables: HOST array of num_patterns device pointers.  The metadata travels as kernel arguments; stream-ordered,
+ * nothing synchronises.
+ *   partition    tiles in 1..N-1; no tile twice across the whole set; at most 24 patterns; a set that leaves tiles out is
+ *                allowed (it is still admissible).
+ *   any-bytes rule  the engine hands this call rows padded up to a multiple of 1024 whose padding is stale or all zero, so it is
+ *                in bounds for ANY bytes: pos(t) of a row = the LAST position p < N with row[p] == t, 0 if there is none; bytes
+ *                >= N match no tile.  Every digit is then < N and every index < N^(k+1) by construction.  The value of a row
+ *                that is no permutation is whatever the tables hold there, 0xFF and 0xFE terms included, and is deterministic.
+ * DCA_E_BADARG before any launch, the message naming the argument: dim outside 3..7; k outside 1..N-1 or a table over 2^34
+ * bytes; a tile that is 0, >= N or named twice (build: within the pattern; eval: across the set); num_patterns outside 1..24; a
+ * NULL tiles / ks / tables / table / out (states and out may be NULL when n == 0); ld < N; n < 0 or >= 2^31. */
+int64_t dca_pdb_bytes(int dim, int k);
+int dca_pdb_build(int dim, const uint8_t* tiles /*host [k]*/, int k, uint8_t* table /*device [N^(k+1)]*/, int* sweeps /*host or NULL*/,
+                  void* stream);
+int dca_pdb_eval(int dim, const uint8_t* states /*[n, ld]*/, int64_t n, int64_t ld, int num_patterns, const uint8_t* tiles /*host*/,
+                 const int* ks /*host [num_patterns]*/, const uint8_t* const* tables /*host [num_patterns] of device pointers*/,
+                 float* out /*[n]*/, void* stream);
+
 /* state hash (a9).  The reference's hash VALUES are process-randomised SipHash (cube3.py:17-21)
  * or unpinned boost::hash_range (parallel_weighted_astar.cpp:104-111); what is pinned is key
  * equality.  This library defines, for a D-byte state split in little-endian 8-byte words
