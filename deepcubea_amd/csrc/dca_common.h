@@ -15,7 +15,7 @@ namespace dca {
 // Equals Cube3._compute_rotation_idxs (environments/cube3.py:183-256) and the literal
 // rotateIdxs tables of cpp/environments.h:75-105 (pinned: sha256 d090eb61… in the tests).
 // ------------------------------------------------------------------------------------------
-struct Cube3Perm {
+struct alignas(16) Cube3Perm {  // (16-byte aligned and padded to 656 bytes: 41 lanes stage it with one 16-byte load each)
     uint8_t p[12][54];
 };
 
@@ -128,8 +128,18 @@ __host__ __device__ inline bool known_duplicate(int env, uint32_t g_parent, uint
 
 // byte i of the goal state: cube3 arange(54) (cube3.py:62-69), puzzles 1..n^2-1,0 (n_puzzle.py:69-76), lightsout zeros
 // (lights_out.py:55-63)
-__host__ __device__ inline uint32_t goal_byte(int env, int D, int i) {
+constexpr __host__ __device__ inline uint32_t goal_byte(int env, int D, int i) {
     return (env == DCA_ENV_CUBE3 || env == DCA_ENV_CUBE4) ? (uint32_t)i : env == DCA_ENV_NPUZZLE ? (uint32_t)((i + 1) % D) : 0u;
+}
+// the goal's bytes 8k .. 8k+7 as one little-endian word, bytes past the row 0 — and the mask of the bytes that belong to the
+// row: is_solved of a row held as 8-byte words (rows of at most 64 bytes: the cubes' 4x4x4 sibling compares faces, not bytes)
+constexpr __host__ __device__ inline uint64_t goal_word(int env, int D, int k) {
+    uint64_t w = 0;
+    for (int j = 0; j < 8 && 8 * k + j < D; j++) w |= (uint64_t)goal_byte(env, D, 8 * k + j) << (8 * j);
+    return w;
+}
+constexpr __host__ __device__ inline uint64_t row_word_mask(int D, int k) {
+    return D - 8 * k >= 8 ? ~0ull : (1ull << (8 * (D - 8 * k))) - 1ull;
 }
 // is_solved, one byte at a time: `ok` after byte i (value b) of a state given `ok` before it.  cube3 / puzzles / lightsout:
 // equality with the goal byte (cube3.py:71-75, cpp:119-126,249-256).  cube4: every face shows ONE colour (sticker / 16 equal
@@ -172,6 +182,13 @@ __host__ __device__ inline uint32_t manhattan_term(int dim, uint32_t pos, uint32
     int g = (int)t - 1;
     int dr = (int)(pos / dim) - g / dim, dc = (int)(pos % dim) - g % dim;
     return (uint32_t)((dr < 0 ? -dr : dr) + (dc < 0 ? -dc : dc));
+}
+
+// the weights 7 i + 3 of the built-in heuristics' byte sum for bytes i0 .. i0 + 3, one byte each: bits shift .. shift + 7
+constexpr __host__ __device__ inline uint32_t sum_weights(int i0, int shift) {
+    uint32_t v = 0;
+    for (int b = 0; b < 4; b++) v |= (((uint32_t)(7 * (i0 + b) + 3) >> shift) & 0xFFu) << (8 * b);
+    return v;
 }
 
 // built-in heuristics (include/dca.h DCA_HEUR_*); `sum` = sum_i s_i*(7i+3), `h` = state hash, `manh` = Manhattan distance

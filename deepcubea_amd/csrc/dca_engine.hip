@@ -2580,6 +2580,21 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
     constexpr int kTileParents = kEngTile;  // shadows the stand-alone kernels' 64 (32 / 64 parents per workgroup measured SLOWER
                                             // also for the launches that write one-hot rows: profiles/r06_engine_ab.txt)
     constexpr int TP = kEngTile;
+    // cube3's move table depends on nothing: every lane asks for one 16-byte piece of it (41 pieces; the lanes past them
+    // re-read the last one) before the kernel waits for anything else, and lanes 0-40 store theirs to LDS after the parent
+    // gather's wait.  Inline asm because the compiler would sink the load behind the control-block reads, to its use; it is
+    // the wave's oldest load, so any later compiler-counted wait for a younger load implies that it has landed — the first
+    // such wait is the `done` test's own (one load in flight by the compiler's count: vmcnt(0)), on every path, the early
+    // exits included, so the registers are never written after the compiler has given them to something else.
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    constexpr int kPermChunks = (int)sizeof(Cube3Perm) / 16;
+    u32x4 permv;
+    if constexpr (ENV == DCA_ENV_CUBE3) {
+        static_assert(sizeof(Cube3Perm) % 16 == 0 && alignof(Cube3Perm) == 16 && TL::TAB_BYTES == (int)sizeof(Cube3Perm),
+                      "cube3's move table is staged in 16-byte pieces");
+        const u32x4* pp = reinterpret_cast<const u32x4*>(&d_cube3_perm) + min(threadIdx.x, (uint32_t)kPermChunks - 1u);
+        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(permv) : "v"(pp) : "memory");
+    }
     gp<Ctl> c = E.ctl;
     if (c->done) return;
     Stamp stamp(E, P_EXPAND);
@@ -2590,12 +2605,12 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
     __shared__ uint32_t l_pid[TP], l_g[TP], l_mv[TP];
     __shared__ uint32_t l_qn, l_qcc[kThreads], l_qrep[kThreads], l_qres[kThreads];
     __shared__ uint32_t l_ohq;  // one-hot rows: next 1 KiB piece (one wave-wide 16-byte store) nobody has claimed yet
-    static_assert((EV::D + 3) / 4 < 16, "no spare lane per row for the parent's path cost");
     // batch geometry: every workgroup derives it from the state the previous iteration left (S[iters & 1]) and the
     // pop that k_rank just finished; workgroup 0 also records it for the rest of the iteration (close_pop)
     const uint32_t it = (uint32_t)c->iters;
     const IterState S0 = c->S[it & 1];
     const uint32_t want = c->want;
+    const uint32_t cur_new = c->cur_f;  // FRONT is edited in place: put-backs and children are appended to it
     uint32_t npop = want;
     if (E.sem == DCA_SEM_CPP) {
         const uint32_t fs = c->first_solved;
@@ -2603,7 +2618,6 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
     }
     const uint32_t base = (S0.pool_n + 15u) & ~15u;  // 16-aligned ids => 16-byte aligned child rows for every D
     const bool fail = (uint64_t)base + (uint64_t)npop * (uint64_t)EV::A > (uint64_t)E.max_nodes;
-    const uint32_t cur_new = c->cur_f;  // FRONT is edited in place: put-backs and children are appended to it
     if (blockIdx.x == 0 && threadIdx.x == 0) close_pop(E, c, S0, it, want, npop, base, fail);
     if (fail) return;
     const uint32_t r0 = blockIdx.x * kTileParents;
@@ -2618,38 +2632,56 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
     const uint32_t np = min((uint32_t)kTileParents, npop - r0);
     if (OH != 0 && threadIdx.x == 0) l_ohq = 0;
     {
-        // gather the popped rows by node id.  One lane per (parent, 4-byte word): 16 lanes cover a row, so
-        // a 256-thread block fetches 16 rows per round and the 4 rounds are issued back to back.
+        // gather the popped parents by node id: ONE dependent level behind the id.  The 16 lanes of a row group all load the
+        // parent's id (clamped index: no branch), then every lane issues the same dword load with its own address — lanes
+        // w < WPR a word of the row (the tail word of a row whose length is no multiple of 4 as the dword that ends at the row's
+        // last byte, shifted into place: gather_word, dca_tile.h), lane WPR the parent's path cost — and the same byte load of
+        // the move that made the parent (what tells the children that need no CLOSED probe): one wait for all of it.  The
+        // per-child loop below used to wait for the path cost — a dependent random access — before it could write anything.
         constexpr int WPR = (EV::D + 3) / 4;  // words per row (<= 14)
-        static_assert(WPR <= 16, "row wider than 64 bytes");
-        const uint32_t w = threadIdx.x & 15;  // 16 lanes per row, 16 rows per round
-        // (a spare lane of every row fetches the parent's path cost in the same round trip as the row itself: the
-        // per-child loop below used to wait for it — a dependent random access — before it could write anything; and the
-        // move that made the parent, same dependent level: what tells the children that need no CLOSED probe)
+        static_assert(WPR + 2 <= 16, "16 lanes per parent: the row's words, its path cost, its move");
+        static_assert(TP * 16 == kThreads, "one 16-lane group per parent of the tile");
+        const uint32_t w = threadIdx.x & 15, r = threadIdx.x >> 4;
+        // (the empty asm statements pin what the compiler otherwise undoes: it reads each array's base inside the branch that
+        // uses it and sinks the move's load into the one lane's branch that stores it, every one of them a level of its own)
+        gp<const uint32_t> ppop = E.pop_id;
+        gp<const uint8_t> pst = E.state, pg = reinterpret_cast<gp<const uint8_t>>(E.g), pmv = E.move;
+        asm volatile("" : "+s"(ppop), "+s"(pst), "+s"(pg), "+s"(pmv));
+        const uint32_t pid = ppop[r0 + min(r, np - 1u)] & ID_MASK;
+        const GatherWord gw = gather_word(EV::D, (int)w);
+        const bool row_lane = w < (uint32_t)WPR;
+        gp<const uint8_t> src = (row_lane ? pst : pg) + (row_lane ? (size_t)pid * EV::D + (uint32_t)gw.off : (size_t)pid * 4);
+        uint32_t v = load_word(src);
+        uint32_t mv = pmv[pid];
+        asm volatile("" : "+v"(v), "+v"(mv));  // the one wait: row word / path cost and move together
+        if (r < np) {
+            if (w < (uint32_t)WPR) {
+                v >>= gw.shift;
+                uint8_t* dst = lpar + r * EV::D + 4 * w;
+                if constexpr (EV::D % 4 == 0) {
+                    *reinterpret_cast<uint32_t*>(dst) = v;
+                } else if constexpr (EV::D % 2 == 0) {
+                    *reinterpret_cast<uint16_t*>(dst) = (uint16_t)v;
+                    if (gw.n == 4) *reinterpret_cast<uint16_t*>(dst + 2) = (uint16_t)(v >> 16);
+                } else {
 #pragma unroll
-        for (uint32_t r = threadIdx.x >> 4; r < (uint32_t)TP; r += 16) {
-        if (r < np && w == WPR) {
-            const uint32_t pid = E.pop_id[r0 + r] & ID_MASK;
-            l_pid[r] = pid;
-            l_g[r] = (uint32_t)E.g[pid];
-            l_mv[r] = (uint32_t)E.move[pid];
-        }
-        if (r < np && w < WPR) {
-            gp<const uint8_t> row = E.state + (size_t)(E.pop_id[r0 + r] & ID_MASK) * EV::D;
-            uint32_t v = 0;
-            // rows start at id*D: read byte-wise only where a word would cross the row end
-            if (4 * w + 4 <= EV::D) {
-                v = load_word(row + 4 * w);
-            } else {
-                for (int b = 0; 4 * w + b < EV::D; b++) v |= (uint32_t)row[4 * w + b] << (8 * b);
+                    for (int b = 0; b < 4; b++)
+                        if (b < gw.n) dst[b] = (uint8_t)(v >> (8 * b));
+                }
+            } else if (w == (uint32_t)WPR) {
+                l_pid[r] = pid;
+                l_g[r] = v;
+            } else if (w == (uint32_t)WPR + 1u) {
+                l_mv[r] = mv;
             }
-#pragma unroll
-            for (int b = 0; b < 4; b++)
-                if (4 * w + b < EV::D) lpar[r * EV::D + 4 * w + b] = (uint8_t)(v >> (8 * b));
-        }
         }
     }
-    if constexpr (ENV == DCA_ENV_CUBE3) stage_tables<ENV, DIM>(ltab, lpar, np);
+    if constexpr (ENV == DCA_ENV_CUBE3) {
+        // (the table was requested at the top of the kernel, the wave's oldest load: the wait the stores above needed covers
+        // it — said again here, at no cost, for a wave whose rows all lie past the tile's end and which skipped those stores)
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(permv) : : "memory");
+        if (threadIdx.x < (uint32_t)kPermChunks) reinterpret_cast<u32x4*>(ltab)[threadIdx.x] = permv;
+    }
     __syncthreads();
     if constexpr (ENV != DCA_ENV_CUBE3) {
         stage_tables<ENV, DIM>(ltab, lpar, np);
@@ -2756,9 +2788,16 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
         bool known = false;  // a duplicate by its parent's node fields alone (known_duplicate, dca_common.h): never probed
         if (cvalid) {
         uint32_t r = cc / EV::A, a = cc - r * EV::A;
-        uint64_t sum = 0;
+        // sum_i s_i * (7 i + 3) in 32 bits: the whole sum is at most D * 255 * (7 (D - 1) + 3) < 2^32 for every row length
+        // (D = 54: 5 150 070); widened where heur_from takes it.  Four bytes per instruction, from the assembled words: a 4 x u8
+        // dot product against the low bytes of the four weights, and — where a weight passes 255 (i >= 37) — another against
+        // their high bytes, added in 256 times over at the end.
+        static_assert((uint64_t)EV::D * 255u * (7u * (EV::D - 1) + 3u) < (1ull << 32), "the heuristics' byte sum overflows 32 bits");
+        static_assert(7 * (EV::D - 1) + 3 < 65536, "the heuristics' weights are two bytes");
+        uint32_t sum = 0, sum_hi = 0;
         h = hash_init(EV::D);
         uint32_t manh = 0;
+        // is_solved (cube3.py:71-75, cpp:119-126,249-256): the row's 8-byte words against the goal's, the last one masked to the row
         bool ok = true;
 #pragma unroll
         for (int k = 0; k < EV::D; k += 8) {
@@ -2767,15 +2806,21 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
             for (int j = 0; j < 8; j++) {
                 if (k + j < EV::D) {
                     uint32_t b = t.child_byte(r, a, k + j);
-                    uint32_t goal = goal_byte(ENV, EV::D, k + j);
-                    ok &= (b == goal);
                     w |= (uint64_t)b << (8 * j);
-                    sum += (uint64_t)b * (uint64_t)(7 * (k + j) + 3);
                     if constexpr (ENV == DCA_ENV_NPUZZLE) manh += manhattan_term(DIM, (uint32_t)(k + j), b);
                 }
             }
             h = hash_word(h, w);
             roww[k >> 3] = w;
+            ok &= (w & row_word_mask(EV::D, k >> 3)) == goal_word(ENV, EV::D, k >> 3);
+#pragma unroll
+            for (int q = 0; q < 8; q += 4) {
+                if (k + q < EV::D) {
+                    const uint32_t x = (uint32_t)(w >> (8 * q));  // (bytes past the row are 0)
+                    sum = __builtin_amdgcn_udot4(x, sum_weights(k + q, 0), sum, false);
+                    if (sum_weights(k + q, 8) != 0u) sum_hi = __builtin_amdgcn_udot4(x, sum_weights(k + q, 8), sum_hi, false);
+                }
+            }
             // stage the gathered bytes (rows start on even offsets when D is even: 2-byte stores; else bytes)
             uint8_t* dst = lst + cc * EV::D + k;
 #pragma unroll
@@ -2801,7 +2846,7 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
         E.parent[id] = pid;
         E.move[id] = (uint8_t)a;
         E.solved[id] = ok ? 1 : 0;
-        if (heur_id >= 0) E.child_h[j] = heur_from(heur_id, sum, h, manh);
+        if (heur_id >= 0) E.child_h[j] = heur_from(heur_id, (uint64_t)(sum + (sum_hi << 8)), h, manh);
         }
         {
             // ---- find-or-insert the CLOSED slot of this round's children (rows taken from LDS)
@@ -2822,7 +2867,10 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
                         // for a new state — was measured and lost badly: 61 us vs 26 us for the probe of a batch; returning
                         // atomics are that much dearer here).  ONE 16-byte load fetches the slot's entry together with its value: entries never
                         // change once written and values only change in k_commit, so a line cached by an earlier reader on
-                        // this CU is either current or shows an EMPTY entry that the compare-and-swap then corrects.
+                        // this CU is either current or shows an EMPTY entry that the compare-and-swap then corrects.  (For the same
+                        // reason an EARLIER look at the home slot would be as good as this one.  Requesting it right after the hash,
+                        // under the staging stores, the node-field stores and the barrier, was built and measured: 0.8 / 1.3 us per
+                        // iteration SLOWER — profiles/expand_gather_ab.txt — and taken out.)
                         const uint4 sl = *reinterpret_cast<const uint4*>(&E.tab[slot]);
                         uint64_t e = ((uint64_t)sl.y << 32) | sl.x;
                         v0 = sl.z;  // the slot's value before this batch (GINF while nothing was recorded)

@@ -29,6 +29,40 @@ struct EnvT<DCA_ENV_LIGHTSOUT, DIM> {
     static constexpr int D = DIM * DIM, A = DIM * DIM, DEPTH = 6;  // (ResnetModel(num_tiles, 6, ...), lights_out.py:80)
 };
 
+// The engine's parent gather: the 16 lanes of a row group fetch a D-byte row with ONE dword load each (lane w < (D + 3) / 4;
+// the next lane takes the parent's path cost, one more its move).  Lane w holds row bytes 4w .. 4w + n - 1 in the low n bytes of
+// (loaded dword >> shift): a full word is loaded where it lies; the tail word of a row whose length is no multiple of 4 is the
+// dword that ENDS at the row's last byte (off = D - 4), shifted down — no load touches a byte outside [row, row + D).
+struct GatherWord {
+    int off, shift, n;  // byte offset of the loaded dword within the row, right shift, row bytes the lane ends up with
+};
+constexpr __host__ __device__ inline GatherWord gather_word(int D, int w) {
+    if (4 * w >= D) return GatherWord{0, 0, 0};
+    if (4 * w + 4 <= D) return GatherWord{4 * w, 0, 4};
+    return GatherWord{D - 4, 8 * (4 * w + 4 - D), D - 4 * w};
+}
+// every row byte lands in exactly one lane, at its place, and no dword leaves the row
+constexpr bool gather_covers(int D) {
+    if (D < 4 || (D + 3) / 4 + 2 > 16) return false;  // 16 lanes: the row's words, the path cost, the move
+    int seen[64] = {};
+    for (int w = 0; w < 16; w++) {
+        const GatherWord g = gather_word(D, w);
+        if (g.n == 0) continue;
+        if (g.off < 0 || g.off + 4 > D || g.shift != 8 * (4 - g.n)) return false;
+        for (int b = 0; b < g.n; b++) {
+            const int src = g.off + g.shift / 8 + b;  // the row byte that ends up as byte b of lane w's word
+            if (src != 4 * w + b || src >= D) return false;
+            seen[src]++;
+        }
+    }
+    for (int i = 0; i < D; i++)
+        if (seen[i] != 1) return false;
+    return true;
+}
+static_assert(gather_covers(9) && gather_covers(16) && gather_covers(25) && gather_covers(36) && gather_covers(49) &&
+                  gather_covers(54),
+              "parent gather: the lanes' dwords must cover each row byte exactly once and none outside the row");
+
 // LDS view of one parent tile + its move tables
 template <int ENV, int DIM, int TP = kTileParents>
 struct Tile {
