@@ -24,36 +24,123 @@ HEUR_MOD97, HEUR_KNUTH3, HEUR_HASHU01, HEUR_ZERO, HEUR_MANHATTAN = 0, 1, 2, 3, 4
 
 _TORCH_DT = {torch.float32: DT_F32, torch.float16: DT_F16, torch.bfloat16: DT_BF16}
 
-# every symbol include/dca.h (the product ABI) and include/dca_debug.h (test / tuning / profiling hooks) declare
-# (tests check the library exports all of them)
-ABI_SYMBOLS = [
-    "dca_abi_version", "dca_last_error", "dca_cube3_perm_table", "dca_npuzzle_swap_table",
-    "dca_cube3_next_state", "dca_cube3_prev_state", "dca_npuzzle_next_state", "dca_npuzzle_prev_state",
-    "dca_cube3_expand_fused", "dca_npuzzle_expand_fused", "dca_is_solved", "dca_hash64", "dca_nnet_input",
-    "dca_onehot", "dca_heuristic_builtin", "dca_generate_states", "dca_bellman_backup",
-    "dca_engine_create", "dca_engine_create_multi", "dca_engine_num_instances", "dca_engine_destroy",
-    "dca_engine_reset", "dca_engine_reset_instance", "dca_engine_root_commit", "dca_engine_root_commit_instance",
-    "dca_engine_root_nnet_in", "dca_engine_root_nnet_in_instance", "dca_engine_status_instance",
-    "dca_engine_solution_instance", "dca_engine_pop_expand", "dca_engine_commit", "dca_engine_run_builtin",
-    "dca_engine_enable_packed", "dca_engine_pop_expand_packed", "dca_engine_commit_packed",
-    "dca_engine_profile_builtin", "dca_engine_set_tiers", "dca_engine_debug", "dca_debug_tune", "dca_engine_status", "dca_engine_last_children", "dca_engine_solution",
-    "dca_bn_workspace_bytes", "dca_bn_train_forward", "dca_bn_train_backward",
-    "dca_l1_supported", "dca_l1_kpad", "dca_l1_onehot_gemm", "dca_act_split", "dca_f16x3_gemm", "dca_split_planes", "dca_f16x3_gemm_variant",
-    "dca_absmax_bits", "dca_split_planes_scaled", "dca_split_rows_scaled", "dca_fill_inv_pow2", "dca_engine_plan_chunk",
-    "dca_gemm16", "dca_gemm16_variant", "dca_gemm8", "dca_quant_e4m3", "dca_lightsout_next_state", "dca_lightsout_expand_fused",
-    "dca_head_gemv", "dca_engine_packed_state", "dca_engine_info", "dca_gemm8_mx", "dca_l1_onehot_gemm_mx",
-    "dca_cube4_perm_table", "dca_cube4_next_state", "dca_cube4_prev_state", "dca_cube4_expand_fused",
-    "dca_engine_set_weight_instance", "dca_engine_set_weights", "dca_engine_park_instance", "dca_engine_last_popped",
-    "dca_engine_reset_many", "dca_engine_root_commit_many", "dca_engine_set_weights_dev", "dca_debug_write_ceiling",
-    "dca_l1_supported8", "dca_l1_kpad8", "dca_l1_onehot_gemm8", "dca_l1_embed_supported", "dca_l1_embed",
-    "dca_gemm64", "dca_l1_embed64", "dca_head_gemv64",
-    "dca_l1_embed_wgrad_slice_rows", "dca_l1_embed_wgrad_workspace_bytes", "dca_l1_embed_wgrad",
-    "dca_wgrad_f16", "dca_wgrad_splits", "dca_wgrad_workspace_bytes",
-    "dca_f16_gemm", "dca_cast_planes_scaled", "dca_cast_rows_scaled",
-    "dca_hcache_bytes", "dca_hcache_clear", "dca_hcache_lookup", "dca_hcache_finish",
-    "dca_engine_known_duplicate",
-    "dca_pdb_bytes", "dca_pdb_build", "dca_pdb_eval",
-]
+# Every entry point the two headers declare, in their order: name -> "return parameters", one letter per C type.  This table is
+# the one place that knows how wide a C parameter is: lib() turns it into restype / argtypes, so callers pass plain Python values
+# and a wrong width or argument count raises ctypes.ArgumentError / TypeError (tests check it against the headers).
+#   parameters  p any pointer (c_void_p: None, an int, byref(...), a ctypes array)   i int   l int64_t   u uint64_t   d double
+#   returns     i int   l int64_t   v void   s const char*   b const uint8_t* (a host table)
+_CTYPE = {"p": C.c_void_p, "i": C.c_int, "l": C.c_int64, "u": C.c_uint64, "d": C.c_double,
+          "v": None, "s": C.c_char_p, "b": C.POINTER(C.c_uint8)}
+_SIGNATURES = {
+    # include/dca.h: the product ABI
+    "dca_abi_version": "i",
+    "dca_last_error": "s",
+    "dca_cube3_perm_table": "b",
+    "dca_npuzzle_swap_table": "i ip",
+    "dca_cube3_next_state": "i plipp",
+    "dca_cube3_prev_state": "i plipp",
+    "dca_npuzzle_next_state": "i pliipp",
+    "dca_npuzzle_prev_state": "i pliipp",
+    "dca_lightsout_next_state": "i pliipp",
+    "dca_cube3_expand_fused": "i plpppippp",
+    "dca_npuzzle_expand_fused": "i plippippp",
+    "dca_lightsout_expand_fused": "i plippippp",
+    "dca_cube4_perm_table": "b",
+    "dca_cube4_next_state": "i plipp",
+    "dca_cube4_prev_state": "i plipp",
+    "dca_cube4_expand_fused": "i plpppp",
+    "dca_is_solved": "i iiplpp",
+    "dca_hash64": "i plipp",
+    "dca_nnet_input": "i iiplpp",
+    "dca_onehot": "i pliipip",
+    "dca_heuristic_builtin": "i iplipp",
+    "dca_generate_states": "i iiliiulpppip",
+    "dca_bellman_backup": "i ppliippp",
+    "dca_hcache_bytes": "l il",
+    "dca_hcache_clear": "i pilp",
+    "dca_hcache_lookup": "i pilpllpppp",
+    "dca_hcache_finish": "i pillpppp",
+    "dca_pdb_bytes": "l ii",
+    "dca_pdb_build": "i ipippp",
+    "dca_pdb_eval": "i ipllippppp",
+    "dca_engine_create": "i piidilii",
+    "dca_engine_create_multi": "i piidiliii",
+    "dca_engine_num_instances": "i p",
+    "dca_engine_destroy": "v p",
+    "dca_engine_reset": "i ppp",
+    "dca_engine_reset_instance": "i pipp",
+    "dca_engine_root_commit": "i ppp",
+    "dca_engine_root_commit_instance": "i pipp",
+    "dca_engine_root_nnet_in": "i pp",
+    "dca_engine_root_nnet_in_instance": "i pip",
+    "dca_engine_pop_expand": "i ppppp",
+    "dca_engine_commit": "i ppp",
+    "dca_engine_enable_packed": "i pil",
+    "dca_engine_pop_expand_packed": "i pppppp",
+    "dca_engine_commit_packed": "i ppp",
+    "dca_engine_packed_state": "i ppp",
+    "dca_engine_run_builtin": "i piiip",
+    "dca_engine_status": "i ppp",
+    "dca_engine_status_instance": "i pipp",
+    "dca_engine_set_weight_instance": "i pid",
+    "dca_engine_set_weights": "i ppi",
+    "dca_engine_park_instance": "i pip",
+    "dca_engine_last_popped": "i pppp",
+    "dca_engine_reset_many": "i ppip",
+    "dca_engine_root_commit_many": "i ppip",
+    "dca_engine_set_weights_dev": "i ppip",
+    "dca_engine_info": "i ppp",
+    "dca_engine_last_children": "i pppp",
+    "dca_engine_solution": "i ppippp",
+    "dca_engine_solution_instance": "i pipippp",
+    "dca_bn_workspace_bytes": "l l",
+    "dca_bn_train_forward": "i pppplldippppplp",
+    "dca_bn_train_backward": "i ppppppllippppplp",
+    "dca_l1_supported": "i ii",
+    "dca_l1_kpad": "l ii",
+    "dca_l1_onehot_gemm": "i pliipilpipipp",
+    "dca_l1_supported8": "i ii",
+    "dca_l1_kpad8": "l ii",
+    "dca_l1_onehot_gemm8": "i pliiplppipp",
+    "dca_l1_embed_supported": "i ii",
+    "dca_l1_embed": "i pliiplpipipp",
+    "dca_l1_embed_wgrad_slice_rows": "l ii",
+    "dca_l1_embed_wgrad_workspace_bytes": "l liil",
+    "dca_l1_embed_wgrad": "i pliipllplpplp",
+    "dca_act_split": "i ppppdillpppp",
+    "dca_f16x3_gemm": "i pplilppilpdppippplpp",
+    "dca_gemm16": "i plilpilippiplp",
+    "dca_gemm8": "i plilpilpppiplpldp",
+    "dca_gemm8_mx": "i pplillpilpppiplplplp",
+    "dca_l1_onehot_gemm_mx": "i pliiplpipplp",
+    "dca_quant_e4m3": "i pillldplp",
+    "dca_split_planes": "i plllpplpp",
+    "dca_absmax_bits": "i plllpp",
+    "dca_split_planes_scaled": "i plllpppllp",
+    "dca_split_rows_scaled": "i plllppllppp",
+    "dca_fill_inv_pow2": "i plpp",
+    "dca_f16_gemm": "i plilpilpdpplp",
+    "dca_cast_planes_scaled": "i plllppllp",
+    "dca_cast_rows_scaled": "i plllpllppp",
+    "dca_wgrad_splits": "i lii",
+    "dca_wgrad_workspace_bytes": "l lii",
+    "dca_wgrad_f16": "i pplpplliippiplplp",
+    "dca_head_gemv": "i pililppipp",
+    "dca_head_gemv64": "i plilppipp",
+    "dca_gemm64": "i plilpilppiplp",
+    "dca_l1_embed64": "i pliiplpipp",
+    # include/dca_debug.h: test / tuning / profiling hooks
+    "dca_engine_plan_chunk": "i lipp",
+    "dca_engine_known_duplicate": "i iiliii",
+    "dca_engine_profile_builtin": "i piiippp",
+    "dca_engine_set_tiers": "i pll",
+    "dca_engine_debug": "i ppp",
+    "dca_debug_tune": "i ii",
+    "dca_debug_write_ceiling": "i pllp",
+    "dca_f16x3_gemm_variant": "i i",
+    "dca_gemm16_variant": "i i",
+}
+ABI_SYMBOLS = list(_SIGNATURES)
 
 
 class DcaError(RuntimeError):
@@ -77,47 +164,10 @@ def lib() -> C.CDLL:
             raise DcaError("HIP extension missing: %s — build it with `make -C deepcubea_amd/csrc` "
                            "(or __graft_entry__.build()); there is no CPU fallback" % LIB_PATH)
         _lib = C.CDLL(LIB_PATH)
-        _lib.dca_last_error.restype = C.c_char_p
-        _lib.dca_cube3_perm_table.restype = C.POINTER(C.c_uint8)
-        _lib.dca_cube4_perm_table.restype = C.POINTER(C.c_uint8)
-        for name in ABI_SYMBOLS:
+        for name, sig in _SIGNATURES.items():
             fn = getattr(_lib, name)  # AttributeError here = stale build of libdca_hip.so
-            if name not in ("dca_last_error", "dca_cube3_perm_table", "dca_cube4_perm_table", "dca_engine_destroy", "dca_bn_workspace_bytes",
-                            "dca_l1_kpad", "dca_l1_kpad8", "dca_l1_embed_wgrad_slice_rows", "dca_l1_embed_wgrad_workspace_bytes",
-                            "dca_wgrad_workspace_bytes", "dca_hcache_bytes", "dca_pdb_bytes"):
-                fn.restype = C.c_int
-        _lib.dca_l1_kpad.restype = C.c_int64
-        _lib.dca_l1_kpad8.restype = C.c_int64
-        _lib.dca_bn_workspace_bytes.restype = C.c_int64
-        _lib.dca_l1_embed_wgrad_slice_rows.restype = C.c_int64
-        _lib.dca_l1_embed_wgrad_slice_rows.argtypes = [C.c_int, C.c_int]
-        _lib.dca_l1_embed_wgrad_workspace_bytes.restype = C.c_int64
-        _lib.dca_l1_embed_wgrad_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int64]
-        _lib.dca_bn_workspace_bytes.argtypes = [C.c_int64]
-        _lib.dca_wgrad_splits.argtypes = [C.c_int64, C.c_int, C.c_int]
-        _lib.dca_wgrad_workspace_bytes.restype = C.c_int64
-        _lib.dca_wgrad_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
-        _lib.dca_wgrad_f16.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
-                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-        _lib.dca_f16_gemm.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_double,
-                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        _lib.dca_cast_planes_scaled.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
-                                                C.c_void_p]
-        _lib.dca_cast_rows_scaled.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
-                                              C.c_void_p, C.c_void_p]
-        _lib.dca_hcache_bytes.restype = C.c_int64
-        _lib.dca_hcache_bytes.argtypes = [C.c_int, C.c_int64]
-        _lib.dca_hcache_clear.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
-        _lib.dca_hcache_lookup.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p]
-        _lib.dca_hcache_finish.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.dca_pdb_bytes.restype = C.c_int64
-        _lib.dca_pdb_bytes.argtypes = [C.c_int, C.c_int]
-        _lib.dca_pdb_build.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.dca_pdb_eval.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p]
-        _lib.dca_engine_known_duplicate.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int]
-        _lib.dca_engine_destroy.restype = None
+            ret, _, params = sig.partition(" ")
+            fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[c] for c in params]
         if _lib.dca_abi_version() != 6:
             raise DcaError("libdca_hip.so ABI version mismatch")
     return _lib
@@ -134,15 +184,20 @@ def require_gpu() -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def stream_ptr() -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def stream_ptr() -> int:
+    return torch.cuda.current_stream().cuda_stream
 
 
-def ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
-    if t is None:
-        return C.c_void_p(0)
-    assert t.is_cuda and t.is_contiguous(), "device-resident contiguous tensor required"
-    return C.c_void_p(t.data_ptr())
+def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    """Device address of a contiguous tensor, as the plain integer a pointer parameter takes; None -> NULL."""
+    assert t is None or (t.is_cuda and t.is_contiguous()), "device-resident contiguous tensor required"
+    return None if t is None else t.data_ptr()
+
+
+def _raw(t: Optional[torch.Tensor]) -> Optional[int]:
+    """Device address of a tensor that the callee walks with an explicit row stride (views welcome); None -> NULL."""
+    assert t is None or t.is_cuda
+    return None if t is None else t.data_ptr()
 
 
 def env_ids(env_name: str):
@@ -193,7 +248,7 @@ def npuzzle_swap_table(dim: int) -> np.ndarray:
 
 def engine_known_duplicate(env: int, dim: int, g_parent: int, move_parent: int, action: int, blank: int = 0) -> bool:
     """Does the engine's expansion skip the CLOSED probe for this child (include/dca_debug.h)?  Host only."""
-    rc = lib().dca_engine_known_duplicate(int(env), int(dim), int(g_parent), int(move_parent), int(action), int(blank))
+    rc = lib().dca_engine_known_duplicate(env, dim, g_parent, move_parent, action, blank)
     check(min(rc, 0), "dca_engine_known_duplicate")
     return rc == 1
 
@@ -211,16 +266,15 @@ def next_state(env: int, dim: int, states: torch.Tensor, action: int, prev: bool
     L = lib()
     if env == ENV_CUBE3:
         fn = L.dca_cube3_prev_state if prev else L.dca_cube3_next_state
-        check(fn(ptr(states), C.c_int64(n), int(action), ptr(out), stream_ptr()), "dca_cube3_next_state")
+        check(fn(ptr(states), n, action, ptr(out), stream_ptr()), "dca_cube3_next_state")
     elif env == ENV_CUBE4:
         fn = L.dca_cube4_prev_state if prev else L.dca_cube4_next_state
-        check(fn(ptr(states), C.c_int64(n), int(action), ptr(out), stream_ptr()), "dca_cube4_next_state")
+        check(fn(ptr(states), n, action, ptr(out), stream_ptr()), "dca_cube4_next_state")
     elif env == ENV_LIGHTSOUT:  # every move is its own inverse (lights_out.py:52-53)
-        check(L.dca_lightsout_next_state(ptr(states), C.c_int64(n), dim, int(action), ptr(out), stream_ptr()),
-              "dca_lightsout_next_state")
+        check(L.dca_lightsout_next_state(ptr(states), n, dim, action, ptr(out), stream_ptr()), "dca_lightsout_next_state")
     else:
         fn = L.dca_npuzzle_prev_state if prev else L.dca_npuzzle_next_state
-        check(fn(ptr(states), C.c_int64(n), dim, int(action), ptr(out), stream_ptr()), "dca_npuzzle_next_state")
+        check(fn(ptr(states), n, dim, action, ptr(out), stream_ptr()), "dca_npuzzle_next_state")
     return out
 
 
@@ -249,16 +303,15 @@ def expand_fused(env: int, dim: int, parents: torch.Tensor, *, children: bool = 
     L = lib()
     if env == ENV_CUBE4:
         assert oh is None and not nnet_in, "cube4 has no network input in the reference (environment kernels only)"
-        check(L.dca_cube4_expand_fused(ptr(parents), C.c_int64(n), ptr(out.get("children")), ptr(out.get("solved")),
-                                       ptr(out.get("hash")), stream_ptr()), "dca_cube4_expand_fused")
+        check(L.dca_cube4_expand_fused(ptr(parents), n, ptr(out.get("children")), ptr(out.get("solved")), ptr(out.get("hash")),
+                                       stream_ptr()), "dca_cube4_expand_fused")
     elif env == ENV_CUBE3:
-        check(L.dca_cube3_expand_fused(ptr(parents), C.c_int64(n), ptr(out.get("children")), ptr(out.get("nnet_in")),
-                                       ptr(oh), ohdt, ptr(out.get("solved")), ptr(out.get("hash")), stream_ptr()),
-              "dca_cube3_expand_fused")
+        check(L.dca_cube3_expand_fused(ptr(parents), n, ptr(out.get("children")), ptr(out.get("nnet_in")), ptr(oh), ohdt,
+                                       ptr(out.get("solved")), ptr(out.get("hash")), stream_ptr()), "dca_cube3_expand_fused")
     else:
         fn = L.dca_lightsout_expand_fused if env == ENV_LIGHTSOUT else L.dca_npuzzle_expand_fused
-        check(fn(ptr(parents), C.c_int64(n), dim, ptr(out.get("children")), ptr(oh), ohdt,
-                 ptr(out.get("solved")), ptr(out.get("hash")), stream_ptr()), "dca_npuzzle/lightsout_expand_fused")
+        check(fn(ptr(parents), n, dim, ptr(out.get("children")), ptr(oh), ohdt, ptr(out.get("solved")), ptr(out.get("hash")),
+                 stream_ptr()), "dca_npuzzle/lightsout_expand_fused")
         if nnet_in and out.get("children") is not None:
             out["nnet_in"] = out["children"].view(n * A, D)  # n_puzzle.py:84-89: the tiles themselves
     return out
@@ -267,24 +320,21 @@ def expand_fused(env: int, dim: int, parents: torch.Tensor, *, children: bool = 
 def is_solved(env: int, dim: int, states: torch.Tensor) -> torch.Tensor:
     states = _u8(states)
     out = torch.empty((states.shape[0],), dtype=torch.uint8, device=states.device)
-    check(lib().dca_is_solved(env, dim, ptr(states), C.c_int64(states.shape[0]), ptr(out), stream_ptr()),
-          "dca_is_solved")
+    check(lib().dca_is_solved(env, dim, ptr(states), states.shape[0], ptr(out), stream_ptr()), "dca_is_solved")
     return out
 
 
 def hash64(states: torch.Tensor) -> torch.Tensor:
     states = _u8(states)
     out = torch.empty((states.shape[0],), dtype=torch.int64, device=states.device)
-    check(lib().dca_hash64(ptr(states), C.c_int64(states.shape[0]), states.shape[1], ptr(out), stream_ptr()),
-          "dca_hash64")
+    check(lib().dca_hash64(ptr(states), states.shape[0], states.shape[1], ptr(out), stream_ptr()), "dca_hash64")
     return out
 
 
 def nnet_input(env: int, dim: int, states: torch.Tensor) -> torch.Tensor:
     states = _u8(states)
     out = torch.empty_like(states)
-    check(lib().dca_nnet_input(env, dim, ptr(states), C.c_int64(states.shape[0]), ptr(out), stream_ptr()),
-          "dca_nnet_input")
+    check(lib().dca_nnet_input(env, dim, ptr(states), states.shape[0], ptr(out), stream_ptr()), "dca_nnet_input")
     return out
 
 
@@ -292,15 +342,15 @@ def onehot(idx: torch.Tensor, depth: int, dtype: torch.dtype = torch.float32) ->
     idx = _u8(idx)
     n, D = idx.shape
     out = torch.empty((n, D * depth), dtype=dtype, device=idx.device)
-    check(lib().dca_onehot(ptr(idx), C.c_int64(n), D, depth, ptr(out), _TORCH_DT[dtype], stream_ptr()), "dca_onehot")
+    check(lib().dca_onehot(ptr(idx), n, D, depth, ptr(out), _TORCH_DT[dtype], stream_ptr()), "dca_onehot")
     return out
 
 
 def heuristic_builtin(heur_id: int, states: torch.Tensor) -> torch.Tensor:
     states = _u8(states)
     out = torch.empty((states.shape[0],), dtype=torch.float32, device=states.device)
-    check(lib().dca_heuristic_builtin(heur_id, ptr(states), C.c_int64(states.shape[0]), states.shape[1], ptr(out),
-                                      stream_ptr()), "dca_heuristic_builtin")
+    check(lib().dca_heuristic_builtin(heur_id, ptr(states), states.shape[0], states.shape[1], ptr(out), stream_ptr()),
+          "dca_heuristic_builtin")
     return out
 
 
@@ -312,9 +362,8 @@ def generate_states(env: int, dim: int, n: int, back_lo: int, back_hi: int, seed
     states = torch.empty((n, D), dtype=torch.uint8, device=dev)
     nb = torch.empty((n,), dtype=torch.int32, device=dev)
     mv = torch.full((n, max(back_hi, 1)), -1, dtype=torch.int8, device=dev) if want_moves else None
-    check(lib().dca_generate_states(env, dim, C.c_int64(n), int(back_lo), int(back_hi), C.c_uint64(seed & (2**64 - 1)),
-                                    C.c_int64(index0), ptr(states), ptr(nb), ptr(mv), max(back_hi, 1), stream_ptr()),
-          "dca_generate_states")
+    check(lib().dca_generate_states(env, dim, n, back_lo, back_hi, seed & (2**64 - 1), index0, ptr(states), ptr(nb), ptr(mv),
+                                    max(back_hi, 1), stream_ptr()), "dca_generate_states")
     return states, nb, mv
 
 
@@ -325,8 +374,8 @@ def bellman_backup(h_children: torch.Tensor, solved_parent: Optional[torch.Tenso
     n = h.numel() // num_moves
     ctg = torch.empty((n,), dtype=torch.float32, device=h.device)
     am = torch.empty((n,), dtype=torch.int32, device=h.device)
-    check(lib().dca_bellman_backup(ptr(h), ptr(solved_parent), C.c_int64(n), int(num_moves), int(clip_zero), ptr(ctg),
-                                   ptr(am), stream_ptr()), "dca_bellman_backup")
+    check(lib().dca_bellman_backup(ptr(h), ptr(solved_parent), n, num_moves, clip_zero, ptr(ctg), ptr(am), stream_ptr()),
+          "dca_bellman_backup")
     return ctg, am
 
 
@@ -336,7 +385,7 @@ HCACHE_HIT, HCACHE_EVAL_STORE, HCACHE_DUP, HCACHE_EVAL_ONLY = 0, 1, 2, 3
 
 def hcache_bytes(row_bytes: int, slots: int) -> int:
     """Bytes of a heuristic-cache table: a pure function of its arguments (include/dca.h)."""
-    b = int(lib().dca_hcache_bytes(int(row_bytes), C.c_int64(int(slots))))
+    b = lib().dca_hcache_bytes(row_bytes, slots)
     check(min(b, 0), "dca_hcache_bytes")
     return b
 
@@ -359,7 +408,7 @@ class HeuristicCache:
         self.clear()
 
     def clear(self) -> None:
-        check(lib().dca_hcache_clear(ptr(self.table), self.row_bytes, C.c_int64(self.slots), stream_ptr()), "dca_hcache_clear")
+        check(lib().dca_hcache_clear(ptr(self.table), self.row_bytes, self.slots, stream_ptr()), "dca_hcache_clear")
 
     def used(self) -> int:
         """Slots in use (synchronises)."""
@@ -389,14 +438,14 @@ class HeuristicCache:
         status = torch.empty(n, dtype=torch.uint8, device=dev) if status is None else status
         assert h.dtype == torch.float32 and slot.dtype == torch.int32 and status.dtype == torch.uint8
         assert h.numel() >= n and slot.numel() >= n and status.numel() >= n
-        check(lib().dca_hcache_lookup(ptr(self.table), self.row_bytes, C.c_int64(self.slots), C.c_void_p(rows.data_ptr()), C.c_int64(n),
-                                      C.c_int64(ld), ptr(h), ptr(slot), ptr(status), stream_ptr()), "dca_hcache_lookup")
+        check(lib().dca_hcache_lookup(ptr(self.table), self.row_bytes, self.slots, _raw(rows), n, ld, ptr(h), ptr(slot), ptr(status),
+                                      stream_ptr()), "dca_hcache_lookup")
         return h, slot, status
 
     def finish(self, h: torch.Tensor, slot: torch.Tensor, status: torch.Tensor, n: Optional[int] = None) -> torch.Tensor:
         n = int(status.numel() if n is None else n)
-        check(lib().dca_hcache_finish(ptr(self.table), self.row_bytes, C.c_int64(self.slots), C.c_int64(n), ptr(slot), ptr(status),
-                                      ptr(h), stream_ptr()), "dca_hcache_finish")
+        check(lib().dca_hcache_finish(ptr(self.table), self.row_bytes, self.slots, n, ptr(slot), ptr(status), ptr(h), stream_ptr()),
+              "dca_hcache_finish")
         return h
 
 
@@ -407,7 +456,7 @@ PDB_NO_STATE, PDB_UNREACHABLE = 0xFF, 0xFE  # table bytes: two digits equal / a 
 
 def pdb_bytes(dim: int, k: int) -> int:
     """Bytes of one pattern's table, N^(k+1) with N = dim * dim: a pure function (include/dca.h); DcaError outside its limits."""
-    b = int(lib().dca_pdb_bytes(int(dim), int(k)))
+    b = lib().dca_pdb_bytes(dim, k)
     check(min(b, 0), "dca_pdb_bytes")
     return b
 
@@ -420,7 +469,7 @@ def pdb_build(dim: int, tiles, table: Optional[torch.Tensor] = None):
         table = torch.empty(nbytes, dtype=torch.uint8, device=require_gpu())
     assert table.dtype == torch.uint8 and table.numel() == nbytes
     sweeps = C.c_int(0)
-    check(lib().dca_pdb_build(int(dim), tiles.ctypes.data_as(C.c_void_p), int(len(tiles)), ptr(table), C.byref(sweeps), stream_ptr()),
+    check(lib().dca_pdb_build(dim, tiles.ctypes.data_as(C.c_void_p), len(tiles), ptr(table), C.byref(sweeps), stream_ptr()),
           "dca_pdb_build")
     return table, int(sweeps.value)
 
@@ -444,8 +493,8 @@ def pdb_eval(dim: int, states: torch.Tensor, partition, tables, out: Optional[to
     if out is None:
         out = torch.empty(n, dtype=torch.float32, device=states.device)
     assert out.dtype == torch.float32 and out.numel() >= n
-    check(lib().dca_pdb_eval(int(dim), C.c_void_p(states.data_ptr()), C.c_int64(n), C.c_int64(ld), int(len(partition)),
-                             flat.ctypes.data_as(C.c_void_p), ks.ctypes.data_as(C.c_void_p), ptrs, ptr(out), stream_ptr()), "dca_pdb_eval")
+    check(lib().dca_pdb_eval(dim, _raw(states), n, ld, len(partition), flat.ctypes.data_as(C.c_void_p), ks.ctypes.data_as(C.c_void_p),
+                             ptrs, ptr(out), stream_ptr()), "dca_pdb_eval")
     return out
 
 
@@ -463,9 +512,8 @@ class _BnTrainFn(torch.autograd.Function):
         invstd = torch.empty_like(mean)
         var_u = torch.empty_like(mean)
         sk = skip.contiguous() if skip is not None else None
-        check(lib().dca_bn_train_forward(ptr(x), ptr(sk), ptr(gamma.contiguous()), ptr(beta.contiguous()), C.c_int64(n),
-                                         C.c_int64(c), C.c_double(eps), int(relu), ptr(y), ptr(mean), ptr(invstd), ptr(var_u),
-                                         ptr(ws), C.c_int64(ws.numel()), stream_ptr()), "dca_bn_train_forward")
+        check(lib().dca_bn_train_forward(ptr(x), ptr(sk), ptr(gamma.contiguous()), ptr(beta.contiguous()), n, c, eps, relu, ptr(y),
+                                         ptr(mean), ptr(invstd), ptr(var_u), ptr(ws), ws.numel(), stream_ptr()), "dca_bn_train_forward")
         stats_out.append((mean, var_u))
         ctx.save_for_backward(x, y, mean, invstd, gamma)
         ctx.relu, ctx.has_skip = bool(relu), skip is not None
@@ -481,9 +529,9 @@ class _BnTrainFn(torch.autograd.Function):
         dskip = torch.empty_like(x) if ctx.has_skip else None
         dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
         dbeta = torch.empty_like(dgamma)
-        check(lib().dca_bn_train_backward(ptr(dy), ptr(x), ptr(y), ptr(mean), ptr(invstd), ptr(gamma.contiguous()),
-                                          C.c_int64(n), C.c_int64(c), int(ctx.relu), ptr(dx), ptr(dskip), ptr(dgamma),
-                                          ptr(dbeta), ptr(ws), C.c_int64(ws.numel()), stream_ptr()), "dca_bn_train_backward")
+        check(lib().dca_bn_train_backward(ptr(dy), ptr(x), ptr(y), ptr(mean), ptr(invstd), ptr(gamma.contiguous()), n, c, ctx.relu,
+                                          ptr(dx), ptr(dskip), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream_ptr()),
+              "dca_bn_train_backward")
         return dx, dskip, dgamma, dbeta, None, None, None
 
 
@@ -509,14 +557,6 @@ def _pad64(k: int) -> int:
     return (k + 63) // 64 * 64
 
 
-def _raw(t: Optional[torch.Tensor]) -> C.c_void_p:
-    """Device address of a tensor that the callee walks with an explicit row stride (views welcome); None -> NULL."""
-    if t is None:
-        return C.c_void_p(0)
-    assert t.is_cuda
-    return C.c_void_p(t.data_ptr())
-
-
 def _rows_cols_ld(x: torch.Tensor, m, n, ld):
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
     return (int(x.shape[0]) if m is None else int(m), int(x.shape[1]) if n is None else int(n),
@@ -531,7 +571,7 @@ def absmax_bits(x: torch.Tensor, m: Optional[int] = None, n: Optional[int] = Non
     m, n, ld = _rows_cols_ld(x, m, n, ld)
     if out is None:
         out = torch.empty(1, dtype=torch.int32, device=x.device)
-    check(lib().dca_absmax_bits(_raw(x), C.c_int64(m), C.c_int64(n), C.c_int64(ld), _raw(out), stream_ptr()), "dca_absmax_bits")
+    check(lib().dca_absmax_bits(_raw(x), m, n, ld, _raw(out), stream_ptr()), "dca_absmax_bits")
     return out
 
 
@@ -547,8 +587,8 @@ def split_planes_scaled(x: torch.Tensor, amax: Optional[torch.Tensor] = None, n_
     if out is None:
         out = torch.empty((2, m, ldo), dtype=torch.float16, device=x.device)
     assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (2, m, ldo)
-    check(lib().dca_split_planes_scaled(_raw(x), C.c_int64(m), C.c_int64(n), C.c_int64(ld), _raw(amax), _raw(out[0]), _raw(out[1]),
-                                        C.c_int64(ldo), C.c_int64(n_pad), stream_ptr()), "dca_split_planes_scaled")
+    check(lib().dca_split_planes_scaled(_raw(x), m, n, ld, _raw(amax), _raw(out[0]), _raw(out[1]), ldo, n_pad, stream_ptr()),
+          "dca_split_planes_scaled")
     return out
 
 
@@ -567,8 +607,8 @@ def split_rows_scaled(w: torch.Tensor, other_amax: Optional[torch.Tensor] = None
         col_scale = torch.empty(n, dtype=torch.float32, device=w.device)
     assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (2, n, ldo)
     assert col_scale.dtype == torch.float32 and col_scale.is_contiguous() and col_scale.numel() >= n
-    check(lib().dca_split_rows_scaled(_raw(w), C.c_int64(n), C.c_int64(k), C.c_int64(ld), _raw(out[0]), _raw(out[1]), C.c_int64(ldo),
-                                      C.c_int64(k_pad), _raw(col_scale), _raw(other_amax), stream_ptr()), "dca_split_rows_scaled")
+    check(lib().dca_split_rows_scaled(_raw(w), n, k, ld, _raw(out[0]), _raw(out[1]), ldo, k_pad, _raw(col_scale), _raw(other_amax),
+                                      stream_ptr()), "dca_split_rows_scaled")
     return out, col_scale
 
 
@@ -577,7 +617,7 @@ def fill_inv_pow2(amax: torch.Tensor, n: int, out: Optional[torch.Tensor] = None
     if out is None:
         out = torch.empty(int(n), dtype=torch.float32, device=amax.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n
-    check(lib().dca_fill_inv_pow2(_raw(out), C.c_int64(n), _raw(amax), stream_ptr()), "dca_fill_inv_pow2")
+    check(lib().dca_fill_inv_pow2(_raw(out), n, _raw(amax), stream_ptr()), "dca_fill_inv_pow2")
     return out
 
 
@@ -592,8 +632,7 @@ def cast_planes_scaled(x: torch.Tensor, amax: Optional[torch.Tensor] = None, n_p
     if out is None:
         out = torch.empty((1, m, ldo), dtype=torch.float16, device=x.device)
     assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (1, m, ldo)
-    check(lib().dca_cast_planes_scaled(_raw(x), C.c_int64(m), C.c_int64(n), C.c_int64(ld), _raw(amax), _raw(out), C.c_int64(ldo),
-                                       C.c_int64(n_pad), stream_ptr()), "dca_cast_planes_scaled")
+    check(lib().dca_cast_planes_scaled(_raw(x), m, n, ld, _raw(amax), _raw(out), ldo, n_pad, stream_ptr()), "dca_cast_planes_scaled")
     return out
 
 
@@ -611,8 +650,8 @@ def cast_rows_scaled(w: torch.Tensor, other_amax: Optional[torch.Tensor] = None,
         col_scale = torch.empty(n, dtype=torch.float32, device=w.device)
     assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (1, n, ldo)
     assert col_scale.dtype == torch.float32 and col_scale.is_contiguous() and col_scale.numel() >= n
-    check(lib().dca_cast_rows_scaled(_raw(w), C.c_int64(n), C.c_int64(k), C.c_int64(ld), _raw(out), C.c_int64(ldo), C.c_int64(k_pad),
-                                     _raw(col_scale), _raw(other_amax), stream_ptr()), "dca_cast_rows_scaled")
+    check(lib().dca_cast_rows_scaled(_raw(w), n, k, ld, _raw(out), ldo, k_pad, _raw(col_scale), _raw(other_amax), stream_ptr()),
+          "dca_cast_rows_scaled")
     return out, col_scale
 
 
@@ -629,9 +668,9 @@ def f16_gemm(a_h: torch.Tensor, w_h: torch.Tensor, col_scale: Optional[torch.Ten
     if out is None:
         out = torch.empty((m, n), dtype=torch.float32, device=a_h.device)
     assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (m, n) and out.stride(1) == 1
-    check(lib().dca_f16_gemm(_raw(a_h), C.c_int64(m), int(k), C.c_int64(a_h.stride(0) if m > 1 else k), _raw(w_h), int(n),
-                             C.c_int64(w_h.stride(0) if n > 1 else k), ptr(col_scale), C.c_double(alpha), ptr(bias), _raw(out),
-                             C.c_int64(out.stride(0) if m > 1 else (n + 3) // 4 * 4), stream_ptr()), "dca_f16_gemm")
+    check(lib().dca_f16_gemm(_raw(a_h), m, k, a_h.stride(0) if m > 1 else k, _raw(w_h), n, w_h.stride(0) if n > 1 else k,
+                             ptr(col_scale), alpha, ptr(bias), _raw(out), out.stride(0) if m > 1 else (n + 3) // 4 * 4, stream_ptr()),
+          "dca_f16_gemm")
     return out
 
 
@@ -676,14 +715,14 @@ WGRAD_MODES = ("library", "f16x3", "f16")  # how the training step computes nn.L
 
 def wgrad_splits(m: int, n: int, k: int) -> int:
     """Slices dca_wgrad_f16 cuts m batch rows into for an [n, k] weight gradient: a function of the three sizes alone."""
-    s = int(lib().dca_wgrad_splits(C.c_int64(m), int(n), int(k)))
+    s = lib().dca_wgrad_splits(m, n, k)
     check(min(s, 0), "dca_wgrad_splits")
     return s
 
 
 def wgrad_workspace_bytes(m: int, n: int, k: int) -> int:
     """Bytes of fp32 workspace dca_wgrad_f16 needs: 0 with one slice, else slices * n * k * 4."""
-    b = int(lib().dca_wgrad_workspace_bytes(C.c_int64(m), int(n), int(k)))
+    b = lib().dca_wgrad_workspace_bytes(m, n, k)
     check(min(b, 0), "dca_wgrad_workspace_bytes")
     return b
 
@@ -703,11 +742,10 @@ def wgrad_f16(dy_planes: torch.Tensor, x_planes: torch.Tensor, n: int, k: int, a
     assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, k) and out.stride(1) == 1
     need = wgrad_workspace_bytes(m, n, k)
     ws = torch.empty(need, dtype=torch.uint8, device=out.device) if need else None
-    lo = lambda t: _raw(t[1]) if (t.shape[0] > 1 and products != 1) else C.c_void_p(0)
-    check(lib().dca_wgrad_f16(_raw(dy_planes[0]), lo(dy_planes), C.c_int64(dy_planes.shape[2]), _raw(x_planes[0]), lo(x_planes),
-                              C.c_int64(x_planes.shape[2]), C.c_int64(m), int(n), int(k), _raw(amax_dy), _raw(amax_x), int(products),
-                              _raw(out), C.c_int64(out.stride(0) if n > 1 else k), ptr(ws), C.c_int64(need), stream_ptr()),
-          "dca_wgrad_f16")
+    dy_l, x_l = (t[1] if (t.shape[0] > 1 and products != 1) else None for t in (dy_planes, x_planes))
+    check(lib().dca_wgrad_f16(_raw(dy_planes[0]), _raw(dy_l), dy_planes.shape[2], _raw(x_planes[0]), _raw(x_l), x_planes.shape[2], m, n,
+                              k, _raw(amax_dy), _raw(amax_x), products, _raw(out), out.stride(0) if n > 1 else k, ptr(ws), need,
+                              stream_ptr()), "dca_wgrad_f16")
     return out
 
 
@@ -839,11 +877,11 @@ if TRAIN_WGRAD not in WGRAD_MODES:
 
 # ------------------------------------------------------------------------------ heuristic network, layer 1
 def l1_supported(state_dim: int, depth: int) -> bool:
-    return bool(lib().dca_l1_supported(int(state_dim), int(depth)))
+    return bool(lib().dca_l1_supported(state_dim, depth))
 
 
 def l1_kpad(state_dim: int, depth: int) -> int:
-    return int(lib().dca_l1_kpad(int(state_dim), int(depth)))
+    return lib().dca_l1_kpad(state_dim, depth)
 
 
 def l1_onehot_gemm(states_nnet: torch.Tensor, depth: int, w_tiles: torch.Tensor, planes: int, bias: torch.Tensor,
@@ -865,17 +903,17 @@ def l1_onehot_gemm(states_nnet: torch.Tensor, depth: int, w_tiles: torch.Tensor,
     else:
         out = torch.empty((m, n_pad), dtype=out_dtype, device=x.device)
         code = _TORCH_DT[out_dtype]
-    check(lib().dca_l1_onehot_gemm(ptr(x), C.c_int64(m), int(d), int(depth), ptr(w_tiles), int(planes), C.c_int64(n_pad),
-                                   ptr(bias), int(relu), ptr(out), code, ptr(overflow), stream_ptr()), "dca_l1_onehot_gemm")
+    check(lib().dca_l1_onehot_gemm(ptr(x), m, d, depth, ptr(w_tiles), planes, n_pad, ptr(bias), relu, ptr(out), code, ptr(overflow),
+                                   stream_ptr()), "dca_l1_onehot_gemm")
     return out
 
 
 def l1_supported8(state_dim: int, depth: int) -> bool:
-    return bool(lib().dca_l1_supported8(int(state_dim), int(depth)))
+    return bool(lib().dca_l1_supported8(state_dim, depth))
 
 
 def l1_kpad8(state_dim: int, depth: int) -> int:
-    return int(lib().dca_l1_kpad8(int(state_dim), int(depth)))
+    return lib().dca_l1_kpad8(state_dim, depth)
 
 
 def l1_onehot_gemm8(states_nnet: torch.Tensor, depth: int, w_tiles8: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor,
@@ -887,13 +925,13 @@ def l1_onehot_gemm8(states_nnet: torch.Tensor, depth: int, w_tiles8: torch.Tenso
     n_pad = bias.numel()
     assert scale.dtype == torch.float32 and bias.dtype == torch.float32 and scale.numel() == n_pad and n_pad % 128 == 0
     out = torch.empty((m, n_pad), dtype=E4M3, device=x.device)
-    check(lib().dca_l1_onehot_gemm8(ptr(x), C.c_int64(m), int(d), int(depth), ptr(w_tiles8), C.c_int64(n_pad), ptr(scale),
-                                    ptr(bias), int(relu), ptr(out), stream_ptr()), "dca_l1_onehot_gemm8")
+    check(lib().dca_l1_onehot_gemm8(ptr(x), m, d, depth, ptr(w_tiles8), n_pad, ptr(scale), ptr(bias), relu, ptr(out), stream_ptr()),
+          "dca_l1_onehot_gemm8")
     return out
 
 
 def l1_embed_supported(state_dim: int, depth: int) -> bool:
-    return bool(lib().dca_l1_embed_supported(int(state_dim), int(depth)))
+    return bool(lib().dca_l1_embed_supported(state_dim, depth))
 
 
 def l1_embed(states_nnet: torch.Tensor, depth: int, w_t: torch.Tensor, bias: torch.Tensor, relu: bool, out_dtype=torch.float32,
@@ -919,14 +957,14 @@ def l1_embed(states_nnet: torch.Tensor, depth: int, w_t: torch.Tensor, bias: tor
         code = _TORCH_DT[out_dtype]
     if m == 0:
         return out
-    check(lib().dca_l1_embed(ptr(x), C.c_int64(m), int(d), int(depth), ptr(w_t), C.c_int64(n_pad), ptr(bias), int(relu), ptr(out),
-                             code, ptr(overflow), stream_ptr()), "dca_l1_embed")
+    check(lib().dca_l1_embed(ptr(x), m, d, depth, ptr(w_t), n_pad, ptr(bias), relu, ptr(out), code, ptr(overflow), stream_ptr()),
+          "dca_l1_embed")
     return out
 
 
 def l1_embed_wgrad_slice_rows(state_dim: int, depth: int) -> int:
     """Rows per slice of dca_l1_embed_wgrad's summation order (a property of the geometry; 0: one slice)."""
-    s = int(lib().dca_l1_embed_wgrad_slice_rows(int(state_dim), int(depth)))
+    s = lib().dca_l1_embed_wgrad_slice_rows(state_dim, depth)
     check(min(s, 0), "dca_l1_embed_wgrad_slice_rows")
     return s
 
@@ -946,12 +984,11 @@ def l1_embed_wgrad(states_nnet: torch.Tensor, dy: torch.Tensor, depth: int, want
     db = torch.empty(n, dtype=torch.float32, device=x.device) if want_bias else None
     if m == 0 or n == 0:  # (an empty tensor has no address to hand over)
         return dw.zero_(), (None if db is None else db.zero_())
-    need = int(lib().dca_l1_embed_wgrad_workspace_bytes(C.c_int64(m), int(d), int(depth), C.c_int64(n)))
+    need = lib().dca_l1_embed_wgrad_workspace_bytes(m, d, depth, n)
     check(min(need, 0), "dca_l1_embed_wgrad_workspace_bytes")
     ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None
-    check(lib().dca_l1_embed_wgrad(ptr(x), C.c_int64(m), int(d), int(depth), _raw(dy), C.c_int64(dy.stride(0) if m > 1 else n),
-                                   C.c_int64(n), ptr(dw), C.c_int64(d * depth), ptr(db), ptr(ws), C.c_int64(need), stream_ptr()),
-          "dca_l1_embed_wgrad")
+    check(lib().dca_l1_embed_wgrad(ptr(x), m, d, depth, _raw(dy), dy.stride(0) if m > 1 else n, n, ptr(dw), d * depth, ptr(db), ptr(ws),
+                                   need, stream_ptr()), "dca_l1_embed_wgrad")
     return dw, db
 
 
@@ -1011,9 +1048,8 @@ def act_split(y: torch.Tensor, bias: Optional[torch.Tensor], skip: Optional[torc
     a3 = torch.empty((2, m, n), dtype=torch.float16, device=y.device) if want_a3 else None
     x_out = torch.empty_like(y) if want_x else None
     col_scale = alpha if isinstance(alpha, torch.Tensor) else None  # per-output-unit scale vector or one scalar
-    check(lib().dca_act_split(ptr(y), ptr(bias), ptr(skip), ptr(col_scale), C.c_double(1.0 if col_scale is not None else alpha),
-                              int(relu), C.c_int64(m), C.c_int64(n), ptr(x_out), ptr(a3), ptr(overflow), stream_ptr()),
-          "dca_act_split")
+    check(lib().dca_act_split(ptr(y), ptr(bias), ptr(skip), ptr(col_scale), 1.0 if col_scale is not None else alpha, relu, m, n,
+                              ptr(x_out), ptr(a3), ptr(overflow), stream_ptr()), "dca_act_split")
     return a3, x_out
 
 
@@ -1022,8 +1058,7 @@ def split_planes(x: torch.Tensor, overflow: Optional[torch.Tensor] = None) -> to
     assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] % 4 == 0
     m, n = x.shape
     out = torch.empty((2, m, n), dtype=torch.float16, device=x.device)
-    check(lib().dca_split_planes(ptr(x), C.c_int64(m), C.c_int64(n), C.c_int64(n), ptr(out[0]), ptr(out[1]), C.c_int64(n),
-                                 ptr(overflow), stream_ptr()), "dca_split_planes")
+    check(lib().dca_split_planes(ptr(x), m, n, n, ptr(out[0]), ptr(out[1]), n, ptr(overflow), stream_ptr()), "dca_split_planes")
     return out
 
 
@@ -1040,10 +1075,9 @@ def f16x3_gemm(a_planes: torch.Tensor, w_h: torch.Tensor, w_l: torch.Tensor, col
     assert w_h.shape[1] == k and (want_planes or want_x)
     planes = torch.empty((2, m, n), dtype=torch.float16, device=a_planes.device) if want_planes else None
     x_out = torch.empty((m, n), dtype=torch.float32, device=a_planes.device) if want_x else None
-    check(lib().dca_f16x3_gemm(ptr(a_planes[0]), ptr(a_planes[1]), C.c_int64(m), int(k), C.c_int64(k), ptr(w_h), ptr(w_l),
-                               int(n), C.c_int64(k), ptr(col_scale), C.c_double(alpha), ptr(bias), ptr(skip), int(relu),
-                               ptr(planes[0]) if want_planes else C.c_void_p(0), ptr(planes[1]) if want_planes else C.c_void_p(0),
-                               ptr(x_out), C.c_int64(n), ptr(overflow), stream_ptr()), "dca_f16x3_gemm")
+    check(lib().dca_f16x3_gemm(ptr(a_planes[0]), ptr(a_planes[1]), m, k, k, ptr(w_h), ptr(w_l), n, k, ptr(col_scale), alpha, ptr(bias),
+                               ptr(skip), relu, ptr(planes[0]) if want_planes else None, ptr(planes[1]) if want_planes else None,
+                               ptr(x_out), n, ptr(overflow), stream_ptr()), "dca_f16x3_gemm")
     return planes, x_out
 
 
@@ -1059,8 +1093,8 @@ def gemm16(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], skip:
     if out is None:
         out = torch.empty((m, n), dtype=a.dtype, device=a.device)
     assert out.dtype == a.dtype and out.shape == (m, n) and out.is_contiguous() and out.data_ptr() != a.data_ptr()
-    check(lib().dca_gemm16(ptr(a), C.c_int64(m), int(k), C.c_int64(k), ptr(w), int(n), C.c_int64(k), _TORCH_DT[a.dtype],
-                           ptr(bias), ptr(skip), int(relu), ptr(out), C.c_int64(n), stream_ptr()), "dca_gemm16")
+    check(lib().dca_gemm16(ptr(a), m, k, k, ptr(w), n, k, _TORCH_DT[a.dtype], ptr(bias), ptr(skip), relu, ptr(out), n, stream_ptr()),
+          "dca_gemm16")
     return out
 
 
@@ -1078,9 +1112,8 @@ def gemm8(a: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, bias: Optional[
         out16 = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
     assert out16 is None or (out16.dtype == torch.bfloat16 and out16.shape == (m, n) and out16.is_contiguous())
     out8 = torch.empty((m, n), dtype=E4M3, device=a.device) if out8_scale is not None else None
-    check(lib().dca_gemm8(ptr(a), C.c_int64(m), int(k), C.c_int64(k), ptr(w), int(n), C.c_int64(k), ptr(scale), ptr(bias), ptr(skip),
-                          int(relu), ptr(out16), C.c_int64(n), ptr(out8), C.c_int64(n),
-                          C.c_double(out8_scale if out8_scale is not None else 1.0), stream_ptr()), "dca_gemm8")
+    check(lib().dca_gemm8(ptr(a), m, k, k, ptr(w), n, k, ptr(scale), ptr(bias), ptr(skip), relu, ptr(out16), n, ptr(out8), n,
+                          out8_scale if out8_scale is not None else 1.0, stream_ptr()), "dca_gemm8")
     return out16, out8
 
 
@@ -1099,9 +1132,8 @@ def gemm8_mx(a: torch.Tensor, a_scale: torch.Tensor, w: torch.Tensor, w_scale: t
         out16 = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
     out8 = torch.empty((m, n), dtype=E4M3, device=a.device) if want8 else None
     out_sc = torch.empty((m, n // 64), dtype=torch.uint8, device=a.device) if want8 else None
-    check(lib().dca_gemm8_mx(ptr(a), ptr(a_scale), C.c_int64(m), int(k), C.c_int64(k), C.c_int64(k // 64), ptr(w), int(n), C.c_int64(k),
-                             ptr(w_scale), ptr(bias), ptr(skip), int(relu), ptr(out16), C.c_int64(n), ptr(out8), C.c_int64(n),
-                             ptr(out_sc), C.c_int64(n // 64), stream_ptr()), "dca_gemm8_mx")
+    check(lib().dca_gemm8_mx(ptr(a), ptr(a_scale), m, k, k, k // 64, ptr(w), n, k, ptr(w_scale), ptr(bias), ptr(skip), relu, ptr(out16),
+                             n, ptr(out8), n, ptr(out_sc), n // 64, stream_ptr()), "dca_gemm8_mx")
     return out16, out8, out_sc
 
 
@@ -1113,8 +1145,8 @@ def l1_onehot_gemm_mx(states_nnet: torch.Tensor, depth: int, w_tiles: torch.Tens
     n_pad = bias.numel()
     out = torch.empty((m, n_pad), dtype=E4M3, device=x.device)
     sc = torch.empty((m, n_pad // 64), dtype=torch.uint8, device=x.device)
-    check(lib().dca_l1_onehot_gemm_mx(ptr(x), C.c_int64(m), int(d), int(depth), ptr(w_tiles), C.c_int64(n_pad), ptr(bias), int(relu),
-                                      ptr(out), ptr(sc), C.c_int64(n_pad // 64), stream_ptr()), "dca_l1_onehot_gemm_mx")
+    check(lib().dca_l1_onehot_gemm_mx(ptr(x), m, d, depth, ptr(w_tiles), n_pad, ptr(bias), relu, ptr(out), ptr(sc), n_pad // 64,
+                                      stream_ptr()), "dca_l1_onehot_gemm_mx")
     return out, sc
 
 
@@ -1123,8 +1155,7 @@ def quant_e4m3(x: torch.Tensor, scale: float) -> torch.Tensor:
     assert x.dtype in (torch.float32, torch.bfloat16) and x.is_contiguous() and x.dim() == 2 and x.shape[1] % 4 == 0
     m, n = x.shape
     out = torch.empty((m, n), dtype=E4M3, device=x.device)
-    check(lib().dca_quant_e4m3(ptr(x), _TORCH_DT[x.dtype], C.c_int64(m), C.c_int64(n), C.c_int64(n), C.c_double(scale), ptr(out),
-                               C.c_int64(n), stream_ptr()), "dca_quant_e4m3")
+    check(lib().dca_quant_e4m3(ptr(x), _TORCH_DT[x.dtype], m, n, n, scale, ptr(out), n, stream_ptr()), "dca_quant_e4m3")
     return out
 
 
@@ -1152,11 +1183,11 @@ def head_gemv(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], ou
     if m == 0:
         return out
     if out_dtype == torch.float64:
-        check(lib().dca_head_gemv64(C.c_void_p(x.data_ptr()), C.c_int64(m), int(k), C.c_int64(x.stride(0)), ptr(w), ptr(bias),
-                                    int(w.shape[0]), ptr(out), stream_ptr()), "dca_head_gemv64")
+        check(lib().dca_head_gemv64(_raw(x), m, k, x.stride(0), ptr(w), ptr(bias), w.shape[0], ptr(out), stream_ptr()),
+              "dca_head_gemv64")
         return out
-    check(lib().dca_head_gemv(C.c_void_p(x.data_ptr()), dts[x.dtype], C.c_int64(m), int(k), C.c_int64(x.stride(0)), ptr(w),
-                              ptr(bias), int(w.shape[0]), ptr(out), stream_ptr()), "dca_head_gemv")
+    check(lib().dca_head_gemv(_raw(x), dts[x.dtype], m, k, x.stride(0), ptr(w), ptr(bias), w.shape[0], ptr(out), stream_ptr()),
+          "dca_head_gemv")
     return out
 
 
@@ -1176,9 +1207,8 @@ def gemm64(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], skip:
     assert skip is None or (skip.dtype == torch.float64 and tuple(skip.shape) == (m, n) and _row_view(skip, False)
                             and skip.stride(0) == out.stride(0))  # one ldo for both
     assert skip is None or skip.data_ptr() == out.data_ptr() or skip.data_ptr() != a.data_ptr()
-    vp = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
-    check(lib().dca_gemm64(vp(a), C.c_int64(m), int(k), C.c_int64(a.stride(0)), vp(w), int(n), C.c_int64(w.stride(0)), ptr(bias),
-                           vp(skip), int(relu), vp(out), C.c_int64(out.stride(0)), stream_ptr()), "dca_gemm64")
+    check(lib().dca_gemm64(_raw(a), m, k, a.stride(0), _raw(w), n, w.stride(0), ptr(bias), _raw(skip), relu, _raw(out), out.stride(0),
+                           stream_ptr()), "dca_gemm64")
     return out
 
 
@@ -1197,18 +1227,17 @@ def l1_embed64(states_nnet: torch.Tensor, depth: int, w_t: torch.Tensor, bias: t
     assert out.dtype == torch.float64 and tuple(out.shape) == (m, n_pad)
     if m == 0:
         return out
-    check(lib().dca_l1_embed64(ptr(x), C.c_int64(m), int(d), int(depth), ptr(w_t), C.c_int64(n_pad), ptr(bias), int(relu), ptr(out),
-                               stream_ptr()), "dca_l1_embed64")
+    check(lib().dca_l1_embed64(ptr(x), m, d, depth, ptr(w_t), n_pad, ptr(bias), relu, ptr(out), stream_ptr()), "dca_l1_embed64")
     return out
 
 
 def gemm16_variant(v: int) -> None:
     """Test hook: 3 (default) = ping-pong schedule, swapped operand roles, lean tail per layer form; 2 = the same schedule with
     the general tail; 1 = two-stage loop (one drain + barrier per K-step).  Bit-identical results."""
-    check(lib().dca_gemm16_variant(int(v)), "dca_gemm16_variant")
+    check(lib().dca_gemm16_variant(v), "dca_gemm16_variant")
 
 
 def f16x3_gemm_variant(v: int) -> None:
     """Test hook: 3 (default) = LDS-DMA 256x256 kernel on the ping-pong schedule, 2 = the same tile with two whole-K-step
     stages (bit-identical)."""
-    check(lib().dca_f16x3_gemm_variant(int(v)), "dca_f16x3_gemm_variant")
+    check(lib().dca_f16x3_gemm_variant(v), "dca_f16x3_gemm_variant")

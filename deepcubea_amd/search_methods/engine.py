@@ -42,10 +42,9 @@ class BwasEngine:
         self.m_capacity = self.batch_size * self.num_moves * self.num_instances
         self._h = C.c_void_p(0)
         self.packed = bool(packed)
-        _lib.check(_lib.lib().dca_engine_create_multi(C.byref(self._h), self.env_id, self.dim, C.c_double(self.weight),
-                                                      self.batch_size, C.c_int64(int(max_nodes)), semantics,
-                                                      -1 if packed else _OH[onehot_dtype], self.num_instances),
-                   "dca_engine_create_multi")
+        _lib.check(_lib.lib().dca_engine_create_multi(C.byref(self._h), self.env_id, self.dim, self.weight, self.batch_size,
+                                                      max_nodes, semantics, -1 if packed else _OH[onehot_dtype],
+                                                      self.num_instances), "dca_engine_create_multi")
         self._zero_h = torch.zeros(1, dtype=torch.float32, device="cuda")
         self.rows_evaluated = 0  # network rows handed to heuristic closures by step()
         self.last_rows = -1      # packed stepping: rows of the last iteration (0 = nothing left to expand: every instance done)
@@ -55,7 +54,7 @@ class BwasEngine:
                 self.onehot_stride = int(onehot_stride)
             elif onehot_dtype is not None:
                 self.onehot_stride = (self.onehot_stride + 7) // 8 * 8
-            _lib.check(_lib.lib().dca_engine_enable_packed(self._h, _OH[onehot_dtype], C.c_int64(self.onehot_stride)),
+            _lib.check(_lib.lib().dca_engine_enable_packed(self._h, _OH[onehot_dtype], self.onehot_stride),
                        "dca_engine_enable_packed")
             self.packed_capacity = (self.m_capacity + 1023) // 1024 * 1024
 
@@ -96,25 +95,24 @@ class BwasEngine:
     def reset(self, root: np.ndarray, instance: int = 0) -> None:
         r = np.ascontiguousarray(root, dtype=np.uint8)
         assert r.shape == (self.state_dim,)
-        _lib.check(_lib.lib().dca_engine_reset_instance(self._h, int(instance), r.ctypes.data_as(C.c_void_p),
-                                                        _lib.stream_ptr()), "dca_engine_reset_instance")
+        _lib.check(_lib.lib().dca_engine_reset_instance(self._h, instance, r.ctypes.data_as(C.c_void_p), _lib.stream_ptr()),
+                   "dca_engine_reset_instance")
 
     def root_nnet_in(self, instance: int = 0) -> torch.Tensor:
         p = C.c_void_p(0)
-        _lib.check(_lib.lib().dca_engine_root_nnet_in_instance(self._h, int(instance), C.byref(p)),
-                   "dca_engine_root_nnet_in_instance")
+        _lib.check(_lib.lib().dca_engine_root_nnet_in_instance(self._h, instance, C.byref(p)), "dca_engine_root_nnet_in_instance")
         return _wrap_u8(p.value, (1, self.state_dim))
 
     def root_commit(self, h_root: torch.Tensor, instance: int = 0) -> None:
         h_root = h_root.to(torch.float32).contiguous()
-        _lib.check(_lib.lib().dca_engine_root_commit_instance(self._h, int(instance), _lib.ptr(h_root),
-                                                              _lib.stream_ptr()), "dca_engine_root_commit_instance")
+        _lib.check(_lib.lib().dca_engine_root_commit_instance(self._h, instance, _lib.ptr(h_root), _lib.stream_ptr()),
+                   "dca_engine_root_commit_instance")
 
     def pop_expand(self) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """-> (nnet_in [M,D] uint8 view, onehot [M, D*depth] view or None), M = batch*num_moves fixed."""
         pn, po, m = C.c_void_p(0), C.c_void_p(0), C.c_int64(0)
-        _lib.check(_lib.lib().dca_engine_pop_expand(self._h, C.byref(pn), C.byref(po), C.byref(m),
-                                                    _lib.stream_ptr()), "dca_engine_pop_expand")
+        _lib.check(_lib.lib().dca_engine_pop_expand(self._h, C.byref(pn), C.byref(po), C.byref(m), _lib.stream_ptr()),
+                   "dca_engine_pop_expand")
         nn = _wrap_u8(pn.value, (m.value, self.state_dim))
         oh = None
         if po.value:
@@ -143,36 +141,35 @@ class BwasEngine:
 
     def set_weight(self, weight: float, instance: int = 0) -> None:
         """Weight of path cost of ONE instance (astar.py:196 `weights`: AStar takes a list, one per instance)."""
-        _lib.check(_lib.lib().dca_engine_set_weight_instance(self._h, int(instance), C.c_double(float(weight))),
-                   "dca_engine_set_weight_instance")
+        _lib.check(_lib.lib().dca_engine_set_weight_instance(self._h, instance, weight), "dca_engine_set_weight_instance")
 
     def set_weights(self, weights) -> None:
         """Weights of path cost of instances 0 .. len(weights)-1 at once (between iterations)."""
         w = np.ascontiguousarray(weights, dtype=np.float64)
-        _lib.check(_lib.lib().dca_engine_set_weights(self._h, w.ctypes.data_as(C.c_void_p), int(w.size)), "dca_engine_set_weights")
+        _lib.check(_lib.lib().dca_engine_set_weights(self._h, w.ctypes.data_as(C.c_void_p), w.size), "dca_engine_set_weights")
 
     def reset_many(self, roots_dev: torch.Tensor) -> None:
         """Instances 0..n-1 restart from the rows of a DEVICE tensor [n, D] uint8, the others are parked; nothing synchronises."""
         assert roots_dev.is_cuda and roots_dev.dtype == torch.uint8 and roots_dev.is_contiguous()
         assert roots_dev.dim() == 2 and roots_dev.shape[1] == self.state_dim and roots_dev.shape[0] <= self.num_instances
-        _lib.check(_lib.lib().dca_engine_reset_many(self._h, _lib.ptr(roots_dev), int(roots_dev.shape[0]), _lib.stream_ptr()),
+        _lib.check(_lib.lib().dca_engine_reset_many(self._h, _lib.ptr(roots_dev), roots_dev.shape[0], _lib.stream_ptr()),
                    "dca_engine_reset_many")
 
     def root_commit_many(self, h_roots: torch.Tensor) -> None:
         h = h_roots.to(torch.float32).contiguous().view(-1)
-        _lib.check(_lib.lib().dca_engine_root_commit_many(self._h, _lib.ptr(h), int(h.numel()), _lib.stream_ptr()),
+        _lib.check(_lib.lib().dca_engine_root_commit_many(self._h, _lib.ptr(h), h.numel(), _lib.stream_ptr()),
                    "dca_engine_root_commit_many")
 
     def set_weights_dev(self, weights_dev: torch.Tensor) -> None:
         """Weights of path cost of instances 0..n-1 from a device float64 tensor (stream-ordered, no host sync)."""
         w = weights_dev.to(torch.float64).contiguous().view(-1)
         assert w.is_cuda and 1 <= w.numel() <= self.num_instances
-        _lib.check(_lib.lib().dca_engine_set_weights_dev(self._h, _lib.ptr(w), int(w.numel()), _lib.stream_ptr()),
+        _lib.check(_lib.lib().dca_engine_set_weights_dev(self._h, _lib.ptr(w), w.numel(), _lib.stream_ptr()),
                    "dca_engine_set_weights_dev")
 
     def park(self, instance: int) -> None:
         """Mark an instance finished (its launches are no-ops) until it is reset again."""
-        _lib.check(_lib.lib().dca_engine_park_instance(self._h, int(instance), _lib.stream_ptr()), "dca_engine_park_instance")
+        _lib.check(_lib.lib().dca_engine_park_instance(self._h, instance, _lib.stream_ptr()), "dca_engine_park_instance")
 
     def last_popped(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """Between pop_expand and commit: (states u8 [K*batch, D], flags u8 [K*batch]) of the parents just popped,
@@ -219,8 +216,8 @@ class BwasEngine:
         self.commit(h.to(torch.float32).contiguous())
 
     def run_builtin(self, heur_id: int, iters: int, use_graph: bool = False) -> None:
-        _lib.check(_lib.lib().dca_engine_run_builtin(self._h, heur_id, int(iters), int(use_graph),
-                                                     _lib.stream_ptr()), "dca_engine_run_builtin")
+        _lib.check(_lib.lib().dca_engine_run_builtin(self._h, heur_id, iters, use_graph, _lib.stream_ptr()),
+                   "dca_engine_run_builtin")
 
     PROF_SLOTS = ["refill_hist", "refill_scan", "refill_move", "sel_hist", "sel_scan", "sel_collect", "rank", "expand",
                   "probe", "decide", "pack", "commit", "rank_small", "rank_big", "rank_big_load", "rank_big_count",
@@ -232,16 +229,15 @@ class BwasEngine:
         iteration -> {"span_ms": {launch: ms}, "gap_ms": {launch: ms}}.  Launches that did not run are omitted."""
         n = len(self.PROF_SLOTS)
         span, gap = (C.c_float * n)(), (C.c_float * n)()
-        _lib.check(_lib.lib().dca_engine_profile_builtin(self._h, heur_id, int(iters), int(use_graph), span, gap,
-                                                         _lib.stream_ptr()), "dca_engine_profile_builtin")
+        _lib.check(_lib.lib().dca_engine_profile_builtin(self._h, heur_id, iters, use_graph, span, gap, _lib.stream_ptr()),
+                   "dca_engine_profile_builtin")
         it = max(iters, 1)
         return {"span_ms": {nm: span[k] / it for k, nm in enumerate(self.PROF_SLOTS) if span[k] > 0},
                 "gap_ms": {nm: gap[k] / it for k, nm in enumerate(self.PROF_SLOTS) if span[k] > 0}}
 
     def set_tiers(self, front_keep: int, front_max: int) -> None:
         """Override the FRONT-tier hysteresis (tests use tiny values to force constant refills / spills)."""
-        _lib.check(_lib.lib().dca_engine_set_tiers(self._h, C.c_int64(front_keep), C.c_int64(front_max)),
-                   "dca_engine_set_tiers")
+        _lib.check(_lib.lib().dca_engine_set_tiers(self._h, front_keep, front_max), "dca_engine_set_tiers")
 
     def debug(self) -> dict:
         out = (C.c_double * 16)()
@@ -252,7 +248,7 @@ class BwasEngine:
 
     def status(self, instance: int = 0) -> dict:
         st = _lib.DcaStatus()
-        _lib.check(_lib.lib().dca_engine_status_instance(self._h, int(instance), C.byref(st), _lib.stream_ptr()),
+        _lib.check(_lib.lib().dca_engine_status_instance(self._h, instance, C.byref(st), _lib.stream_ptr()),
                    "dca_engine_status_instance")
         return {k: getattr(st, k) for k, _ in _lib.DcaStatus._fields_}
 
@@ -265,8 +261,8 @@ class BwasEngine:
     def solution(self, instance: int = 0) -> Tuple[List[int], float]:
         moves = np.zeros(4096, np.int32)
         n, pc = C.c_int(0), C.c_double(0)
-        _lib.check(_lib.lib().dca_engine_solution_instance(self._h, int(instance), moves.ctypes.data_as(C.c_void_p),
-                                                           moves.size, C.byref(n), C.byref(pc), _lib.stream_ptr()),
+        _lib.check(_lib.lib().dca_engine_solution_instance(self._h, instance, moves.ctypes.data_as(C.c_void_p), moves.size,
+                                                           C.byref(n), C.byref(pc), _lib.stream_ptr()),
                    "dca_engine_solution_instance")
         return moves[:n.value].tolist(), float(pc.value)
 

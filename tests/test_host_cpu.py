@@ -28,6 +28,81 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert _lib.lib().dca_abi_version() == 6
 
 
+def _header_prototypes():
+    """{name: (C return type, [C parameter types])} of every dca_*(...) prototype in the two headers."""
+    protos = {}
+    for header in ("dca.h", "dca_debug.h"):
+        text = open(os.path.join(ROOT, "include", header)).read()
+        text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)  # comments first: they sit inside parameter lists too
+        text = re.sub(r"//[^\n]*", " ", text)
+        text = "\n".join(line for line in text.split("\n") if not line.lstrip().startswith("#"))
+        for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(dca_\w+)\s*\(([^()]*)\)\s*;", text):
+            ret, name, params = " ".join(m.group(1).split()), m.group(2), [" ".join(p.split()) for p in m.group(3).split(",")]
+            assert name not in protos, "%s is declared twice" % name
+            if params == ["void"]:
+                params = []
+            # a parameter is "type name": drop the name, keep the stars with the type
+            protos[name] = (ret, [re.sub(r"\w+$", "", p).strip() for p in params])
+    return protos
+
+
+def test_every_entry_point_has_the_headers_signature():
+    """lib() declares restype and argtypes of every entry point, and they are what include/dca.h and include/dca_debug.h say:
+    a call with a wrong width or argument count then raises instead of reading half a register."""
+    from deepcubea_amd import _lib
+    scalars = {"int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double}
+    returns = {"int": C.c_int, "int64_t": C.c_int64, "void": None, "const char*": C.c_char_p,
+               "const uint8_t*": C.POINTER(C.c_uint8)}
+
+    def param(ctype, where):
+        if ctype.endswith("*"):  # any pointer: dca_engine*, dca_engine**, const uint8_t**, dca_status*, void* stream, ...
+            return C.c_void_p
+        assert ctype in scalars, "%s: no rule for the C parameter type %r" % (where, ctype)
+        return scalars[ctype]
+
+    protos = _header_prototypes()
+    assert len(protos) >= 105 and set(protos) == set(_lib.ABI_SYMBOLS) and len(set(_lib.ABI_SYMBOLS)) == len(_lib.ABI_SYMBOLS)
+    L = _lib.lib()
+    for name, (ret, params) in protos.items():
+        fn = getattr(L, name)
+        assert ret in returns, "%s: no rule for the C return type %r" % (name, ret)
+        assert fn.restype == returns[ret], "%s: restype %r, the header returns %s" % (name, fn.restype, ret)
+        assert fn.argtypes is not None, "%s has no argtypes" % name
+        assert list(fn.argtypes) == [param(p, name) for p in params], name
+    for name in ("dca_last_error", "dca_cube3_perm_table", "dca_cube4_perm_table", "dca_engine_destroy"):
+        assert protos[name][0] != "int"  # the parser does tell the return types apart
+    assert protos["dca_abi_version"] == ("int", []) and protos["dca_hcache_bytes"] == ("int64_t", ["int", "int64_t"])
+    assert protos["dca_engine_root_nnet_in"][1] == ["dca_engine*", "const uint8_t**"]
+    assert protos["dca_generate_states"][1][5] == "uint64_t" and protos["dca_engine_set_weight_instance"][1][2] == "double"
+
+
+def test_every_call_site_passes_the_declared_number_of_arguments():
+    """Every direct call `<expr>.dca_NAME(...)` in the package, the benchmark, the tests and the tools has as many positional
+    arguments as the entry point has parameters (a wrong count is a TypeError that only the GPU machine would raise)."""
+    import ast
+    from deepcubea_amd import _lib
+    want = {name: len(fn.argtypes) for name in _lib.ABI_SYMBOLS for fn in [getattr(_lib.lib(), name)]}
+    files = [os.path.join(ROOT, "bench.py")]
+    for top in ("deepcubea_amd", "tests", "tools"):
+        for d, _, names in os.walk(os.path.join(ROOT, top)):
+            files += [os.path.join(d, n) for n in names if n.endswith(".py")]
+    seen, bad = 0, []
+    for path in sorted(files):
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr.startswith("dca_")):
+                continue
+            if any(isinstance(a, ast.Starred) for a in node.args):
+                continue
+            seen += 1
+            where = "%s:%d %s" % (os.path.relpath(path, ROOT), node.lineno, node.func.attr)
+            if node.func.attr not in want:
+                bad.append(where + ": not an entry point")
+            elif len(node.args) != want[node.func.attr] or node.keywords:
+                bad.append("%s: %d arguments, the header has %d" % (where, len(node.args), want[node.func.attr]))
+    assert not bad, "\n".join(bad)
+    assert seen >= 200  # the walk does find the call sites (221 when this test was written)
+
+
 def test_host_tables_match_golden(golden):
     from deepcubea_amd import _lib
     assert np.array_equal(_lib.cube3_perm_table(), golden["cube3_perm"])
