@@ -6,6 +6,17 @@
 #include "../../include/dca.h"
 #include "../../include/dca_debug.h"
 
+// Address spaces for pointers whose home a kernel knows: a global-memory pointer's accesses are global_* instructions that count
+// on vmcnt alone (a generic pointer's are flat_*, vmcnt AND lgkmcnt).  Only the device compilation pass sees them: the host pass
+// parses the kernels too, without the device language's implicit conversions between address spaces, and never runs them.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DCA_GLOBAL __attribute__((address_space(1)))
+#define DCA_LDS __attribute__((address_space(3)))
+#else
+#define DCA_GLOBAL
+#define DCA_LDS
+#endif
+
 namespace dca {
 
 // ------------------------------------------------------------------------------------------

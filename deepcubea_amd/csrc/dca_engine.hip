@@ -209,12 +209,7 @@ __device__ __forceinline__ uint32_t rank_shares(uint32_t cn) {
 // accesses, which count on vmcnt AND lgkmcnt, so that every wait drains every queue), and uniform control-block reads
 // become scalar loads.  The HOST view (EngH, what the host fills in and uploads) holds plain pointers; same layout.
 // (Only the device compilation pass sees the address space: the host pass parses the kernels too, without the device
-// language's implicit conversions between a global and a generic pointer, and never runs them.)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define DCA_GLOBAL __attribute__((address_space(1)))
-#else
-#define DCA_GLOBAL
-#endif
+// language's implicit conversions between a global and a generic pointer, and never runs them: DCA_GLOBAL, dca_common.h.)
 template <class T>
 using gp = T DCA_GLOBAL*;  // pointer into global memory
 template <class T>

@@ -18,18 +18,13 @@
 // are staged through registers — 16-byte coalesced global loads issued a whole K-step ahead of their LDS write, so they
 // fly under the 48 MFMAs per wave of the current step — into row-major LDS rows whose 16-byte chunks are XOR-swizzled
 // with (row >> 1) & 7: every ds_read_b128 lane group then touches each LDS bank exactly once.  Two workgroups per CU
-// (2 x 64 KB LDS, <= 256 VGPRs) overlap one group's staging with the other's MFMAs.  Workgroup ids are remapped so that
-// the N tiles sharing an A tile run on ONE XCD (its L2 then reads the A tile from HBM once).
-#include <atomic>
+// (2 x 64 KB LDS, <= 256 VGPRs) overlap one group's staging with the other's MFMAs.  Tile map, swizzles, the LDS-DMA call, the
+// half-tile slots and the launchers' helpers are the shared ones of dca_dense.h.
 #include <type_traits>
 
-#include "dca_common.h"
+#include "dca_dense.h"
 
 namespace dca {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int GBK = 64;  // K granularity of the planes (operands are padded to it)
 
@@ -48,8 +43,6 @@ struct GemmArgs {
     float* x_out;             // result fp32 [m, ldo] or null
     int* overflow;
 };
-
-__device__ __forceinline__ uint32_t swz(uint32_t row, uint32_t chunk) { return row * 128u + ((chunk ^ ((row >> 1) & 7u)) << 4); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // v2 (default): 256 x 256 outputs per workgroup, 8 waves as 2 (M) x 4 (N), each wave 4 x 2 tiles of 32x32x16 (128
@@ -72,11 +65,7 @@ constexpr int HLDS = 2 * HSTAGE;      // two stages: 128 KB
 // operands — MFMAs alone sustain 2030 instead of 1780 TFLOP/s at the chip's power limit (tools/mfma_power_probe.hip; csrc/
 // dca_gemm16.hip has the story) — and these kernels run AT that limit.  A fragment of a 16-row block for one 32-deep K-step:
 // lane (g = lane >> 4, j = lane & 15) holds row j, 16-byte chunk g of the 64-byte row; D = A . B: lane (g, j) holds D[4 g + r][j].
-// The chunk swizzle of a 64-byte row is chunk ^ f((row >> 2) & 3) with f = (0, 2, 3, 1) (it was the identity for the 32-row
-// fragments): the four lane groups of a ds_read_b128 — {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and their upper twins — then
-// meet 16 different (row & 3, slot) pairs, i.e. every bank group once.
-__device__ __forceinline__ uint32_t swz64_key(uint32_t row) { return (0x78u >> (((row >> 2) & 3u) * 2u)) & 3u; }
-__device__ __forceinline__ uint32_t swz64(uint32_t row, uint32_t chunk) { return row * 64u + ((chunk ^ swz64_key(row)) << 4); }
+// The chunk swizzle of a 64-byte row is swz64 (dca_dense.h; it was the identity for the 32-row fragments).
 __device__ __forceinline__ f32x4 mma16h(const f16x8& a, const f16x8& b, const f32x4& c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
@@ -192,15 +181,10 @@ __global__ __launch_bounds__(HTHREADS, 2) void k_f16x3_gemm_v2(const GemmArgs p)
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, l31 = lane & 31, h = lane >> 5;
     const int wm = w >> 2, wn = w & 3;
-    const int nNt = (p.n + HBN_T - 1) / HBN_T;
-    const int64_t nMt = (p.m + HBM_T - 1) / HBM_T;
-    const int64_t bid = blockIdx.x;
-    const int64_t slot = bid >> 3;
-    const int64_t mt = (slot / nNt) * 8 + (bid & 7);  // the N tiles of one M tile sit on one XCD
-    const int nt = (int)(slot % nNt);
-    if (mt >= nMt) return;
-    const int64_t m0 = mt * HBM_T;
-    const int n0 = nt * HBN_T;
+    const TileOfBlock tb = tile_of_block<HBM_T, HBN_T>(p.m, p.n);
+    if (!tb.has) return;
+    const int64_t m0 = tb.m0;
+    const int n0 = tb.n0;
 
     // LDS-DMA map: instruction q of wave w fills rows [rb*16, rb*16+16) of image q >> 1, rb = (q & 1) * 8 + w; lane i
     // lands on row i >> 2, physical chunk i & 3, and therefore fetches logical chunk (i & 3) ^ ((row >> 2) & 3).
@@ -225,8 +209,7 @@ __global__ __launch_bounds__(HTHREADS, 2) void k_f16x3_gemm_v2(const GemmArgs p)
 #pragma unroll
         for (int q = 0; q < 8; q++) {
             uint8_t* dst = lds + stage * HSTAGE + (q >> 1) * HIMG + ((q & 1) * 8 + w) * 1024;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[q] + k0),
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+            lds_dma16(src[q] + k0, dst);
         }
     };
 
@@ -289,25 +272,15 @@ __global__ __launch_bounds__(HTHREADS, 2) void k_f16x3_gemm_v2(const GemmArgs p)
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int PSLOT3 = 2 * 128 * 64;  // one half-tile: two planes of 128 rows x 64 B
 constexpr int PBUF3 = 4 * PSLOT3;     // one K-step: A01 | A23 | B0 | B1
-constexpr int PS_A01 = 0, PS_A23 = 1, PS_B0 = 2, PS_B1 = 3;
-
-#define DCA_BAR() asm volatile("s_barrier" ::: "memory")
-#define DCA_RD_DONE_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#define DCA_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 
 __global__ __launch_bounds__(HTHREADS, 2) void k_f16x3_gemm_v3(const GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, l31 = lane & 31, h = lane >> 5;
     const int wm = w >> 2, wn = w & 3;
-    const int nNt = (p.n + HBN_T - 1) / HBN_T;
-    const int64_t nMt = (p.m + HBM_T - 1) / HBM_T;
-    const int64_t bid = blockIdx.x;
-    const int64_t slot = bid >> 3;
-    const int64_t mt = (slot / nNt) * 8 + (bid & 7);  // the N tiles of one M tile sit on one XCD
-    const int nt = (int)(slot % nNt);
-    if (mt >= nMt) return;
-    const int64_t m0 = mt * HBM_T;
-    const int n0 = nt * HBN_T;
+    const TileOfBlock tb = tile_of_block<HBM_T, HBN_T>(p.m, p.n);
+    if (!tb.has) return;
+    const int64_t m0 = tb.m0;
+    const int n0 = tb.n0;
 
     // DMA map: instruction q (0 = high plane, 1 = low plane) of wave w fills local rows [w*16, +16) of that plane of a
     // half-tile slot; lane i lands on local row r = w*16 + (i >> 2), physical chunk i & 3, and fetches logical chunk
@@ -319,12 +292,12 @@ __global__ __launch_bounds__(HTHREADS, 2) void k_f16x3_gemm_v3(const GemmArgs p)
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             if (u < 2) {
-                int64_t gr = m0 + (r >> 6) * 128 + (u == PS_A23 ? 64 : 0) + (r & 63);
+                int64_t gr = DCA_SLOT_ROW_A(m0, u, r);
                 gr = gr < p.m ? gr : p.m - 1;
                 src[u][0] = p.ah + gr * p.lda + c * 8;
                 src[u][1] = p.al + gr * p.lda + c * 8;
             } else {
-                int gn = n0 + (int)((r >> 5) * 64 + (u == PS_B1 ? 32 : 0) + (r & 31));
+                int gn = n0 + DCA_SLOT_COL_B(u, r);
                 gn = gn < p.n ? gn : p.n - 1;
                 src[u][0] = p.wh + (int64_t)gn * p.ldw + c * 8;
                 src[u][1] = p.wl + (int64_t)gn * p.ldw + c * 8;
@@ -335,8 +308,7 @@ __global__ __launch_bounds__(HTHREADS, 2) void k_f16x3_gemm_v3(const GemmArgs p)
 #pragma unroll
         for (int q = 0; q < 2; q++) {
             uint8_t* dst = lds + buf * PBUF3 + u * PSLOT3 + q * 8192 + w * 1024;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[u][q] + k0),
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+            lds_dma16(src[u][q] + k0, dst);
         }
     };
 
@@ -462,9 +434,6 @@ __global__ __launch_bounds__(HTHREADS, 2) void k_f16x3_gemm_v3(const GemmArgs p)
     }
     if (wm == 0) DCA_BAR();  // ... and the first waits for it here
 #undef DCA_MMA12
-#undef DCA_VMCNT
-#undef DCA_RD_DONE_BAR
-#undef DCA_BAR
 
     f16x3_epilogue(p, lds, acc, m0, n0, w, wm, wn, lane, l31, h);
 }
@@ -483,11 +452,13 @@ __global__ __launch_bounds__(HTHREADS, 2) void k_f16_gemm(const GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, l31 = lane & 31, h = lane >> 5;
     const int wm = w >> 2, wn = w & 3;
+    // tile_of_block(), written out: through the call one scalar register of the DMA setup gets another number, and this kernel's
+    // instructions are pinned from the first LDS-DMA on (profiles/dense_header_isa.txt)
     const int nNt = (p.n + HBN_T - 1) / HBN_T;
     const int64_t nMt = (p.m + HBM_T - 1) / HBM_T;
     const int64_t bid = blockIdx.x;
     const int64_t slot = bid >> 3;
-    const int64_t mt = (slot / nNt) * 8 + (bid & 7);  // the N tiles of one M tile sit on one XCD
+    const int64_t mt = (slot / nNt) * 8 + (bid & 7);
     const int nt = (int)(slot % nNt);
     if (mt >= nMt) return;
     const int64_t m0 = mt * HBM_T;
@@ -516,8 +487,7 @@ __global__ __launch_bounds__(HTHREADS, 2) void k_f16_gemm(const GemmArgs p) {
 #pragma unroll
         for (int q = 0; q < 8; q++) {
             uint8_t* dst = lds + stage * HSTAGE + (q >> 1) * HIMG + ((q & 1) * 8 + w) * 1024;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[q] + k0),
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+            lds_dma16(src[q] + k0, dst);
         }
     };
 
@@ -588,12 +558,7 @@ __global__ __launch_bounds__(256) void k_split_planes(const float* __restrict__ 
 // gradients span many binades.  So every operand is scaled by a POWER OF TWO chosen from its own magnitude before it is
 // split (exact: only the exponent moves), bringing its largest element into [2^14, 2^15): the low plane of everything
 // within 2^-10 of that is a normal fp16 number, what lies below is held to 2^-39 of the largest element.  The inverse scales
-// come back through the GEMM's per-column factor.
-__device__ __forceinline__ float pow2_scale_of(uint32_t amax_bits) {
-    const int ex = (int)((amax_bits >> 23) & 0xFFu) - 127;        // floor(log2 amax) for a normal amax
-    if (ex < -100 || ex > 100) return 1.0f;                       // zero / denormal / inf / nan: leave as is
-    return __uint_as_float((uint32_t)(127 + 14 - ex) << 23);
-}
+// come back through the GEMM's per-column factor.  (pow2_scale_of: dca_dense.h — the weight-gradient kernel undoes the same scales.)
 
 // max |x| over the matrix as float bits (non-negative floats order like their bit patterns); out zeroed by the host
 __global__ __launch_bounds__(256) void k_absmax_bits(const float* __restrict__ x, int64_t m, int64_t n, int64_t ld,
@@ -732,6 +697,17 @@ using namespace dca;
 
 static int g_gemm_variant = 3;
 
+// tile count, dynamic-LDS limit (once per device), launch: what dca_f16x3_gemm and dca_f16_gemm do once their arguments are accepted
+static int launch_gemm(const char* entry, void (*kernel)(GemmArgs), const char* kernel_name, const GemmArgs& p, void* stream) {
+    unsigned blocks;
+    if (int rc = tile_grid(entry, p.m, p.n, HBM_T, HBN_T, &blocks)) return rc;
+    static std::atomic<uint64_t> attr_devs{0};
+    if (int rc = dynamic_lds_once(attr_devs, {reinterpret_cast<const void*>(k_f16x3_gemm_v2), reinterpret_cast<const void*>(k_f16x3_gemm_v3),
+                                              reinterpret_cast<const void*>(k_f16_gemm)}, HLDS)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(HTHREADS), HLDS, (hipStream_t)stream, p);
+    return launch_check(kernel_name);
+}
+
 extern "C" {
 
 /* test hook: 2 = the LDS-DMA 256 x 256 kernel with two whole-K-step stages (the reference the race screens compare against),
@@ -753,18 +729,7 @@ int dca_f16x3_gemm(const void* a_h, const void* a_l, int64_t m, int k, int64_t l
     // the kernels leave with 16-byte row segments: 4-column-aligned outputs (every layer of the network has them)
     DCA_ARG(ldo % 4 == 0 && ((uintptr_t)out_h | (uintptr_t)out_l) % 8 == 0 && ((uintptr_t)x_out | (uintptr_t)skip) % 16 == 0);
     if (m == 0) return 0;
-    {   // the dynamic-LDS limit is a per-device function attribute: set it once for every device this process uses
-        static std::atomic<uint64_t> attr_devs{0};
-        int dev = 0;
-        DCA_HIP(hipGetDevice(&dev));
-        const uint64_t bit = 1ull << (dev & 63);
-        if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-            DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_f16x3_gemm_v2), hipFuncAttributeMaxDynamicSharedMemorySize, HLDS));
-            DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_f16x3_gemm_v3), hipFuncAttributeMaxDynamicSharedMemorySize, HLDS));
-            attr_devs.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    GemmArgs p;
+    GemmArgs p{};
     p.ah = reinterpret_cast<const _Float16*>(a_h);
     p.al = reinterpret_cast<const _Float16*>(a_l);
     p.wh = reinterpret_cast<const _Float16*>(w_h);
@@ -784,18 +749,7 @@ int dca_f16x3_gemm(const void* a_h, const void* a_l, int64_t m, int k, int64_t l
     p.ol = reinterpret_cast<_Float16*>(out_l);
     p.x_out = x_out;
     p.overflow = overflow;
-    const int64_t nMt = (m + HBM_T - 1) / HBM_T;
-    const int64_t nNt = (n + HBN_T - 1) / HBN_T;
-    const int64_t blocks = ((nMt + 7) / 8) * 8 * nNt;
-    if (blocks > 0x7FFFFFFFll) {
-        set_error("dca_f16x3_gemm: too many tiles");
-        return DCA_E_BADARG;
-    }
-    if (g_gemm_variant == 2)
-        hipLaunchKernelGGL(k_f16x3_gemm_v2, dim3((unsigned)blocks), dim3(HTHREADS), HLDS, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(k_f16x3_gemm_v3, dim3((unsigned)blocks), dim3(HTHREADS), HLDS, (hipStream_t)stream, p);
-    return launch_check("k_f16x3_gemm");
+    return launch_gemm(__func__, g_gemm_variant == 2 ? k_f16x3_gemm_v2 : k_f16x3_gemm_v3, "k_f16x3_gemm", p, stream);
 }
 
 int dca_f16_gemm(const void* a_h, int64_t m, int k, int64_t lda, const void* w_h, int n, int64_t ldw, const float* col_scale,
@@ -804,45 +758,20 @@ int dca_f16_gemm(const void* a_h, int64_t m, int k, int64_t lda, const void* w_h
     DCA_ARG(lda >= k && ldw >= k && lda % 8 == 0 && ldw % 8 == 0 && ldo >= n && ldo % 4 == 0);
     DCA_ARG(((uintptr_t)a_h | (uintptr_t)w_h | (uintptr_t)x_out) % 16 == 0);
     if (m == 0) return 0;
-    {   // the dynamic-LDS limit is a per-device function attribute: set it once for every device this process uses
-        static std::atomic<uint64_t> attr_devs{0};
-        int dev = 0;
-        DCA_HIP(hipGetDevice(&dev));
-        const uint64_t bit = 1ull << (dev & 63);
-        if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-            DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_f16_gemm), hipFuncAttributeMaxDynamicSharedMemorySize, HLDS));
-            attr_devs.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    GemmArgs p;
+    GemmArgs p{};  // (no low planes, no skip, no ReLU, no result planes)
     p.ah = reinterpret_cast<const _Float16*>(a_h);
-    p.al = nullptr;
     p.wh = reinterpret_cast<const _Float16*>(w_h);
-    p.wl = nullptr;
     p.col_scale = col_scale;
     p.bias = bias;
-    p.skip = nullptr;
     p.alpha = (float)alpha;
-    p.relu = 0;
     p.m = m;
     p.n = n;
     p.k = k;
     p.lda = lda;
     p.ldw = ldw;
     p.ldo = ldo;
-    p.oh = nullptr;
-    p.ol = nullptr;
     p.x_out = x_out;
-    p.overflow = nullptr;
-    const int64_t nMt = (m + HBM_T - 1) / HBM_T;
-    const int64_t nNt = (n + HBN_T - 1) / HBN_T;
-    const int64_t blocks = ((nMt + 7) / 8) * 8 * nNt;
-    if (blocks > 0x7FFFFFFFll) {
-        set_error("dca_f16_gemm: too many tiles");
-        return DCA_E_BADARG;
-    }
-    hipLaunchKernelGGL(k_f16_gemm, dim3((unsigned)blocks), dim3(HTHREADS), HLDS, (hipStream_t)stream, p);
-    return launch_check("k_f16_gemm");
+    return launch_gemm(__func__, k_f16_gemm, "k_f16_gemm", p, stream);
 }
 
 int dca_cast_planes_scaled(const float* x, int64_t m, int64_t n, int64_t ld, const uint32_t* amax_bits, void* out_h, int64_t ldo,

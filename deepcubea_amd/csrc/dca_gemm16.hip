@@ -15,22 +15,14 @@
 // waves as 2 (M) x 4 (N), each wave 4 x 2 tiles of v_mfma_f32_32x32x16_{bf16,f16} (128 accumulator VGPRs, 32 MFMAs per
 // K-step of 64).  The two operand images of a K-step (256 rows x 128 B each = 64 KB) are filled by
 // global_load_lds_dwordx4 (LDS-DMA: no staging registers) into one of TWO stages, so the loads of step t+1 fly under the
-// MFMAs of step t; one raw s_barrier per K-step.  A DMA instruction writes 64 lanes x 16 B linearly (8 rows of 128 B), so
-// the XOR swizzle that makes the ds_read_b128 fragment reads conflict-free — chunk ^ ((row >> 1) & 7) for 128-byte rows —
-// is applied to each lane's GLOBAL source address.  Workgroup ids are remapped so that the N tiles sharing an A tile run
-// on one XCD.
-#include <atomic>
+// MFMAs of step t; one raw s_barrier per K-step.  Tile map, the swizzle of the 128-byte LDS rows (applied to each lane's GLOBAL
+// source address), the LDS-DMA call, the half-tile slots, the number formats and the launchers' helpers are the shared ones of
+// dca_dense.h.
 #include <type_traits>
 
-#include "dca_common.h"
+#include "dca_dense.h"
 
 namespace dca {
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // The matrix instruction of all three kernels is v_mfma_f32_16x16x32_{bf16,f16} (round 6; it was 32x32x16 until then).  Both
 // shapes peak at the same rate, but on RANDOM operands the chip runs at its power limit and the 32x32x16 form draws more per
@@ -66,33 +58,6 @@ struct Gemm16Args {
     int64_t lda, ldw, ldo;
 };
 
-__device__ __forceinline__ uint32_t swz128(uint32_t row, uint32_t chunk) { return row * 128u + ((chunk ^ ((row >> 1) & 7u)) << 4); }
-
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-// round to nearest even (what torch does), NaN stays NaN: gfx950's v_cvt_pk_bf16_f32 — one instruction per two values where
-// the integer sequence (NaN test, bias add, shift) took six per value: ~700 VALU instructions per wave and tile
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
-    const f32x2_t v = {lo, hi};
-    const bf16x2_t b = __builtin_convertvector(v, bf16x2_t);
-    uint32_t u;
-    __builtin_memcpy(&u, &b, 4);
-    return u;
-}
-__device__ __forceinline__ uint16_t to_bf16(float f) { return (uint16_t)(pack_bf16x2(f, 0.f) & 0xFFFFu); }
-__device__ __forceinline__ float from_bf16(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint16_t to_f16(float f) {
-    const _Float16 h = (_Float16)f;
-    uint16_t r;
-    __builtin_memcpy(&r, &h, 2);
-    return r;
-}
-__device__ __forceinline__ float from_f16(uint16_t b) {
-    _Float16 h;
-    __builtin_memcpy(&h, &b, 2);
-    return (float)h;
-}
-
 // Layer tail, shared by both schedules.  Accumulator layout (activations = A operand): acc[ib][jb][r] = row ib * 16 + 4 g + r,
 // column jb * 16 + j of the wave's 128 x 64 (g = lane >> 4, j = lane & 15).  NJ counts the wave's 32-column groups.
 template <bool BF16, int NJ>
@@ -114,8 +79,8 @@ __device__ __forceinline__ void gemm16_epilogue(const Gemm16Args& p, uint8_t* ld
     const int c4 = (lane % LPR) * 4;  // this lane's 4 columns inside the wave's CW
     const int colg = n0 + wn * CW + c4;
     const bool full4 = colg + 3 < p.n;
-    auto cvt_in = [](uint16_t b) { return BF16 ? from_bf16(b) : from_f16(b); };
-    auto cvt_out = [](float f) { return BF16 ? to_bf16(f) : to_f16(f); };
+    auto cvt_in = [](uint16_t b) { return BF16 ? bf16_to_f32(b) : f16_to_f32(b); };
+    auto cvt_out = [](float f) { return BF16 ? f32_to_bf16(f) : f32_to_f16(f); };
     // (row block as a compile-time constant: left as a loop, the 4 x NJ accumulator blocks would be indexed dynamically —
     // the compiler then keeps all of them in scratch)
     auto rows32 = [&](auto ic) {
@@ -156,8 +121,8 @@ __device__ __forceinline__ void gemm16_epilogue(const Gemm16Args& p, uint8_t* ld
                 }
                 uint2 ov;
                 if constexpr (BF16) {
-                    ov.x = pack_bf16x2(u[0], u[1]);
-                    ov.y = pack_bf16x2(u[2], u[3]);
+                    ov.x = f32_to_bf16x2(u[0], u[1]);
+                    ov.y = f32_to_bf16x2(u[2], u[3]);
                 } else {
                     ov.x = (uint32_t)cvt_out(u[0]) | ((uint32_t)cvt_out(u[1]) << 16);
                     ov.y = (uint32_t)cvt_out(u[2]) | ((uint32_t)cvt_out(u[3]) << 16);
@@ -182,18 +147,13 @@ __device__ __forceinline__ void gemm16_epilogue(const Gemm16Args& p, uint8_t* ld
 template <bool BF16>
 __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16(const Gemm16Args p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    using frag_t = typename std::conditional<BF16, b16x8, h16x8>::type;
+    using frag_t = typename std::conditional<BF16, bf16x8, f16x8>::type;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, l31 = lane & 31, h = lane >> 5;
     const int wm = w >> 2, wn = w & 3;
-    const int nNt = (p.n + QBN - 1) / QBN;
-    const int64_t nMt = (p.m + QBM - 1) / QBM;
-    const int64_t bid = blockIdx.x;
-    const int64_t slot = bid >> 3;
-    const int64_t mt = (slot / nNt) * 8 + (bid & 7);  // the N tiles of one M tile sit on one XCD (workgroup b runs on XCD b % 8)
-    const int nt = (int)(slot % nNt);
-    if (mt >= nMt) return;
-    const int64_t m0 = mt * QBM;
-    const int n0 = nt * QBN;
+    const TileOfBlock tb = tile_of_block<QBM, QBN>(p.m, p.n);
+    if (!tb.has) return;
+    const int64_t m0 = tb.m0;
+    const int n0 = tb.n0;
 
     // LDS-DMA map: instruction q of wave w fills rows [rb*8, rb*8+8) of image q >> 2, rb = (q & 3) * 8 + w; lane i lands
     // on row i >> 3, physical chunk i & 7, and therefore fetches logical chunk (i & 7) ^ ((row >> 1) & 7).  Rows past the
@@ -218,8 +178,7 @@ __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16(const Gemm16Args p) {
 #pragma unroll
         for (int q = 0; q < 8; q++) {
             uint8_t* dst = lds + stage * QSTAGE + (q >> 2) * QIMG + ((q & 3) * 8 + w) * 1024;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[q] + k0),
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+            lds_dma16(src[q] + k0, dst);
         }
     };
 
@@ -295,26 +254,17 @@ __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16(const Gemm16Args p) {
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int PSLOT = 128 * 128;  // one half-tile: 128 rows x 128 B
 constexpr int PBUF = 4 * PSLOT;   // one K-tile: A01 | A23 | B0 | B1
-constexpr int PS_A01 = 0, PS_A23 = 1, PS_B0 = 2, PS_B1 = 3;
-
-#define DCA_BAR() asm volatile("s_barrier" ::: "memory")
-#define DCA_RD_DONE_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 template <bool BF16>
 __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16p(const Gemm16Args p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    using frag_t = typename std::conditional<BF16, b16x8, h16x8>::type;
+    using frag_t = typename std::conditional<BF16, bf16x8, f16x8>::type;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, l31 = lane & 31, h = lane >> 5;
     const int wm = w >> 2, wn = w & 3;
-    const int nNt = (p.n + QBN - 1) / QBN;
-    const int64_t nMt = (p.m + QBM - 1) / QBM;
-    const int64_t bid = blockIdx.x;
-    const int64_t slot = bid >> 3;
-    const int64_t mt = (slot / nNt) * 8 + (bid & 7);
-    const int nt = (int)(slot % nNt);
-    if (mt >= nMt) return;
-    const int64_t m0 = mt * QBM;
-    const int n0 = nt * QBN;
+    const TileOfBlock tb = tile_of_block<QBM, QBN>(p.m, p.n);
+    if (!tb.has) return;
+    const int64_t m0 = tb.m0;
+    const int n0 = tb.n0;
 
     // DMA map: instruction q (0, 1) of wave w fills local rows [(q*8 + w)*8, +8) of a half-tile slot; lane i lands on local
     // row r = that + (i >> 3), physical chunk i & 7, and fetches logical chunk (i & 7) ^ ((r >> 1) & 7) of the matrix row
@@ -327,11 +277,11 @@ __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16p(const Gemm16Args p) {
             const uint32_t r = (uint32_t)((q * 8 + w) * 8 + (lane >> 3));
             const uint32_t c = (uint32_t)(lane & 7) ^ ((r >> 1) & 7u);
             if (u < 2) {
-                int64_t gr = m0 + (r >> 6) * 128 + (u == PS_A23 ? 64 : 0) + (r & 63);
+                int64_t gr = DCA_SLOT_ROW_A(m0, u, r);
                 gr = gr < p.m ? gr : p.m - 1;
                 src[u][q] = p.a + gr * p.lda + c * 8;
             } else {
-                int gn = n0 + (int)((r >> 5) * 64 + (u == PS_B1 ? 32 : 0) + (r & 31));
+                int gn = n0 + DCA_SLOT_COL_B(u, r);
                 gn = gn < p.n ? gn : p.n - 1;
                 src[u][q] = p.w + (int64_t)gn * p.ldw + c * 8;
             }
@@ -340,8 +290,7 @@ __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16p(const Gemm16Args p) {
 #pragma unroll
         for (int q = 0; q < 2; q++) {
             uint8_t* dst = lds + buf * PBUF + u * PSLOT + (q * 8 + w) * 1024;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[u][q] + k0),
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+            lds_dma16(src[u][q] + k0, dst);
         }
     };
 
@@ -387,7 +336,6 @@ __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16p(const Gemm16Args p) {
         __builtin_amdgcn_s_setprio(0);                                                                                \
         __builtin_amdgcn_sched_barrier(0);                                                                            \
     } while (0)
-#define DCA_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 
     const int nk = p.k / QBK;
     // one K-tile; N1 / N2: tiles kt+1 / kt+2 exist (compile-time, so the steady-state body is branch-free).  On entry:
@@ -464,7 +412,6 @@ __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16p(const Gemm16Args p) {
         tile(kt, std::false_type{}, std::false_type{});
     }
     if (wm == 0) DCA_BAR();  // ... and the first waits for it here
-#undef DCA_VMCNT
 #undef DCA_MMA8
 
     gemm16_epilogue<BF16, 2>(p, lds, acc, m0, n0, w, wm, wn, lane, l31, h);
@@ -514,23 +461,23 @@ __device__ __forceinline__ int sigma16(int jb, int i) {
 template <bool BF16>
 __device__ __forceinline__ uint32_t pack16x2(float lo, float hi) {
     if constexpr (BF16)
-        return pack_bf16x2(lo, hi);
+        return f32_to_bf16x2(lo, hi);
     else
-        return (uint32_t)to_f16(lo) | ((uint32_t)to_f16(hi) << 16);
+        return (uint32_t)f32_to_f16(lo) | ((uint32_t)f32_to_f16(hi) << 16);
 }
 template <bool BF16>
 __device__ __forceinline__ float lo16(uint32_t v) {
     if constexpr (BF16)
         return __uint_as_float(v << 16);
     else
-        return from_f16((uint16_t)(v & 0xFFFFu));
+        return f16_to_f32((uint16_t)(v & 0xFFFFu));
 }
 template <bool BF16>
 __device__ __forceinline__ float hi16(uint32_t v) {
     if constexpr (BF16)
         return __uint_as_float(v & 0xFFFF0000u);
     else
-        return from_f16((uint16_t)(v >> 16));
+        return f16_to_f32((uint16_t)(v >> 16));
 }
 
 // Tail of a FULL tile.  tl: this wave's 4 KB exchange slice; rows cm0 + wm*128 .. +128, columns cn0 + wn*64 .. +64.
@@ -630,12 +577,12 @@ __device__ __forceinline__ void gemm16_tail_full(const Gemm16Args& p, uint8_t* t
 template <bool BF16, bool SKIP, bool BIAS>
 __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16s(const Gemm16Args p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    using frag_t = typename std::conditional<BF16, b16x8, h16x8>::type;
+    using frag_t = typename std::conditional<BF16, bf16x8, f16x8>::type;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, l31 = lane & 31, h = lane >> 5;
     const int wm = w >> 2, wn = w & 3;
-    const int nNt = p.n / QBN;  // (m, n: multiples of the tile)
+    const int nNt = p.n / QBN;  // (m, n: multiples of the tile: tile_of_block() without its roundings)
     const int64_t slot = blockIdx.x >> 3;
-    const int64_t m0 = ((slot / nNt) * 8 + (blockIdx.x & 7)) * QBM;  // the N tiles of one M tile sit on one XCD
+    const int64_t m0 = ((slot / nNt) * 8 + (blockIdx.x & 7)) * QBM;
     const int n0 = (int)(slot % nNt) * QBN;
     if (m0 >= p.m) return;
     const int nk = p.k / QBK;
@@ -649,7 +596,7 @@ __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16s(const Gemm16Args p) {
             const uint32_t r = (uint32_t)((q * 8 + w) * 8 + (lane >> 3));
             const uint32_t c = (uint32_t)(lane & 7) ^ ((r >> 1) & 7u);
             if (u < 2) {
-                const int64_t gr = m0 + (r >> 6) * 128 + (u == PS_A23 ? 64 : 0) + (r & 63);
+                const int64_t gr = DCA_SLOT_ROW_A(m0, u, r);
                 src[u][q] = p.a + gr * p.lda + c * 8;
             } else {
                 const int gn = n0 + (int)(r >> 5) * 64 + sigma16((u == PS_B1 ? 2 : 0) + (int)((r >> 4) & 1), (int)(r & 15));
@@ -660,8 +607,7 @@ __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16s(const Gemm16Args p) {
 #pragma unroll
         for (int q = 0; q < 2; q++) {
             uint8_t* dst = lds + buf * PBUF + u * PSLOT + (q * 8 + w) * 1024;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[u][q] + k0),
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+            lds_dma16(src[u][q] + k0, dst);
         }
     };
     const int g4 = lane >> 4, j16 = lane & 15;
@@ -697,7 +643,6 @@ __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16s(const Gemm16Args p) {
         __builtin_amdgcn_s_setprio(0);                                                                                \
         __builtin_amdgcn_sched_barrier(0);                                                                            \
     } while (0)
-#define DCA_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
     auto tile = [&](int kt, auto n1c, auto n2c) {  // one K-tile: identical to variant 2's
         constexpr bool N1 = decltype(n1c)::value, N2 = decltype(n2c)::value;
         const int b = kt & 1;
@@ -773,7 +718,6 @@ __global__ __launch_bounds__(QTHREADS, 2) void k_gemm16s(const Gemm16Args p) {
     if (wm == 0) DCA_BAR();  // ... and the first waits for it here: nobody reads the operand slots any more
     // the tail's piece exchange uses the first 32 KB of the (now idle) operand slots, 4 KB per wave
     gemm16_tail_full<BF16, SKIP, true, BIAS>(p, lds + w * 4096, acc, m0, n0, wm, wn, l31, h);
-#undef DCA_VMCNT
 #undef DCA_MMA8
 }
 
@@ -812,25 +756,24 @@ int dca_gemm16(const void* a, int64_t m, int k, int64_t lda, const void* w, int 
     DCA_ARG(lda >= k && ldw >= k && lda % 8 == 0 && ldw % 8 == 0 && ldo >= n && ldo % 4 == 0);
     DCA_ARG(((uintptr_t)a | (uintptr_t)w) % 16 == 0 && ((uintptr_t)out | (uintptr_t)skip) % 8 == 0);
     if (m > 0) {  // `out` may alias `skip`, never the operand (its tiles are re-read while other tiles' epilogues write)
-        const uintptr_t a0 = (uintptr_t)a, a1 = a0 + ((size_t)(m - 1) * (size_t)lda + (size_t)k) * 2;
-        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + ((size_t)(m - 1) * (size_t)ldo + (size_t)n) * 2;
+        const auto [a0, a1] = rows_range(a, m, k, lda, 2);
+        const auto [o0, o1] = rows_range(out, m, n, ldo, 2);
         DCA_ARG(!(o0 < a1 && a0 < o1));
     }
     if (m == 0) return 0;
-    {   // the dynamic-LDS limit is a per-device function attribute: set it once for every device this process uses
-        static std::atomic<uint64_t> attr_devs{0};
-        int dev = 0;
-        DCA_HIP(hipGetDevice(&dev));
-        const uint64_t bit = 1ull << (dev & 63);
-        if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-            DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm16<true>), hipFuncAttributeMaxDynamicSharedMemorySize, QLDS));
-            DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm16<false>), hipFuncAttributeMaxDynamicSharedMemorySize, QLDS));
-            DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm16p<true>), hipFuncAttributeMaxDynamicSharedMemorySize, QLDS));
-            DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm16p<false>), hipFuncAttributeMaxDynamicSharedMemorySize, QLDS));
-            for (int f = 0; f < 8; f++) DCA_HIP(hipFuncSetAttribute(lean_kernel(f & 1, (f >> 1) & 1, f >> 2), hipFuncAttributeMaxDynamicSharedMemorySize, QLDS));
-            attr_devs.fetch_or(bit, std::memory_order_release);
-        }
-    }
+    // One check of the whole shape bounds every part launched below — the lean part and both strips: the count is monotone in m
+    // and in n.  (It refuses slightly earlier than the parts would, at more than 2^31 tiles: no real buffer reaches that size.)
+    const char* const entry = __func__;
+    unsigned blocks;
+    if (int rc = tile_grid(entry, m, n, QBM, QBN, &blocks)) return rc;
+    static std::atomic<uint64_t> attr_devs{0};
+    if (int rc = dynamic_lds_once(attr_devs,
+                                  {reinterpret_cast<const void*>(k_gemm16<true>), reinterpret_cast<const void*>(k_gemm16<false>),
+                                   reinterpret_cast<const void*>(k_gemm16p<true>), reinterpret_cast<const void*>(k_gemm16p<false>),
+                                   lean_kernel(0, 0, 0), lean_kernel(1, 0, 0), lean_kernel(0, 1, 0), lean_kernel(1, 1, 0),
+                                   lean_kernel(0, 0, 1), lean_kernel(1, 0, 1), lean_kernel(0, 1, 1), lean_kernel(1, 1, 1)},
+                                  QLDS))
+        return rc;
     Gemm16Args p;
     p.a = reinterpret_cast<const uint16_t*>(a);
     p.w = reinterpret_cast<const uint16_t*>(w);
@@ -847,14 +790,8 @@ int dca_gemm16(const void* a, int64_t m, int k, int64_t lda, const void* w, int 
     hipStream_t s = (hipStream_t)stream;
     // one workgroup per 256 x 256 tile, any shape, any form (variants 1, 2)
     auto launch_generic = [&](const Gemm16Args& q, int variant) -> int {
-        const int64_t nMt = (q.m + QBM - 1) / QBM;
-        const int64_t nNt = (q.n + QBN - 1) / QBN;
-        const int64_t blocks = ((nMt + 7) / 8) * 8 * nNt;
-        if (blocks > 0x7FFFFFFFll) {
-            set_error("dca_gemm16: too many tiles");
-            return DCA_E_BADARG;
-        }
-        const dim3 grid((unsigned)blocks), block(QTHREADS);
+        if (int rc = tile_grid(entry, q.m, q.n, QBM, QBN, &blocks)) return rc;
+        const dim3 grid(blocks), block(QTHREADS);
         if (variant == 1) {
             if (dtype == DCA_DT_BF16)
                 hipLaunchKernelGGL(k_gemm16<true>, grid, block, QLDS, s, q);
@@ -883,14 +820,9 @@ int dca_gemm16(const void* a, int64_t m, int k, int64_t lda, const void* w, int 
         Gemm16Args q = p;
         q.m = mf;
         q.n = nf;
-        const int64_t nMt = mf / QBM, nNt = nf / QBN;
-        const int64_t blocks = ((nMt + 7) / 8) * 8 * nNt;
-        if (blocks > 0x7FFFFFFFll) {
-            set_error("dca_gemm16: too many tiles");
-            return DCA_E_BADARG;
-        }
+        if (int rc = tile_grid(entry, mf, nf, QBM, QBN, &blocks)) return rc;
         void* kargs[] = {&q};
-        DCA_HIP(hipLaunchKernel(lean_kernel(dtype == DCA_DT_BF16, skip != nullptr, bias != nullptr), dim3((unsigned)blocks), dim3(QTHREADS), kargs, QLDS, s));
+        DCA_HIP(hipLaunchKernel(lean_kernel(dtype == DCA_DT_BF16, skip != nullptr, bias != nullptr), dim3(blocks), dim3(QTHREADS), kargs, QLDS, s));
     }
     auto strip = [&](int64_t r0, int64_t rows, int c0, int cols) -> int {  // rows [r0, r0 + rows) x columns [c0, c0 + cols)
         if (rows <= 0 || cols <= 0) return 0;

@@ -11,28 +11,25 @@
 //
 // Tile and schedule are those of csrc/dca_gemm16.hip variant 2 (the derivation and the RAW / WAR argument are written out
 // there): 256 x 256 outputs per workgroup, 8 waves as 2 (M) x 4 (N), the two wave rows one barrier apart (one multiplies while
-// the other reads fragments and issues DMA), a K-tile of 128 BYTES per row — the same 128-byte LDS rows, the same XOR swizzle
-// on the DMA source address, the same four 16 KB half-tile slots per K-tile and the same counted s_waitcnt vmcnt(10) — only a
+// the other reads fragments and issues DMA), a K-tile of 128 BYTES per row — tile map, 128-byte LDS rows and their swizzle, the
+// four 16 KB half-tile slots per K-tile and the counted waits are the shared ones of dca_dense.h — only a
 // K-tile is now 128 deep: per phase a wave issues 4 MFMAs of 32x32x64 (16 passes each) where the bf16 kernel issues 8 of
 // 32x32x16 (8 passes), i.e. the same matrix-pipe time for twice the products.  A lane's 32-byte MFMA operand is two 16-byte
 // chunks of its row (lane half h of K-step t takes chunks 4t + 2h and 4t + 2h + 1); A and B use the same chunk -> byte
 // order, which is all the instruction needs (it pairs byte b of the A lane with byte b of the B lane of the same half).
-#include <atomic>
 #include <type_traits>
 
-#include "dca_common.h"
+#include "dca_dense.h"
 
 namespace dca {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int EBM = 256, EBN = 256, EBK = 128, ETHREADS = 512;
 constexpr int ESLOT = 128 * 128;  // one half-tile: 128 rows x 128 B
 constexpr int EBUF = 4 * ESLOT;   // one K-tile: A01 | A23 | B0 | B1
 constexpr int ELDS = 2 * EBUF;    // 128 KB
-constexpr int ES_A01 = 0, ES_A23 = 1, ES_B0 = 2, ES_B1 = 3;
 
 struct Gemm8Args {
     const uint8_t* a;    // [m, lda] e4m3
@@ -76,37 +73,6 @@ __device__ __forceinline__ uint32_t e8m0_of_amax(float amax, float& inv) {
     inv = __uint_as_float((uint32_t)(127 - e) << 23);  // 2^-e
     return (uint32_t)(e + 127);
 }
-
-__device__ __forceinline__ uint32_t swz128b(uint32_t row, uint32_t chunk) { return row * 128u + ((chunk ^ ((row >> 1) & 7u)) << 4); }
-
-typedef __bf16 g8_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float g8_f32x2 __attribute__((ext_vector_type(2)));
-// round to nearest even, NaN stays NaN: gfx950's v_cvt_pk_bf16_f32, two values per instruction (the integer sequence it
-// replaces took six per value — a visible share of the layer tail, csrc/dca_gemm16.hip)
-__device__ __forceinline__ uint32_t f32_to_bf16x2(float lo, float hi) {
-    const g8_f32x2 v = {lo, hi};
-    const g8_bf16x2 b = __builtin_convertvector(v, g8_bf16x2);
-    uint32_t u;
-    __builtin_memcpy(&u, &b, 4);
-    return u;
-}
-__device__ __forceinline__ uint16_t f32_to_bf16(float f) { return (uint16_t)(f32_to_bf16x2(f, 0.f) & 0xFFFFu); }
-__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-
-// four floats -> four e4m3 bytes (round to nearest even, saturating at +-448: e4m3fn has no infinity)
-__device__ __forceinline__ uint32_t pack_e4m3(float a, float b, float c, float d) {
-    a = fminf(fmaxf(a, -448.f), 448.f);
-    b = fminf(fmaxf(b, -448.f), 448.f);
-    c = fminf(fmaxf(c, -448.f), 448.f);
-    d = fminf(fmaxf(d, -448.f), 448.f);
-    uint32_t r = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-    r = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, (int)r, true);
-    return r;
-}
-
-#define DCA_BAR() asm volatile("s_barrier" ::: "memory")
-#define DCA_RD_DONE_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#define DCA_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 
 // Layer tail.  MODE < 0: any shape, any form, block-scaled results included, every option tested at run time.  MODE >= 0 (bit 0
 // skip, bit 1 bf16 output, bit 2 e4m3 output with the static scale, bit 3 bias): the same tail compiled for ONE of the network's
@@ -218,15 +184,10 @@ __global__ __launch_bounds__(ETHREADS, 2) void k_gemm8(const Gemm8Args p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, l31 = lane & 31, h = lane >> 5;
     const int wm = w >> 2, wn = w & 3;
-    const int nNt = (p.n + EBN - 1) / EBN;
-    const int64_t nMt = (p.m + EBM - 1) / EBM;
-    const int64_t bid = blockIdx.x;
-    const int64_t slot = bid >> 3;
-    const int64_t mt = (slot / nNt) * 8 + (bid & 7);  // the N tiles of one M tile sit on one XCD (workgroup b runs on XCD b % 8)
-    const int nt = (int)(slot % nNt);
-    if (mt >= nMt) return;
-    const int64_t m0 = mt * EBM;
-    const int n0 = nt * EBN;
+    const TileOfBlock tb = tile_of_block<EBM, EBN>(p.m, p.n);
+    if (!tb.has) return;
+    const int64_t m0 = tb.m0;
+    const int n0 = tb.n0;
 
     // DMA map: instruction q (0, 1) of wave w fills local rows [(q*8 + w)*8, +8) of a half-tile slot; lane i lands on local
     // row r = that + (i >> 3), physical chunk i & 7, and fetches logical chunk (i & 7) ^ ((r >> 1) & 7) of the matrix row
@@ -239,11 +200,11 @@ __global__ __launch_bounds__(ETHREADS, 2) void k_gemm8(const Gemm8Args p) {
             const uint32_t r = (uint32_t)((q * 8 + w) * 8 + (lane >> 3));
             const uint32_t c = (uint32_t)(lane & 7) ^ ((r >> 1) & 7u);
             if (u < 2) {
-                int64_t gr = m0 + (r >> 6) * 128 + (u == ES_A23 ? 64 : 0) + (r & 63);
+                int64_t gr = DCA_SLOT_ROW_A(m0, u, r);
                 gr = gr < p.m ? gr : p.m - 1;
                 src[u][q] = p.a + gr * p.lda + c * 16;
             } else {
-                int gn = n0 + (int)((r >> 5) * 64 + (u == ES_B1 ? 32 : 0) + (r & 31));
+                int gn = n0 + DCA_SLOT_COL_B(u, r);
                 gn = gn < p.n ? gn : p.n - 1;
                 src[u][q] = p.w + (int64_t)gn * p.ldw + c * 16;
             }
@@ -252,8 +213,7 @@ __global__ __launch_bounds__(ETHREADS, 2) void k_gemm8(const Gemm8Args p) {
 #pragma unroll
         for (int q = 0; q < 2; q++) {
             uint8_t* dst = lds + buf * EBUF + u * ESLOT + (q * 8 + w) * 1024;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[u][q] + k0),
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+            lds_dma16(src[u][q] + k0, dst);
         }
     };
 
@@ -270,7 +230,7 @@ __global__ __launch_bounds__(ETHREADS, 2) void k_gemm8(const Gemm8Args p) {
 #pragma unroll
     for (int ks = 0; ks < 2; ks++)
 #pragma unroll
-        for (int j = 0; j < 2; j++) foff[ks][j] = swz128b((uint32_t)l31, 4u * ks + 2u * (uint32_t)h + j);
+        for (int j = 0; j < 2; j++) foff[ks][j] = swz128((uint32_t)l31, 4u * ks + 2u * (uint32_t)h + j);
     const uint32_t a_row0 = (uint32_t)wm * 64u * 128u;  // A slots: this wave row's 64 local rows
     const uint32_t b_row0 = (uint32_t)wn * 32u * 128u;  // B slots: this wave column's 32 local rows
 
@@ -292,7 +252,7 @@ __global__ __launch_bounds__(ETHREADS, 2) void k_gemm8(const Gemm8Args p) {
 #pragma unroll
             for (int ks = 0; ks < 2; ks++) av[ii][ks] = frag(base + u * ESLOT + a_row0 + ii * 4096, ks);
             if constexpr (MXIN)  // tile row = wm * 128 + (u == A23 ? 64 : 0) + ii * 32 + l31
-                sa[ii] = *reinterpret_cast<const uint16_t*>(lsc + sc_row0 + (uint32_t)((u == ES_A23 ? 64 : 0) + ii * 32) * SK + 2u * (uint32_t)kt);
+                sa[ii] = *reinterpret_cast<const uint16_t*>(lsc + sc_row0 + (uint32_t)((u == PS_A23 ? 64 : 0) + ii * 32) * SK + 2u * (uint32_t)kt);
         }
     };
     auto read_b = [&](const uint8_t* base, int u, i32x8 (&wv)[2]) {
@@ -327,10 +287,10 @@ __global__ __launch_bounds__(ETHREADS, 2) void k_gemm8(const Gemm8Args p) {
         const int b = kt & 1;
         const uint8_t* base = lds + b * EBUF;
         // phase 1: (A01, B0); restage A23 of kt+1; retire B1 of kt
-        read_b(base, ES_B0, wv0);
-        read_a(base, ES_A01, kt);
+        read_b(base, PS_B0, wv0);
+        read_a(base, PS_A01, kt);
         if constexpr (N1) {
-            issue(ES_A23, b ^ 1, (kt + 1) * EBK);
+            issue(PS_A23, b ^ 1, (kt + 1) * EBK);
             DCA_VMCNT(10);
         } else {
             DCA_VMCNT(2);
@@ -339,9 +299,9 @@ __global__ __launch_bounds__(ETHREADS, 2) void k_gemm8(const Gemm8Args p) {
         DCA_MMA4(0, 0, wv0);
         DCA_BAR();
         // phase 2: (A01, B1); restage A01 of kt+2; retire A23 of kt
-        read_b(base, ES_B1, wv1);
+        read_b(base, PS_B1, wv1);
         if constexpr (N2) {
-            issue(ES_A01, b, (kt + 2) * EBK);
+            issue(PS_A01, b, (kt + 2) * EBK);
             DCA_VMCNT(10);
         } else if constexpr (N1) {
             DCA_VMCNT(8);
@@ -352,14 +312,14 @@ __global__ __launch_bounds__(ETHREADS, 2) void k_gemm8(const Gemm8Args p) {
         DCA_MMA4(0, 1, wv1);
         DCA_BAR();
         // phase 3: (A23, B1); restage B0 of kt+2
-        read_a(base, ES_A23, kt);
-        if constexpr (N2) issue(ES_B0, b, (kt + 2) * EBK);
+        read_a(base, PS_A23, kt);
+        if constexpr (N2) issue(PS_B0, b, (kt + 2) * EBK);
         DCA_RD_DONE_BAR();
         DCA_MMA4(2, 1, wv1);
         DCA_BAR();
         // phase 4: (A23, B0) from registers; restage B1 of kt+2; retire A01, B0 of kt+1
         if constexpr (N2) {
-            issue(ES_B1, b, (kt + 2) * EBK);
+            issue(PS_B1, b, (kt + 2) * EBK);
             DCA_VMCNT(10);
         } else if constexpr (N1) {
             DCA_VMCNT(4);
@@ -388,14 +348,14 @@ __global__ __launch_bounds__(ETHREADS, 2) void k_gemm8(const Gemm8Args p) {
             asm volatile("global_load_dword %0, %1, off" : "=v"(scw[j]) : "v"(src_sc) : "memory");
         }
     }
-    issue(ES_A01, 0, 0);
-    issue(ES_B0, 0, 0);
-    issue(ES_B1, 0, 0);
-    issue(ES_A23, 0, 0);
+    issue(PS_A01, 0, 0);
+    issue(PS_B0, 0, 0);
+    issue(PS_B1, 0, 0);
+    issue(PS_A23, 0, 0);
     if (nk > 1) {
-        issue(ES_A01, 1, EBK);
-        issue(ES_B0, 1, EBK);
-        issue(ES_B1, 1, EBK);
+        issue(PS_A01, 1, EBK);
+        issue(PS_B0, 1, EBK);
+        issue(PS_B1, 1, EBK);
     }
     if constexpr (MXIN) {
         const uint32_t words = 256u * SK / 4u;
@@ -450,9 +410,6 @@ __global__ __launch_bounds__(ETHREADS, 2) void k_gemm8(const Gemm8Args p) {
         }
     }
 }
-#undef DCA_VMCNT
-#undef DCA_RD_DONE_BAR
-#undef DCA_BAR
 
 // bf16 / fp32 [m, n] -> e4m3(sat(x * scale)): the entry into an fp8 layer for activations that did not come out of an fp8 epilogue
 template <typename T>
@@ -479,6 +436,17 @@ __global__ __launch_bounds__(256) void k_quant_e4m3(const T* __restrict__ x, int
 
 using namespace dca;
 
+// tile count, dynamic-LDS limit (once per device), launch: what dca_gemm8 and dca_gemm8_mx do once their arguments are accepted
+template <bool MXIN>
+static int launch_gemm8(const char* entry, const Gemm8Args& p, int lds_bytes, void* stream) {
+    unsigned blocks;
+    if (int rc = tile_grid(entry, p.m, p.n, EBM, EBN, &blocks)) return rc;
+    static std::atomic<uint64_t> attr_devs{0};
+    if (int rc = dynamic_lds_once(attr_devs, {reinterpret_cast<const void*>(k_gemm8<MXIN>)}, MXIN ? ELDS + 256 * (8192 / 64) : ELDS)) return rc;
+    hipLaunchKernelGGL(k_gemm8<MXIN>, dim3(blocks), dim3(ETHREADS), lds_bytes, (hipStream_t)stream, p);
+    return launch_check(MXIN ? "k_gemm8<mx>" : "k_gemm8");
+}
+
 extern "C" {
 
 int dca_gemm8(const void* a, int64_t m, int k, int64_t lda, const void* w, int n, int64_t ldw, const float* scale, const float* bias,
@@ -488,27 +456,11 @@ int dca_gemm8(const void* a, int64_t m, int k, int64_t lda, const void* w, int n
     DCA_ARG(((uintptr_t)a | (uintptr_t)w) % 16 == 0);
     DCA_ARG((!out16 && !skip) || (ldo16 >= n && ldo16 % 4 == 0 && ((uintptr_t)out16 | (uintptr_t)skip) % 8 == 0));
     DCA_ARG(!out8 || (ldo8 >= n && ldo8 % 4 == 0 && (uintptr_t)out8 % 4 == 0 && out8_scale > 0.0));
-    {   // the A tiles are re-read through LDS-DMA while the epilogues of other tiles write: no output may overlap the operand
-        const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (m > 0 ? (size_t)(m - 1) * (size_t)lda + (size_t)k : 0);
-        auto overlaps = [&](const void* o, int64_t ld, size_t esz) {
-            if (!o || m == 0) return false;
-            const uintptr_t o0 = (uintptr_t)o, o1 = o0 + ((size_t)(m - 1) * (size_t)ld + (size_t)n) * esz;
-            return o0 < a1 && a0 < o1;
-        };
-        DCA_ARG(!overlaps(out8, ldo8, 1) && !overlaps(out16, ldo16, 2));
-    }
+    const ByteRange operand = rows_range(a, m, k, lda, 1);  // no output may overlap it (dca_dense.h)
+    auto overlaps = [&](const void* o, int64_t ld, size_t esz) { return o && ranges_overlap(operand, rows_range(o, m, n, ld, esz)); };
+    DCA_ARG(!overlaps(out8, ldo8, 1) && !overlaps(out16, ldo16, 2));
     if (m == 0) return 0;
-    {   // the dynamic-LDS limit is a per-device function attribute: set it once for every device this process uses
-        static std::atomic<uint64_t> attr_devs{0};
-        int dev = 0;
-        DCA_HIP(hipGetDevice(&dev));
-        const uint64_t bit = 1ull << (dev & 63);
-        if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-            DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm8<false>), hipFuncAttributeMaxDynamicSharedMemorySize, ELDS));
-            attr_devs.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    Gemm8Args p;
+    Gemm8Args p{};  // (the block-scale fields stay null / 0)
     p.a = reinterpret_cast<const uint8_t*>(a);
     p.w = reinterpret_cast<const uint8_t*>(w);
     p.scale = scale;
@@ -525,20 +477,7 @@ int dca_gemm8(const void* a, int64_t m, int k, int64_t lda, const void* w, int n
     p.ldw = ldw;
     p.ldo16 = ldo16;
     p.ldo8 = ldo8;
-    const int64_t nMt = (m + EBM - 1) / EBM;
-    const int64_t nNt = (n + EBN - 1) / EBN;
-    const int64_t blocks = ((nMt + 7) / 8) * 8 * nNt;
-    if (blocks > 0x7FFFFFFFll) {
-        set_error("dca_gemm8: too many tiles");
-        return DCA_E_BADARG;
-    }
-    p.a_scale = nullptr;
-    p.ld_asc = 0;
-    p.out8_sc = nullptr;
-    p.ld_osc = 0;
-    p.out8_scale_ptr_set = 0;
-    hipLaunchKernelGGL(k_gemm8<false>, dim3((unsigned)blocks), dim3(ETHREADS), ELDS, (hipStream_t)stream, p);
-    return launch_check("k_gemm8");
+    return launch_gemm8<false>(__func__, p, ELDS, stream);
 }
 
 int dca_gemm8_mx(const void* a, const void* a_scale, int64_t m, int k, int64_t lda, int64_t ld_asc, const void* w, int n, int64_t ldw,
@@ -550,29 +489,11 @@ int dca_gemm8_mx(const void* a, const void* a_scale, int64_t m, int k, int64_t l
     DCA_ARG((!out16 && !skip) || (ldo16 >= n && ldo16 % 4 == 0 && ((uintptr_t)out16 | (uintptr_t)skip) % 8 == 0));
     DCA_ARG((out8 != nullptr) == (out8_scale != nullptr));
     DCA_ARG(!out8 || (ldo8 >= n && ldo8 % 4 == 0 && (uintptr_t)out8 % 4 == 0 && n % 64 == 0 && ld_osc >= n / 64));
-    {
-        const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (m > 0 ? (size_t)(m - 1) * (size_t)lda + (size_t)k : 0);
-        auto overlaps = [&](const void* o, int64_t ld, size_t esz) {
-            if (!o || m == 0) return false;
-            const uintptr_t o0 = (uintptr_t)o, o1 = o0 + ((size_t)(m - 1) * (size_t)ld + (size_t)n) * esz;
-            return o0 < a1 && a0 < o1;
-        };
-        DCA_ARG(!overlaps(out8, ldo8, 1) && !overlaps(out16, ldo16, 2) && out8_scale != a_scale);
-    }
+    const ByteRange operand = rows_range(a, m, k, lda, 1);
+    auto overlaps = [&](const void* o, int64_t ld, size_t esz) { return o && ranges_overlap(operand, rows_range(o, m, n, ld, esz)); };
+    DCA_ARG(!overlaps(out8, ldo8, 1) && !overlaps(out16, ldo16, 2) && out8_scale != a_scale);
     if (m == 0) return 0;
-    const int lds_bytes = ELDS + 256 * (k / 64);
-    {
-        static std::atomic<uint64_t> attr_devs{0};
-        int dev = 0;
-        DCA_HIP(hipGetDevice(&dev));
-        const uint64_t bit = 1ull << (dev & 63);
-        if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-            DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm8<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        ELDS + 256 * (8192 / 64)));
-            attr_devs.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    Gemm8Args p;
+    Gemm8Args p{};
     p.a = reinterpret_cast<const uint8_t*>(a);
     p.w = reinterpret_cast<const uint8_t*>(w);
     p.scale = w_scale;
@@ -594,15 +515,7 @@ int dca_gemm8_mx(const void* a, const void* a_scale, int64_t m, int k, int64_t l
     p.out8_sc = reinterpret_cast<uint8_t*>(out8_scale);
     p.ld_osc = ld_osc;
     p.out8_scale_ptr_set = out8_scale != nullptr ? 1 : 0;
-    const int64_t nMt = (m + EBM - 1) / EBM;
-    const int64_t nNt = (n + EBN - 1) / EBN;
-    const int64_t blocks = ((nMt + 7) / 8) * 8 * nNt;
-    if (blocks > 0x7FFFFFFFll) {
-        set_error("dca_gemm8_mx: too many tiles");
-        return DCA_E_BADARG;
-    }
-    hipLaunchKernelGGL(k_gemm8<true>, dim3((unsigned)blocks), dim3(ETHREADS), lds_bytes, (hipStream_t)stream, p);
-    return launch_check("k_gemm8<mx>");
+    return launch_gemm8<true>(__func__, p, ELDS + 256 * (k / 64), stream);
 }
 
 int dca_quant_e4m3(const void* x, int dtype, int64_t m, int64_t n, int64_t ld, double scale, void* out, int64_t ldo, void* stream) {

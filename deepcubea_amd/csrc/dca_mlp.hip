@@ -18,12 +18,9 @@
 // ([plane][k/8][column][8] => 512 contiguous bytes per half-wave, conflict-free), then the workgroup walks over row
 // chunks of 512 (64 rows per wave = 2x2 tiles of v_mfma_f32_32x32x16_bf16, 64 accumulator VGPRs).  Per K-step a wave
 // issues 4*P MFMAs for 2 A-fragment rebuilds and 2*P ds_read_b128: the MFMA pipe is the limiter.
-#include "dca_common.h"
+#include "dca_dense.h"
 
 namespace dca {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int kL1Threads = 512;  // 8 waves = 2 per SIMD: one wave's mask build / epilogue hides under the other's MFMAs
 constexpr int kL1Rows = kL1Threads;  // rows per chunk (64 per wave)
@@ -42,16 +39,6 @@ struct L1Geo {
     static constexpr int CHKC = CH_STEPS * 2;     // 16-byte weight chunks per LDS chunk and plane
     static constexpr int MWC = (CH_STEPS * 16 + 31) / 32;  // one-hot mask words per row and chunk
 };
-
-__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {  // gfx950's v_cvt_pk_bf16_f32 (round to nearest even)
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const f2 v = {f, 0.f};
-    const bf2 b = __builtin_convertvector(v, bf2);
-    uint32_t u;
-    __builtin_memcpy(&u, &b, 4);
-    return (uint16_t)(u & 0xFFFFu);
-}
 
 template <int D, int DEPTH, int P,
           int OUT /*0 f32, 1 f16, 2 bf16, (3 unused,) 4 two fp16 planes (high, then low at +m*ldo),
@@ -232,11 +219,7 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
                             for (int e = 0; e < 4; e++) {
                                 const float a0 = u[2 * e], a1 = u[2 * e + 1];
                                 if constexpr (OUT == 2) {
-                                    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-                                    typedef float f2 __attribute__((ext_vector_type(2)));
-                                    const f2 vv = {a0, a1};
-                                    const bf2 bb2 = __builtin_convertvector(vv, bf2);
-                                    __builtin_memcpy(&w[e], &bb2, 4);
+                                    w[e] = f32_to_bf16x2(a0, a1);
                                 } else {
                                     _Float16 h0 = (_Float16)a0, h1 = (_Float16)a1;
                                     if (OUT == 4 && pass == 1) {  // the low plane: what the high halves left over
@@ -295,7 +278,7 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
                             if (relu) v = fmaxf(v, 0.f);
                             uint32_t w;
                             if constexpr (OUT == 2) {
-                                w = f32_to_bf16_rne(v);
+                                w = f32_to_bf16(v);
                             } else if constexpr (OUT == 5) {  // e4m3fn has no infinity: saturate at +-448
                                 w = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(v, -448.f), 448.f), 0.f, 0, false) & 0xFFu;
                             } else if constexpr (OUT == 6) {  // quantised after the transposition, once the row's block scale is known
@@ -376,7 +359,7 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
                         else if constexpr (OUT == 1)
                             reinterpret_cast<_Float16*>(out)[r * ldo + col] = (_Float16)v;
                         else if constexpr (OUT == 2)
-                            reinterpret_cast<uint16_t*>(out)[r * ldo + col] = f32_to_bf16_rne(v);
+                            reinterpret_cast<uint16_t*>(out)[r * ldo + col] = f32_to_bf16(v);
                         else {  // the two fp16 planes dca_f16x3_gemm reads: high halves, then (m*ldo further) low halves
                             _Float16* q = reinterpret_cast<_Float16*>(out) + r * ldo + col;
                             if (!(fabsf(v) <= 60000.0f) && overflow) *overflow = 1;

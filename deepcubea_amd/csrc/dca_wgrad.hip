@@ -29,19 +29,11 @@
 // Measured (profiles/wgrad_probe.txt, batch 10 000, library fp32 GEMM / products 3 / products 1, ms): 5000 x 324 0.33 / 0.17 / 0.10,
 // 1000 x 5000 0.91 / 0.40 / 0.23, 1000 x 1000 0.17 / 0.11 / 0.08; the fold is 6-8 us.  Built, measured, removed: two LDS buffers and
 // one barrier per K-tile — 0.44 against 0.40 ms at 1000 x 5000: the barriers are not what bounds it.
-#include "dca_common.h"
+#include "dca_dense.h"
 
 namespace dca {
 
-// every pointer a kernel dereferences is a global-memory pointer (global_* accesses on vmcnt alone, never flat_*); only the device
-// pass sees the address space
-#if defined(__HIP_DEVICE_COMPILE__)
-#define DCA_GLOBAL __attribute__((address_space(1)))
-#define DCA_LDS __attribute__((address_space(3)))
-#else
-#define DCA_GLOBAL
-#define DCA_LDS
-#endif
+// every pointer a kernel dereferences is a global-memory pointer (global_* accesses on vmcnt alone, never flat_*: DCA_GLOBAL)
 template <class T>
 using gp = T DCA_GLOBAL*;
 
@@ -52,20 +44,11 @@ constexpr int WG_PLANE_BYTES = WG_KT * 256;
 constexpr int64_t WG_MIN_SLICE = 256;     // no slice shorter than this many rows (8 K-tiles)
 constexpr int WG_FILL = 256;              // workgroups that fill the machine (one per CU)
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef short s8v __attribute__((ext_vector_type(8)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));  // 16 bytes of a plane row
 
-// the scale dca_split_planes_scaled derives from max|v| (csrc/dca_gemm.hip pow2_scale_of — the same rule, kept beside its user:
-// no device symbol is shared between translation units)
-__device__ __forceinline__ float wg_pow2_scale_of(uint32_t amax_bits) {
-    const int ex = (int)((amax_bits >> 23) & 0xFFu) - 127;
-    if (ex < -100 || ex > 100) return 1.0f;
-    return __uint_as_float((uint32_t)(127 + 14 - ex) << 23);
-}
-__device__ __forceinline__ float wg_inv_scale(gp<const uint32_t> amax_bits) { return amax_bits ? 1.0f / wg_pow2_scale_of(*amax_bits) : 1.0f; }
+// undoes the scale dca_split_planes_scaled derives from max|v| (pow2_scale_of, dca_dense.h)
+__device__ __forceinline__ float wg_inv_scale(gp<const uint32_t> amax_bits) { return amax_bits ? 1.0f / pow2_scale_of(*amax_bits) : 1.0f; }
 
 // byte offset of 16-byte chunk ch (0..15) of row `row` inside a plane's K-tile
 __device__ __forceinline__ uint32_t lds_off(uint32_t row, uint32_t ch) {
@@ -80,8 +63,8 @@ __device__ __forceinline__ s4v tr_read(uint32_t a) {
     return s4v{};
 #endif
 }
-__device__ __forceinline__ h8 frag_of(s4v a, s4v b) {
-    return __builtin_bit_cast(h8, (s8v)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
+__device__ __forceinline__ f16x8 frag_of(s4v a, s4v b) {
+    return __builtin_bit_cast(f16x8, (s8v)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
 struct WgradArgs {
@@ -117,7 +100,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_wgrad(const WgradArgs p) {
         src[1] = (gp<const _Float16>)p.dyl + n0 + 8 * s_ch;
         src[NPL + 1] = (gp<const _Float16>)p.xl + k0 + 8 * s_ch;
     }
-    u4v pre[2 * NPL][2];
+    u32x4 pre[2 * NPL][2];
     auto prefetch = [&](int64_t r0) {
 #pragma unroll
         for (int q = 0; q < 2 * NPL; q++) {
@@ -126,8 +109,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_wgrad(const WgradArgs p) {
 #pragma unroll
             for (int u = 0; u < 2; u++) {
                 const int64_t r = r0 + s_row + 16 * u;
-                pre[q][u] = u4v{0u, 0u, 0u, 0u};
-                if (in && r < r_end) pre[q][u] = *(gp<const u4v>)(src[q] + r * ld);
+                pre[q][u] = u32x4{0u, 0u, 0u, 0u};
+                if (in && r < r_end) pre[q][u] = *(gp<const u32x4>)(src[q] + r * ld);
             }
         }
     };
@@ -148,21 +131,21 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_wgrad(const WgradArgs p) {
             b_addr[i][h] = lbase + (uint32_t)(NPL * WG_PLANE_BYTES) + lds_off(row, (uint32_t)(8 * wk + 2 * i) + (pp >> 1)) + 8u * (pp & 1u);
         }
 
-    f4v acc[4][4];
+    f32x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
-        for (int j = 0; j < 4; j++) acc[i][j] = f4v{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     prefetch(r_begin);
     for (int64_t r0 = r_begin; r0 < r_end; r0 += WG_KT) {
 #pragma unroll
         for (int q = 0; q < 2 * NPL; q++)
 #pragma unroll
-            for (int u = 0; u < 2; u++) *reinterpret_cast<u4v*>(lds + q * WG_PLANE_BYTES + st_off[u]) = pre[q][u];
+            for (int u = 0; u < 2; u++) *reinterpret_cast<u32x4*>(lds + q * WG_PLANE_BYTES + st_off[u]) = pre[q][u];
         __syncthreads();
         if (r0 + WG_KT < r_end) prefetch(r0 + WG_KT);
-        h8 bh[4], bl[4];
+        f16x8 bh[4], bl[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             bh[j] = frag_of(tr_read(b_addr[j][0]), tr_read(b_addr[j][1]));
@@ -170,8 +153,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_wgrad(const WgradArgs p) {
         }
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const h8 ah = frag_of(tr_read(a_addr[i][0]), tr_read(a_addr[i][1]));
-            h8 al;
+            const f16x8 ah = frag_of(tr_read(a_addr[i][0]), tr_read(a_addr[i][1]));
+            f16x8 al;
             if (NPL == 2) al = frag_of(tr_read(a_addr[i][0] + WG_PLANE_BYTES), tr_read(a_addr[i][1] + WG_PLANE_BYTES));
 #pragma unroll
             for (int j = 0; j < 4; j++) {

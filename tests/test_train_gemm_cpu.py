@@ -78,6 +78,45 @@ def test_refusals_need_no_device():
         assert L.dca_last_error().startswith(b"bad argument: "), kw
 
 
+def test_dense_launchers_refuse_before_the_first_device_call():
+    """The dense-layer launchers — dca_f16x3_gemm, dca_f16_gemm, dca_gemm16, dca_gemm8, dca_gemm8_mx — count their tiles in front of
+    the first HIP call: arguments that pass every clause but ask for more than 2^31 - 1 workgroups are refused with DCA_E_BADARG and
+    "<entry point>: too many tiles", not with whatever the runtime says without a device; and a broken clause is still refused in
+    the entry point's own name.  Only where no device is visible: there a regression fails cleanly, on a GPU box it would launch
+    on the fake addresses below."""
+    if torch.cuda.is_available():
+        pytest.skip("what happens before the first device call is told apart only without a device")
+    from deepcubea_amd import _lib
+    L = _lib.lib()
+    a, w = C.c_void_p(1 << 12), C.c_void_p(1 << 13)  # never dereferenced; aligned for every entry point
+    far = C.c_void_p(1 << 60)                        # an output far above the operand's extent (m * lda elements from `a`)
+    huge = 1 << 40                                   # 2^32 row tiles of 256: one tile column already exceeds the grid
+
+    def f16x3(m=huge, k=64, n=256):
+        return L.dca_f16x3_gemm(a, a, m, k, 64, w, w, n, 64, None, 1.0, None, None, 0, None, None, far, 256, None, None)
+
+    def f16(m=huge, k=64, n=256):
+        return L.dca_f16_gemm(a, m, k, 64, w, n, 64, None, 1.0, None, far, 256, None)
+
+    def g16(m=huge, k=64, n=256):
+        return L.dca_gemm16(a, m, k, 64, w, n, 64, _lib.DT_BF16, None, None, 0, far, 256, None)
+
+    def g8(m=huge, k=128, n=256):
+        return L.dca_gemm8(a, m, k, 128, w, n, 128, w, None, None, 0, far, 256, None, 0, 1.0, None)
+
+    def g8mx(m=huge, k=256, n=256):
+        return L.dca_gemm8_mx(a, w, m, k, 256, 4, w, n, 256, w, None, None, 0, far, 256, None, 0, None, 0, None)
+
+    calls = {"dca_f16x3_gemm": f16x3, "dca_f16_gemm": f16, "dca_gemm16": g16, "dca_gemm8": g8, "dca_gemm8_mx": g8mx}
+    for name, call in calls.items():
+        assert call() == -1, name
+        assert L.dca_last_error() == b"%s: too many tiles" % name.encode(), (name, L.dca_last_error())
+        assert call(m=0) == 0, name  # nothing to do comes before the count, as before
+    for name, call in calls.items():  # one broken clause each: k below / off the entry point's K granularity
+        assert call(m=8, k=32 if name != "dca_gemm8_mx" else 128) == -1, name
+        assert L.dca_last_error().startswith(b"bad argument: %s: " % name.encode()), (name, L.dca_last_error())
+
+
 def _net():
     from deepcubea_amd.utils.pytorch_models import ResnetModel
     torch.manual_seed(0)
