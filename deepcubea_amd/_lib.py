@@ -63,6 +63,11 @@ _SIGNATURES = {
     "dca_pdb_bytes": "l ii",
     "dca_pdb_build": "i ipippp",
     "dca_pdb_eval": "i ipllippppp",
+    "dca_cube3_pdb_bytes": "l ii",
+    "dca_cube3_pdb_cubies": "i ip",
+    "dca_cube3_pdb_index": "i ipipip",
+    "dca_cube3_pdb_build": "i ipippp",
+    "dca_cube3_pdb_eval": "i plliipppppp",
     "dca_engine_create": "i piidilii",
     "dca_engine_create_multi": "i piidiliii",
     "dca_engine_num_instances": "i p",
@@ -454,6 +459,21 @@ PDB_MAX_PATTERNS = 24
 PDB_NO_STATE, PDB_UNREACHABLE = 0xFF, 0xFE  # table bytes: two digits equal / a state the goal cannot be reached from
 
 
+def _pdb_rows(states: torch.Tensor, width: int, who: str):
+    """The rows a pattern-database eval walks -> (states with unit byte stride, n, row stride ld)."""
+    if states.dtype != torch.uint8 or not states.is_cuda or states.dim() != 2:
+        raise ValueError("%s: states must be a uint8 device tensor [n, >= %d]" % (who, width))
+    n = states.shape[0]
+    if n > 0 and states.stride(1) != 1:
+        states = states.contiguous()
+    ld = states.stride(0) if n > 1 else max(states.stride(0), states.shape[1])
+    if ld < states.shape[1]:
+        states, ld = states.contiguous(), states.shape[1]
+    if states.shape[1] < width:
+        ld = states.shape[1]  # too narrow a row: the library refuses ld < width
+    return states, n, ld
+
+
 def pdb_bytes(dim: int, k: int) -> int:
     """Bytes of one pattern's table, N^(k+1) with N = dim * dim: a pure function (include/dca.h); DcaError outside its limits."""
     b = lib().dca_pdb_bytes(dim, k)
@@ -477,16 +497,7 @@ def pdb_build(dim: int, tiles, table: Optional[torch.Tensor] = None):
 def pdb_eval(dim: int, states: torch.Tensor, partition, tables, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Sum of the patterns' table bytes per row -> f32 [n].  states: uint8 device rows [n, >= dim * dim] with unit byte stride
     (a strided view is fine); ANY bytes are in bounds (include/dca.h, the any-bytes rule)."""
-    if states.dtype != torch.uint8 or not states.is_cuda or states.dim() != 2:
-        raise ValueError("pdb_eval: states must be a uint8 device tensor [n, >= dim * dim]")
-    n, N = states.shape[0], dim * dim
-    if n > 0 and states.stride(1) != 1:
-        states = states.contiguous()
-    ld = states.stride(0) if n > 1 else max(states.stride(0), states.shape[1])
-    if ld < states.shape[1]:
-        states, ld = states.contiguous(), states.shape[1]
-    if states.shape[1] < N:
-        ld = states.shape[1]  # too narrow for this board: the library refuses ld < N
+    states, n, ld = _pdb_rows(states, dim * dim, "pdb_eval")
     ks = np.ascontiguousarray([len(g) for g in partition], dtype=np.int32)
     flat = np.ascontiguousarray([t for g in partition for t in g], dtype=np.uint8)
     ptrs = (C.c_void_p * max(len(tables), 1))(*[ptr(t) for t in tables])
@@ -495,6 +506,86 @@ def pdb_eval(dim: int, states: torch.Tensor, partition, tables, out: Optional[to
     assert out.dtype == torch.float32 and out.numel() >= n
     check(lib().dca_pdb_eval(dim, _raw(states), n, ld, len(partition), flat.ctypes.data_as(C.c_void_p), ks.ctypes.data_as(C.c_void_p),
                              ptrs, ptr(out), stream_ptr()), "dca_pdb_eval")
+    return out
+
+
+# ------------------------------------------------------------------------------ pattern databases (cube3)
+CUBE3_CORNERS, CUBE3_EDGES = 0, 1
+ROWS_STATE, ROWS_NNET = 0, 1  # what a row's 54 bytes are: sticker ids 0..53 / colour bytes 0..5 (the network input)
+CUBE3_PDB_SLOTS = {CUBE3_CORNERS: (8, 3), CUBE3_EDGES: (12, 2)}  # kind -> (slots n, orientations o)
+
+
+def _byte_list(values) -> np.ndarray:
+    """Small non-negative integers as the uint8 array an entry point reads; ValueError (not a wrapped value) outside a byte."""
+    a = np.ascontiguousarray(list(values), dtype=np.int64)
+    if a.size and (a.min() < 0 or a.max() > 255):
+        raise ValueError("values outside 0..255: %s" % (a.tolist(),))
+    return a.astype(np.uint8)
+
+
+def cube3_pdb_bytes(kind: int, k: int) -> int:
+    """Bytes of one pattern's table, P(n, k) * o^k: a pure function (include/dca.h); DcaError outside its limits."""
+    b = lib().dca_cube3_pdb_bytes(kind, k)
+    check(min(b, 0), "dca_cube3_pdb_bytes")
+    return b
+
+
+def cube3_pdb_cubies(kind: int) -> np.ndarray:
+    """The cubie lists as the library numbers them -> uint8 [n, o] sticker positions."""
+    if kind not in CUBE3_PDB_SLOTS:
+        raise ValueError("kind is CUBE3_CORNERS (0) or CUBE3_EDGES (1), not %r" % (kind,))
+    n, o = CUBE3_PDB_SLOTS[kind]
+    out = np.zeros(n * o, np.uint8)
+    check(lib().dca_cube3_pdb_cubies(kind, out.ctypes.data_as(C.c_void_p)), "dca_cube3_pdb_cubies")
+    return out.reshape(n, o)
+
+
+def cube3_pdb_index(kind: int, cubies, rows: np.ndarray, row_kind: int) -> np.ndarray:
+    """Table index of host rows [m, 54] (or one row [54]) by the code the kernels run -> int64 [m].  No device needed."""
+    cubies = _byte_list(cubies)
+    rows = np.ascontiguousarray(rows, dtype=np.uint8).reshape(-1, 54)
+    out = np.zeros(len(rows), np.int64)
+    fn, one = lib().dca_cube3_pdb_index, C.c_int64(0)
+    cp = cubies.ctypes.data_as(C.c_void_p)
+    for i in range(len(rows)):
+        check(fn(kind, cp, len(cubies), rows[i].ctypes.data_as(C.c_void_p), row_kind, C.byref(one)), "dca_cube3_pdb_index")
+        out[i] = one.value
+    return out
+
+
+def cube3_pdb_build(kind: int, cubies, table: Optional[torch.Tensor] = None):
+    """Fill (or allocate and fill) the device table of one pattern -> (table u8 [P(n,k) * o^k], sweeps).  Synchronises."""
+    cubies = _byte_list(cubies)
+    nbytes = cube3_pdb_bytes(kind, len(cubies))
+    if table is None:
+        table = torch.empty(nbytes, dtype=torch.uint8, device=require_gpu())
+    assert table.dtype == torch.uint8 and table.numel() == nbytes
+    sweeps = C.c_int(0)
+    check(lib().dca_cube3_pdb_build(kind, cubies.ctypes.data_as(C.c_void_p), len(cubies), ptr(table), C.byref(sweeps), stream_ptr()),
+          "dca_cube3_pdb_build")
+    return table, int(sweeps.value)
+
+
+def cube3_pdb_eval(states: torch.Tensor, row_kind: int, patterns, tables, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Max of the patterns' table bytes per row -> f32 [n].  patterns: [(kind, cubies), ...]; states: uint8 device rows
+    [n, >= 54] with unit byte stride (a strided view is fine); ANY bytes are in bounds (include/dca.h, the any-bytes rule)."""
+    states, n, ld = _pdb_rows(states, 54, "cube3_pdb_eval")
+    kinds = np.ascontiguousarray([kind for kind, _ in patterns], dtype=np.int32)
+    ks = np.ascontiguousarray([len(g) for _, g in patterns], dtype=np.int32)
+    flat = _byte_list([c for _, g in patterns for c in g])
+    if len(tables) != len(patterns):
+        raise ValueError("cube3_pdb_eval: %d tables for %d patterns" % (len(tables), len(patterns)))
+    for (kind, g), t in zip(patterns, tables):  # the library cannot see a table's size: a short one would be read past its end
+        if kind in CUBE3_PDB_SLOTS and 1 <= len(g) <= 8 and (t.dtype != torch.uint8 or t.numel() != cube3_pdb_bytes(kind, len(g))):
+            raise ValueError("cube3_pdb_eval: a table of %d elements for a pattern that needs %d bytes"
+                             % (t.numel(), cube3_pdb_bytes(kind, len(g))))
+    ptrs = (C.c_void_p * max(len(tables), 1))(*[ptr(t) for t in tables])
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=states.device)
+    assert out.dtype == torch.float32 and out.numel() >= n
+    check(lib().dca_cube3_pdb_eval(_raw(states), n, ld, row_kind, len(patterns), kinds.ctypes.data_as(C.c_void_p),
+                                   flat.ctypes.data_as(C.c_void_p), ks.ctypes.data_as(C.c_void_p), ptrs, ptr(out), stream_ptr()),
+          "dca_cube3_pdb_eval")
     return out
 
 

@@ -16,6 +16,7 @@
 //
 // What bounds either kernel has not been measured (profiles/pdb_probe.txt holds only wall-clock rates).
 #include "dca_common.h"
+#include "dca_pdb_row.h"
 
 namespace dca {
 
@@ -168,24 +169,7 @@ static int pdb_build_launch(uint8_t* table, uint64_t total, int k, const PdbPatt
 }
 
 // ---------------------------------------------------------------------------------------------------------------- eval
-// the row as little-endian 32-bit words, zero padded: W-byte loads (W = what the base pointer and the row stride are both
-// multiples of) for the whole units inside the row, single bytes where a unit would cross the row's end
-template <int N, int W>
-__host__ __device__ inline void pdb_load_row(const uint8_t* __restrict__ p, uint32_t (&w)[(N + 3) / 4]) {
-    constexpr int NW = (N + 3) / 4;
-#pragma unroll
-    for (int q = 0; q < NW; q++) w[q] = 0;
-    if constexpr (W == 4) {
-#pragma unroll
-        for (int q = 0; q < N / 4; q++) w[q] = *(const uint32_t*)(p + 4 * q);
-#pragma unroll
-        for (int i = N / 4 * 4; i < N; i++) w[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; i++) w[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
-    }
-}
-
+// (the row load, pdb_load_row, is shared with the cube3 tables: dca_pdb_row.h)
 // last position whose byte equals t, 0 if none (t < N is wave-uniform; a byte >= N equals no tile)
 template <int N>
 __host__ __device__ inline uint32_t pdb_find(const uint32_t (&w)[(N + 3) / 4], uint32_t t) {

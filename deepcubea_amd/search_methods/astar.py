@@ -53,19 +53,29 @@ def _load_heuristic(args, env):
     """Device heuristic closure.  `--model_dir synthetic:SEED` builds the environment's network with
     deterministic synthetic weights (the reference checkpoints are not redistributable here)."""
     if _is_pdb(args):
-        # no network: additive pattern databases (utils/pattern_db.py).  The spec is checked before any device work; the closure
-        # reads the packed uint8 rows of the dedup-first path (stride 0 = no one-hot rows)
-        from ..utils.pattern_db import PatternDatabase, parse_pdb_spec
-        partition = parse_pdb_spec(args.env, str(args.model_dir).split(":", 1)[1])
+        # no network: pattern databases — additive ones for the sliding puzzles (utils/pattern_db.py), corner / edge tables
+        # combined by max for cube3 (utils/cube3_pdb.py).  The spec is checked before any device work; the closure reads the
+        # packed uint8 rows of the dedup-first path (stride 0 = no one-hot rows)
+        spec = str(args.model_dir).split(":", 1)[1]
+        if str(args.env).lower() == "cube3":
+            from ..utils.cube3_pdb import Cube3PatternDatabase, parse_cube3_pdb_spec
+            partition = parse_cube3_pdb_spec(spec)
+        else:
+            from ..utils.pattern_db import PatternDatabase, parse_pdb_spec
+            partition = parse_pdb_spec(args.env, spec)
     device, devices, on_gpu = nnet_utils.get_device()
     print("device: %s, devices: %s, on_gpu: %s" % (device, devices, on_gpu))
     if not on_gpu:
         raise _lib.DcaError("--language hip needs an MI355X: no HIP device visible")
     if _is_pdb(args):
         start = time.time()
-        pdb = PatternDatabase(args.env, partition).build()
-        print("pattern database %s: %d bytes, sweeps %s, built in %.2f s"
-              % ("/".join(",".join(str(t) for t in g) for g in pdb.partition), pdb.bytes, pdb.sweeps, time.time() - start))
+        if str(args.env).lower() == "cube3":
+            pdb = Cube3PatternDatabase(partition).build()
+            name = pdb.spec
+        else:
+            pdb = PatternDatabase(args.env, partition).build()
+            name = "/".join(",".join(str(t) for t in g) for g in pdb.partition)
+        print("pattern database %s: %d bytes, sweeps %s, built in %.2f s" % (name, pdb.bytes, pdb.sweeps, time.time() - start))
         return pdb.heuristic_fn_dev(), 0
     nnet = env.get_nnet_model()
     if str(args.model_dir).startswith("synthetic:"):
@@ -236,7 +246,9 @@ def build_parser() -> ArgumentParser:
                         help="Directory of nnet model, or synthetic:SEED, or builtin:manhattan / builtin:zero, or pdb:SPEC — "
                              "additive pattern databases on the sliding puzzles, built on the GPU at start-up: SPEC is a preset "
                              "(puzzle8 4-4; puzzle15 5-5-5, 6-6-3; puzzle24 6-6-6-6; auto = the first of these) or explicit "
-                             "groups of tiles such as 1,2,3,4/5,6,7,8.  Admissible and consistent: with --weight 1 --semantics cpp "
+                             "groups of tiles such as 1,2,3,4/5,6,7,8.  On cube3: corner / edge cubie tables combined by max, SPEC a "
+                             "preset (corners, korf, korf7; no auto) or groups of cubies of one kind such as "
+                             "c0,c1,c2,c3/e0,e1,e2,e3,e4,e5.  Admissible and consistent: with --weight 1 --semantics cpp "
                              "the solutions are optimal")
     parser.add_argument('--env', type=str, required=True, help="Environment: cube3, puzzle8, puzzle15, puzzle24, puzzle35, puzzle48, lightsout7 "
                                                                       "(puzzle8 has every layer-1 kernel puzzle15 has: no --nnet_dtype mode is on a fall-back there)")

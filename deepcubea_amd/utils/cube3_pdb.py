@@ -1,0 +1,175 @@
+"""Pattern databases for cube3 (include/dca.h "pattern databases for cube3", csrc/dca_pdb_cube3.hip): Korf's distance tables
+over corner cubies and over subsets of the edge cubies, combined by max — an exact admissible, consistent heuristic.  With
+`--env cube3 --model_dir pdb:<spec> --weight 1 --semantics cpp` the engine is an optimal solver.
+
+A set is a tuple of patterns, a pattern a (kind, cubies) pair; `parse_cube3_pdb_spec` turns a preset name or explicit groups
+("c0,c1,c2/e0,e1,e2,e3") into one and refuses what cannot be built, before any device work.  Patterns may share cubies: the
+max of admissible tables is admissible."""
+from __future__ import annotations
+
+import re
+from math import perm
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+Pattern = Tuple[int, Tuple[int, ...]]
+PatternSet = Tuple[Pattern, ...]
+
+_C, _E = _lib.CUBE3_CORNERS, _lib.CUBE3_EDGES
+_PREFIX = {_C: "c", _E: "e"}
+PRESETS: Dict[str, PatternSet] = {
+    "corners": ((_C, tuple(range(8))),),
+    "korf": ((_C, tuple(range(8))), (_E, tuple(range(0, 6))), (_E, tuple(range(6, 12)))),
+    "korf7": ((_C, tuple(range(8))), (_E, tuple(range(0, 7))), (_E, tuple(range(5, 12)))),
+}
+MAX_K = 8
+MAX_TABLE_BYTES = 1 << 34  # one pattern's table (the library's own limit)
+
+
+def pattern_bytes(kind: int, k: int) -> int:
+    n, o = _lib.CUBE3_PDB_SLOTS[kind]
+    return perm(n, k) * o ** k
+
+
+def spec_of(patterns: PatternSet) -> str:
+    return "/".join(",".join("%s%d" % (_PREFIX[kind], c) for c in g) for kind, g in patterns)
+
+
+def check_patterns(patterns) -> PatternSet:
+    patterns = tuple((int(kind), tuple(int(c) for c in g)) for kind, g in patterns)
+    if not 1 <= len(patterns) <= _lib.PDB_MAX_PATTERNS:
+        raise ValueError("a pattern database has 1..%d patterns, not %d" % (_lib.PDB_MAX_PATTERNS, len(patterns)))
+    for kind, group in patterns:
+        if kind not in _lib.CUBE3_PDB_SLOTS:
+            raise ValueError("a pattern's kind is 0 (corners) or 1 (edges), not %r" % (kind,))
+        n, _ = _lib.CUBE3_PDB_SLOTS[kind]
+        if not 1 <= len(group) <= MAX_K:
+            raise ValueError("a pattern has 1..%d cubies, not %d" % (MAX_K, len(group)))
+        for c in group:
+            if not 0 <= c < n:
+                raise ValueError("cubie %s%d is out of range: cube3 has %s0..%s%d" % (_PREFIX[kind], c, _PREFIX[kind], _PREFIX[kind], n - 1))
+        if len(set(group)) != len(group):
+            raise ValueError("a cubie is named twice in the pattern %s" % spec_of(((kind, group),)))
+        if pattern_bytes(kind, len(group)) > MAX_TABLE_BYTES:
+            raise ValueError("the pattern %s needs a table of %d bytes: over the cap of 2^34"
+                             % (spec_of(((kind, group),)), pattern_bytes(kind, len(group))))
+    return patterns
+
+
+def parse_cube3_pdb_spec(spec: str) -> PatternSet:
+    """`spec`: a preset ("corners", "korf", "korf7") or explicit groups such as "c0,c1,c2/e0,e1,e2,e3" (cubies separated by
+    commas, patterns by slashes; c = corner 0..7, e = edge 0..11, numbered as dca_cube3_pdb_cubies lists them).  ValueError,
+    with no device needed, for: an unknown name (cube3 has no "auto"), bare numbers, corners and edges in one group, a cubie
+    twice in one group, more than 8 cubies in a group, a table over the size cap, more than 24 groups."""
+    spec = str(spec).strip()
+    if spec.lower() in PRESETS:
+        return PRESETS[spec.lower()]
+    if not re.fullmatch(r"[ce\d,/\s]+", spec) or not re.search(r"\d", spec):
+        raise ValueError("unknown cube3 pattern database %r (presets: %s; or explicit groups such as c0,c1,c2/e0,e1,e2,e3)"
+                         % (spec, ", ".join(sorted(PRESETS))))
+    patterns = []
+    for group in spec.split("/"):
+        names = [t.strip() for t in group.split(",")]
+        if not all(re.fullmatch(r"[ce]\d+", t) for t in names):
+            raise ValueError("pattern group %r: cubies are written c0..c7 / e0..e11, separated by ',', patterns by '/'" % group)
+        if len({t[0] for t in names}) != 1:
+            raise ValueError("pattern group %r mixes corners and edges: a pattern is of one kind" % group)
+        patterns.append((_C if names[0][0] == "c" else _E, tuple(int(t[1:]) for t in names)))
+    return check_patterns(patterns)
+
+
+def table_bytes(patterns: PatternSet) -> List[int]:
+    return [pattern_bytes(kind, len(g)) for kind, g in patterns]
+
+
+class Cube3PatternDatabase:
+    """The tables of one pattern set on the current device.  build() fills them one pattern after another; save() / load() keep
+    them in an .npz; heuristic_fn_dev() is the closure BwasEngine.step calls (it reads the network-input colour rows)."""
+
+    env_name = "cube3"
+
+    def __init__(self, patterns):
+        self.patterns = parse_cube3_pdb_spec(patterns) if isinstance(patterns, str) else check_patterns(patterns)
+        self.tables: List[torch.Tensor] = []
+        self.sweeps: List[int] = []
+
+    @property
+    def spec(self) -> str:
+        return spec_of(self.patterns)
+
+    @property
+    def bytes(self) -> int:
+        return sum(table_bytes(self.patterns))
+
+    def build(self) -> "Cube3PatternDatabase":
+        _lib.require_gpu()
+        self.tables, self.sweeps = [], []
+        for kind, group in self.patterns:
+            table, sweeps = _lib.cube3_pdb_build(kind, group)
+            self.tables.append(table)
+            self.sweeps.append(sweeps)
+        return self
+
+    def set_tables(self, tables: Sequence[np.ndarray]) -> "Cube3PatternDatabase":
+        """Adopt host-made tables (one uint8 array of P(n, k) * o^k bytes per pattern)."""
+        want = table_bytes(self.patterns)
+        if len(tables) != len(want):
+            raise ValueError("%d tables for %d patterns" % (len(tables), len(want)))
+        host = [np.ascontiguousarray(t, dtype=np.uint8).reshape(-1) for t in tables]
+        for t, b in zip(host, want):
+            if t.size != b:
+                raise ValueError("a table of %d bytes where the pattern needs %d" % (t.size, b))
+        dev = _lib.require_gpu()
+        self.tables = [torch.from_numpy(t if t.flags.writeable else t.copy()).to(dev) for t in host]
+        self.sweeps = [0] * len(host)
+        return self
+
+    def heuristic(self, states: torch.Tensor, row_kind: int = _lib.ROWS_STATE) -> torch.Tensor:
+        if len(self.tables) != len(self.patterns):
+            raise _lib.DcaError("Cube3PatternDatabase: build() or load() first")
+        return _lib.cube3_pdb_eval(states, row_kind, self.patterns, self.tables)
+
+    def heuristic_fn_dev(self):
+        """(uint8 colour rows [m, 54] on the device, is_onehot=False) -> float32 [m]: the closure form of BwasEngine.step /
+        solve, which hand a cube3 closure the network-input rows (sticker // 9)."""
+        def fn(states: torch.Tensor, is_onehot: bool = False) -> torch.Tensor:
+            if is_onehot:
+                raise ValueError("a pattern database reads the uint8 network-input rows, not one-hot rows")
+            return self.heuristic(states, _lib.ROWS_NNET)
+        return fn
+
+    def save(self, path: str, tables: Optional[Sequence[np.ndarray]] = None) -> None:
+        """Write the pattern set and the tables to an .npz (`tables`: host arrays to write instead of the device's)."""
+        if tables is None:
+            if len(self.tables) != len(self.patterns):
+                raise _lib.DcaError("Cube3PatternDatabase: nothing to save, build() first")
+            tables = [t.cpu().numpy() for t in self.tables]
+        want = table_bytes(self.patterns)
+        if [int(np.asarray(t).size) for t in tables] != want:
+            raise ValueError("table sizes %s, the pattern set needs %s" % ([int(np.asarray(t).size) for t in tables], want))
+        arrays = {"table_%d" % i: np.ascontiguousarray(t, dtype=np.uint8).reshape(-1) for i, t in enumerate(tables)}
+        arrays["env_name"] = np.array(self.env_name)
+        arrays["partition"] = np.array(self.spec)
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load_host(cls, path: str):
+        """-> (Cube3PatternDatabase without device tables, [host tables]); needs no device."""
+        with np.load(path) as z:
+            if str(z["env_name"]) != cls.env_name:
+                raise ValueError("%s holds tables of %s, not of cube3" % (path, z["env_name"]))
+            pdb = cls(str(z["partition"]))
+            tables = [z["table_%d" % i] for i in range(len(pdb.patterns))]
+        if [int(t.size) for t in tables] != table_bytes(pdb.patterns):
+            raise ValueError("%s: table sizes do not match the pattern set" % path)
+        return pdb, tables
+
+    @classmethod
+    def load(cls, path: str) -> "Cube3PatternDatabase":
+        pdb, tables = cls.load_host(path)
+        return pdb.set_tables(tables)

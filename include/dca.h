@@ -247,6 +247,65 @@ int dca_pdb_eval(int dim, const uint8_t* states /*[n, ld]*/, int64_t n, int64_t 
                  const int* ks /*host [num_patterns]*/, const uint8_t* const* tables /*host [num_patterns] of device pointers*/,
                  float* out /*[n]*/, void* stream);
 
+/* Pattern databases for cube3 (csrc/dca_pdb_cube3.hip; `--env cube3 --model_dir pdb:<spec>`): Korf's distance tables over
+ * corner cubies and over subsets of the edge cubies, combined by MAX (a face turn moves cubies of several patterns at once, so
+ * the tables do not add).  Every table is admissible and consistent on its own, and so is their max.
+ *   cubies       numbered from the move table (dca_cube3_perm_table): two sticker positions belong to one cubie exactly when the
+ *                same set of the 12 moves displaces them — 8 classes of three (corners, kind DCA_CUBE3_CORNERS: n = 8 slots,
+ *                o = 3 orientations), 12 of two (edges, DCA_CUBE3_EDGES: n = 12, o = 2), and the 6 centres.  A cubie's
+ *                positions are listed in ascending order, the cubies of a kind are ordered by their smallest position, and slot
+ *                s is the home of cubie s.  dca_cube3_pdb_cubies writes the lists, [n][o] position bytes (host).
+ *   pattern      an ordered list of k distinct cubies of one kind, 1 <= k <= 8; its table is caller-owned device memory of
+ *                dca_cube3_pdb_bytes(kind, k) = P(n, k) * o^k bytes, P(n, k) = n! / (n - k)! (a pure function; DCA_E_BADARG
+ *                unless kind is 0 or 1, k is 1..8 and the result is <= 2^34: nine edges are refused).
+ *   location     cubie j of a state is at (s_j, r_j): s_j = the slot that holds it, r_j = the index, within slot s_j's position
+ *                list, of the position that shows the cubie's reference facelet — the facelet whose home is the cubie's
+ *                smallest position.
+ *   index rule   slot rank, most significant digit first: digit j is d_j = s_j - #{i < j : s_i < s_j} in radix n - j; then
+ *                index = rank * o^k + the k orientation digits r_j in radix o, cubie 0 most significant.  The goal has every
+ *                cubie at home with r = 0.  No special case for k = n: all eight corners take 8! * 3^8 bytes of which a third
+ *                is reachable.
+ *   value rule   table[index] = the breadth-first distance, in the 12-move metric, of the abstract state (the locations of the
+ *                pattern's cubies, everything else invisible) to the goal; an entry no move sequence reaches holds 0xFE.
+ * dca_cube3_pdb_build fills `table` level by level: sweep d gives the value d to every entry that is still 0xFE and has a
+ * neighbour (one of the 12 moves away) at d - 1; one thread per entry pulls and writes only its own byte.  It SYNCHRONISES the
+ * stream once per sweep to read a "filled" word.  *sweeps (host, or NULL) = the sweeps it took = the deepest level + 1, the
+ * last, empty one included: the table AND the count are the same on every run.  cubies: host [k].
+ * dca_cube3_pdb_index (host only, no device call) is the index of one 54-byte row by the code the kernels run.
+ * dca_cube3_pdb_eval: out[i] = max over the patterns of table_p[index_p(row i)], an integer <= 255, exact in fp32.  states:
+ * device rows [n, ld], ld >= 54, any byte alignment.  row_kind says what a row's bytes are: DCA_ROWS_STATE sticker ids 0..53
+ * (turned into colours, id / 9, on load) or DCA_ROWS_NNET the 54 colour bytes 0..5 of the network input — what
+ * dca_engine_pop_expand_packed and dca_engine_root_nnet_in hand a heuristic closure for cube3.  kinds, ks: host
+ * [num_patterns]; cubies: host, the patterns' cubie lists one after another; tables: HOST array of num_patterns device
+ * pointers.  Up to 24 patterns; patterns MAY share cubies (a max stays admissible); within a pattern the cubies are distinct.
+ * The metadata travels as kernel arguments; stream-ordered, nothing synchronises.
+ *   colour rule  a slot's cubie is recognised by the SET of colours on the slot's positions and oriented by where the smallest
+ *                of them sits (a cubie's reference facelet has its smallest colour): r = the first position of the slot's list
+ *                that holds the slot's smallest byte.
+ *   any-bytes rule  the engine pads closure input to a multiple of 1024 rows whose padding is stale or zero, so every read is in
+ *                bounds for ANY 54 bytes: a byte above 5 (after id / 9 for DCA_ROWS_STATE) belongs to no colour set; cubie j's
+ *                location is that of the LAST slot whose colour set is the cubie's, (0, 0) if there is none; a rank digit is
+ *                clamped to its radix, d_j <= n - j - 1.  Every index is then < P(n, k) * o^k by construction.  The value of a
+ *                row that is no cube state is whatever the tables hold there, and is deterministic.
+ * DCA_E_BADARG before any launch, the message naming the argument: kind outside {0, 1}; k outside 1..8 or a table over 2^34
+ * bytes; a cubie >= n or named twice in its pattern; num_patterns outside 1..24; row_kind outside {0, 1}; a NULL cubies / kinds
+ * / ks / tables / table / row / index / positions / out (states and out may be NULL when n == 0); out not 4-byte aligned;
+ * ld < 54; n < 0 or >= 2^31. */
+#define DCA_CUBE3_CORNERS 0
+#define DCA_CUBE3_EDGES 1
+#define DCA_ROWS_STATE 0
+#define DCA_ROWS_NNET 1
+int64_t dca_cube3_pdb_bytes(int kind, int k);
+int dca_cube3_pdb_cubies(int kind, uint8_t* positions /*host [n*o]*/);
+int dca_cube3_pdb_index(int kind, const uint8_t* cubies /*host [k]*/, int k, const uint8_t* row /*host [54]*/, int row_kind,
+                        int64_t* index /*host*/);
+int dca_cube3_pdb_build(int kind, const uint8_t* cubies /*host [k]*/, int k, uint8_t* table /*device [P(n,k)*o^k]*/,
+                        int* sweeps /*host or NULL*/, void* stream);
+int dca_cube3_pdb_eval(const uint8_t* states /*[n, ld]*/, int64_t n, int64_t ld, int row_kind, int num_patterns,
+                       const int* kinds /*host [num_patterns]*/, const uint8_t* cubies /*host*/,
+                       const int* ks /*host [num_patterns]*/, const uint8_t* const* tables /*host [num_patterns] of device pointers*/,
+                       float* out /*[n]*/, void* stream);
+
 /* state hash (a9).  The reference's hash VALUES are process-randomised SipHash (cube3.py:17-21)
  * or unpinned boost::hash_range (parallel_weighted_astar.cpp:104-111); what is pinned is key
  * equality.  This library defines, for a D-byte state split in little-endian 8-byte words
