@@ -7,6 +7,8 @@ streams and (elsewhere) the heuristic network.
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import math
 import os
 from typing import Optional
 
@@ -474,47 +476,6 @@ def _pdb_rows(states: torch.Tensor, width: int, who: str):
     return states, n, ld
 
 
-def pdb_bytes(dim: int, k: int) -> int:
-    """Bytes of one pattern's table, N^(k+1) with N = dim * dim: a pure function (include/dca.h); DcaError outside its limits."""
-    b = lib().dca_pdb_bytes(dim, k)
-    check(min(b, 0), "dca_pdb_bytes")
-    return b
-
-
-def pdb_build(dim: int, tiles, table: Optional[torch.Tensor] = None):
-    """Fill (or allocate and fill) the device table of the pattern `tiles` -> (table u8 [N^(k+1)], sweeps).  Synchronises."""
-    tiles = np.ascontiguousarray(list(tiles), dtype=np.uint8)
-    nbytes = pdb_bytes(dim, len(tiles))
-    if table is None:
-        table = torch.empty(nbytes, dtype=torch.uint8, device=require_gpu())
-    assert table.dtype == torch.uint8 and table.numel() == nbytes
-    sweeps = C.c_int(0)
-    check(lib().dca_pdb_build(dim, tiles.ctypes.data_as(C.c_void_p), len(tiles), ptr(table), C.byref(sweeps), stream_ptr()),
-          "dca_pdb_build")
-    return table, int(sweeps.value)
-
-
-def pdb_eval(dim: int, states: torch.Tensor, partition, tables, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Sum of the patterns' table bytes per row -> f32 [n].  states: uint8 device rows [n, >= dim * dim] with unit byte stride
-    (a strided view is fine); ANY bytes are in bounds (include/dca.h, the any-bytes rule)."""
-    states, n, ld = _pdb_rows(states, dim * dim, "pdb_eval")
-    ks = np.ascontiguousarray([len(g) for g in partition], dtype=np.int32)
-    flat = np.ascontiguousarray([t for g in partition for t in g], dtype=np.uint8)
-    ptrs = (C.c_void_p * max(len(tables), 1))(*[ptr(t) for t in tables])
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=states.device)
-    assert out.dtype == torch.float32 and out.numel() >= n
-    check(lib().dca_pdb_eval(dim, _raw(states), n, ld, len(partition), flat.ctypes.data_as(C.c_void_p), ks.ctypes.data_as(C.c_void_p),
-                             ptrs, ptr(out), stream_ptr()), "dca_pdb_eval")
-    return out
-
-
-# ------------------------------------------------------------------------------ pattern databases (cube3)
-CUBE3_CORNERS, CUBE3_EDGES = 0, 1
-ROWS_STATE, ROWS_NNET = 0, 1  # what a row's 54 bytes are: sticker ids 0..53 / colour bytes 0..5 (the network input)
-CUBE3_PDB_SLOTS = {CUBE3_CORNERS: (8, 3), CUBE3_EDGES: (12, 2)}  # kind -> (slots n, orientations o)
-
-
 def _byte_list(values) -> np.ndarray:
     """Small non-negative integers as the uint8 array an entry point reads; ValueError (not a wrapped value) outside a byte."""
     a = np.ascontiguousarray(list(values), dtype=np.int64)
@@ -523,11 +484,88 @@ def _byte_list(values) -> np.ndarray:
     return a.astype(np.uint8)
 
 
+def _pdb_build(symbol: str, bytes_fn, family: int, ids, table: Optional[torch.Tensor]):
+    """One pattern's build through `symbol`(family, ids, k, table, sweeps, stream) -> (table, sweeps)."""
+    ids = _byte_list(ids)
+    nbytes = bytes_fn(family, len(ids))
+    if table is None:
+        table = torch.empty(nbytes, dtype=torch.uint8, device=require_gpu())
+    assert table.dtype == torch.uint8 and table.numel() == nbytes
+    sweeps = C.c_int(0)
+    check(getattr(lib(), symbol)(family, ids.ctypes.data_as(C.c_void_p), len(ids), ptr(table), C.byref(sweeps), stream_ptr()), symbol)
+    return table, int(sweeps.value)
+
+
+@functools.lru_cache(maxsize=64)
+def _pdb_set(groups, families, size_of):
+    """What an eval marshals from its pattern set, kept per set (the engine's closure evaluates one set every iteration, and the
+    library only reads these arrays) -> (pointers to families i32, ids u8, ks i32; each pattern's table bytes; the arrays, kept
+    alive).  groups: the patterns' id tuples; families: per pattern the dim or the kind; size_of(family, k): the table's bytes by
+    arithmetic, no library call — None outside the library's limits, where the library words the refusal."""
+    arrays = (np.ascontiguousarray(families, dtype=np.int32), _byte_list([i for g in groups for i in g]),
+              np.ascontiguousarray([len(g) for g in groups], dtype=np.int32))
+    return (tuple(a.ctypes.data_as(C.c_void_p) for a in arrays), tuple(size_of(f, len(g)) for f, g in zip(families, groups)), arrays)
+
+
+def _pdb_eval(who: str, symbol: str, states: torch.Tensor, width: int, groups, families, size_of, tables, out: Optional[torch.Tensor],
+              call):
+    """What the evals share; call(states, n, ld, num_patterns, families, ids, ks, tables, out, stream) makes the family's call."""
+    states, n, ld = _pdb_rows(states, width, who)
+    pointers, sizes, _ = _pdb_set(tuple(tuple(g) for g in groups), tuple(families), size_of)
+    if len(tables) != len(groups):
+        raise ValueError("%s: %d tables for %d patterns" % (who, len(tables), len(groups)))
+    for size, t in zip(sizes, tables):  # the library cannot see a table's size: a short one would be read past its end
+        if size is not None and (t.dtype != torch.uint8 or t.numel() != size):
+            raise ValueError("%s: a table of %d elements for a pattern that needs %d bytes" % (who, t.numel(), size))
+    ptrs = (C.c_void_p * max(len(tables), 1))(*[ptr(t) for t in tables])
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=states.device)
+    assert out.dtype == torch.float32 and out.numel() >= n
+    check(call(_raw(states), n, ld, len(groups), *pointers, ptrs, ptr(out), stream_ptr()), symbol)
+    return out
+
+
+def pdb_bytes(dim: int, k: int) -> int:
+    """Bytes of one pattern's table, N^(k+1) with N = dim * dim: a pure function (include/dca.h); DcaError outside its limits."""
+    b = lib().dca_pdb_bytes(dim, k)
+    check(min(b, 0), "dca_pdb_bytes")
+    return b
+
+
+def _pdb_table_bytes(dim: int, k: int) -> Optional[int]:
+    return (dim * dim) ** (k + 1) if 3 <= dim <= 7 and 1 <= k <= dim * dim - 1 else None
+
+
+def pdb_build(dim: int, tiles, table: Optional[torch.Tensor] = None):
+    """Fill (or allocate and fill) the device table of the pattern `tiles` -> (table u8 [N^(k+1)], sweeps).  Synchronises."""
+    return _pdb_build("dca_pdb_build", pdb_bytes, dim, tiles, table)
+
+
+def pdb_eval(dim: int, states: torch.Tensor, partition, tables, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sum of the patterns' table bytes per row -> f32 [n].  states: uint8 device rows [n, >= dim * dim] with unit byte stride
+    (a strided view is fine); ANY bytes are in bounds (include/dca.h, the any-bytes rule)."""
+    return _pdb_eval("pdb_eval", "dca_pdb_eval", states, dim * dim, partition, (dim,) * len(partition), _pdb_table_bytes, tables, out,
+                     lambda s, n, ld, m, dims, *rest: lib().dca_pdb_eval(dim, s, n, ld, m, *rest))
+
+
+# ------------------------------------------------------------------------------ pattern databases (cube3)
+CUBE3_CORNERS, CUBE3_EDGES = 0, 1
+ROWS_STATE, ROWS_NNET = 0, 1  # what a row's 54 bytes are: sticker ids 0..53 / colour bytes 0..5 (the network input)
+CUBE3_PDB_SLOTS = {CUBE3_CORNERS: (8, 3), CUBE3_EDGES: (12, 2)}  # kind -> (slots n, orientations o)
+
+
 def cube3_pdb_bytes(kind: int, k: int) -> int:
     """Bytes of one pattern's table, P(n, k) * o^k: a pure function (include/dca.h); DcaError outside its limits."""
     b = lib().dca_cube3_pdb_bytes(kind, k)
     check(min(b, 0), "dca_cube3_pdb_bytes")
     return b
+
+
+def _cube3_table_bytes(kind: int, k: int) -> Optional[int]:
+    if kind not in CUBE3_PDB_SLOTS or not 1 <= k <= 8:
+        return None
+    n, o = CUBE3_PDB_SLOTS[kind]
+    return math.perm(n, k) * o ** k
 
 
 def cube3_pdb_cubies(kind: int) -> np.ndarray:
@@ -555,38 +593,15 @@ def cube3_pdb_index(kind: int, cubies, rows: np.ndarray, row_kind: int) -> np.nd
 
 def cube3_pdb_build(kind: int, cubies, table: Optional[torch.Tensor] = None):
     """Fill (or allocate and fill) the device table of one pattern -> (table u8 [P(n,k) * o^k], sweeps).  Synchronises."""
-    cubies = _byte_list(cubies)
-    nbytes = cube3_pdb_bytes(kind, len(cubies))
-    if table is None:
-        table = torch.empty(nbytes, dtype=torch.uint8, device=require_gpu())
-    assert table.dtype == torch.uint8 and table.numel() == nbytes
-    sweeps = C.c_int(0)
-    check(lib().dca_cube3_pdb_build(kind, cubies.ctypes.data_as(C.c_void_p), len(cubies), ptr(table), C.byref(sweeps), stream_ptr()),
-          "dca_cube3_pdb_build")
-    return table, int(sweeps.value)
+    return _pdb_build("dca_cube3_pdb_build", cube3_pdb_bytes, kind, cubies, table)
 
 
 def cube3_pdb_eval(states: torch.Tensor, row_kind: int, patterns, tables, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Max of the patterns' table bytes per row -> f32 [n].  patterns: [(kind, cubies), ...]; states: uint8 device rows
     [n, >= 54] with unit byte stride (a strided view is fine); ANY bytes are in bounds (include/dca.h, the any-bytes rule)."""
-    states, n, ld = _pdb_rows(states, 54, "cube3_pdb_eval")
-    kinds = np.ascontiguousarray([kind for kind, _ in patterns], dtype=np.int32)
-    ks = np.ascontiguousarray([len(g) for _, g in patterns], dtype=np.int32)
-    flat = _byte_list([c for _, g in patterns for c in g])
-    if len(tables) != len(patterns):
-        raise ValueError("cube3_pdb_eval: %d tables for %d patterns" % (len(tables), len(patterns)))
-    for (kind, g), t in zip(patterns, tables):  # the library cannot see a table's size: a short one would be read past its end
-        if kind in CUBE3_PDB_SLOTS and 1 <= len(g) <= 8 and (t.dtype != torch.uint8 or t.numel() != cube3_pdb_bytes(kind, len(g))):
-            raise ValueError("cube3_pdb_eval: a table of %d elements for a pattern that needs %d bytes"
-                             % (t.numel(), cube3_pdb_bytes(kind, len(g))))
-    ptrs = (C.c_void_p * max(len(tables), 1))(*[ptr(t) for t in tables])
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=states.device)
-    assert out.dtype == torch.float32 and out.numel() >= n
-    check(lib().dca_cube3_pdb_eval(_raw(states), n, ld, row_kind, len(patterns), kinds.ctypes.data_as(C.c_void_p),
-                                   flat.ctypes.data_as(C.c_void_p), ks.ctypes.data_as(C.c_void_p), ptrs, ptr(out), stream_ptr()),
-          "dca_cube3_pdb_eval")
-    return out
+    return _pdb_eval("cube3_pdb_eval", "dca_cube3_pdb_eval", states, 54, [g for _, g in patterns], [kind for kind, _ in patterns],
+                     _cube3_table_bytes, tables, out,
+                     lambda s, n, ld, m, *rest: lib().dca_cube3_pdb_eval(s, n, ld, row_kind, m, *rest))
 
 
 # ------------------------------------------------------------------------------ training step

@@ -15,31 +15,12 @@
 //           One byte gather per pattern (up to four in flight), summed, written as fp32.
 //
 // What bounds either kernel has not been measured (profiles/pdb_probe.txt holds only wall-clock rates).
-#include "dca_common.h"
-#include "dca_pdb_row.h"
+#include "dca_pdb_shared.h"
 
 namespace dca {
 
-constexpr int kPdbThreads = 256;
-constexpr int kPdbMaxPatterns = 24;
-constexpr int kPdbMaxK = 8;            // N^(k+1) <= 2^34 allows k = 8 on puzzle8 (all tiles), fewer on every larger board
-constexpr int kPdbMaxBuildBlocks = 1 << 16;
-constexpr int kPdbMaxEvalBlocks = 1 << 14;
 constexpr int kPdbMaxSweeps = 1 << 16;
 constexpr uint8_t kPdbNoState = 0xFF;  // two digits equal
-constexpr uint8_t kPdbInf = 0xFE;      // a state the goal cannot be reached from (or: not reached yet, during the build)
-constexpr int64_t kPdbMaxBytes = (int64_t)1 << 34;
-
-struct PdbPattern {
-    uint8_t tiles[kPdbMaxK];
-};
-
-struct PdbSet {
-    const uint8_t* table[kPdbMaxPatterns];
-    PdbPattern pat[kPdbMaxPatterns];
-    uint8_t k[kPdbMaxPatterns];
-    int np;
-};
 
 // ---------------------------------------------------------------------------------------------------------------- build
 // entry -> 0xFF (two digits equal), 0 (the goal: tile t at t - 1, blank at N - 1) or "not reached yet"
@@ -58,7 +39,7 @@ __host__ __device__ inline uint8_t pdb_init_value(uint64_t e, int k, const PdbPa
             r /= N;
             distinct = distinct && !((seen >> p) & 1);
             seen |= 1ull << p;
-            goal = goal && p == (uint32_t)pat.tiles[j] - 1u;
+            goal = goal && p == (uint32_t)pat.id[j] - 1u;
         }
     return !distinct ? kPdbNoState : goal ? (uint8_t)0 : kPdbInf;
 }
@@ -127,49 +108,22 @@ __global__ __launch_bounds__(kPdbThreads) void pdb_sweep_kernel(uint8_t* table, 
     if (any) __hip_atomic_store(changed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-static unsigned pdb_blocks(uint64_t n, int cap) {
-    const uint64_t b = (n + kPdbThreads - 1) / kPdbThreads;
-    return (unsigned)(b < (uint64_t)cap ? b : (uint64_t)cap);
-}
-
 template <int DIM>
 static int pdb_build_launch(uint8_t* table, uint64_t total, int k, const PdbPattern& pat, int* sweeps, hipStream_t st) {
-    uint32_t* changed = nullptr;
-    DCA_HIP(hipMalloc((void**)&changed, sizeof(uint32_t)));
     const unsigned blocks = pdb_blocks(total, kPdbMaxBuildBlocks);
-    int rc = 0, done = 0;
     hipLaunchKernelGGL(pdb_init_kernel<DIM>, dim3(blocks), dim3(kPdbThreads), 0, st, table, total, k, pat);
-    rc = launch_check("pdb_init_kernel");
-    bool fixed = false;
-    while (rc == 0 && !fixed && done < kPdbMaxSweeps) {
-        uint32_t flag = 0;
-        hipError_t e = hipMemsetAsync(changed, 0, sizeof(uint32_t), st);
-        if (e != hipSuccess) {
-            rc = hip_fail(e, "hipMemsetAsync(pdb changed flag)");
-            break;
-        }
-        hipLaunchKernelGGL(pdb_sweep_kernel<DIM>, dim3(blocks), dim3(kPdbThreads), 0, st, table, total, k, changed);
-        if ((rc = launch_check("pdb_sweep_kernel")) != 0) break;
-        e = hipMemcpyAsync(&flag, changed, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            rc = hip_fail(e, "pdb changed flag read-back");
-            break;
-        }
-        done++;
-        fixed = flag == 0;
-    }
-    (void)hipFree(changed);
-    if (rc == 0 && !fixed) {
-        set_error("dca_pdb_build: no fixed point after %d sweeps", done);
-        return DCA_E_STATE;
-    }
+    int done = 0, rc = launch_check("pdb_init_kernel");
+    if (rc == 0)
+        rc = pdb_sweep_until_quiet(st, kPdbMaxSweeps, "dca_pdb_build", [&](int, uint32_t* changed) {
+            hipLaunchKernelGGL(pdb_sweep_kernel<DIM>, dim3(blocks), dim3(kPdbThreads), 0, st, table, total, k, changed);
+            return launch_check("pdb_sweep_kernel");
+        }, done);
+    if (rc == DCA_E_STATE) set_error("dca_pdb_build: no fixed point after %d sweeps", done);
     if (rc == 0 && sweeps) *sweeps = done;
     return rc;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- eval
-// (the row load, pdb_load_row, is shared with the cube3 tables: dca_pdb_row.h)
 // last position whose byte equals t, 0 if none (t < N is wave-uniform; a byte >= N equals no tile)
 template <int N>
 __host__ __device__ inline uint32_t pdb_find(const uint32_t (&w)[(N + 3) / 4], uint32_t t) {
@@ -179,51 +133,36 @@ __host__ __device__ inline uint32_t pdb_find(const uint32_t (&w)[(N + 3) / 4], u
     return pos;
 }
 
-// one row's value: the sum over the set's patterns of table[blank + N (pos(tile 0) + N (pos(tile 1) + ...))]
-template <int N>
-__host__ __device__ inline uint32_t pdb_row_value(const uint32_t (&w)[(N + 3) / 4], const PdbSet& set) {
-    const uint64_t blank = pdb_find<N>(w, 0u);
-    uint32_t sum = 0;
-    for (int p0 = 0; p0 < set.np; p0 += 4) {  // four independent gathers in flight
-        uint32_t v[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            v[q] = 0;
-            const int pi = p0 + q;
-            if (pi < set.np) {
-                const int k = set.k[pi];
-                uint64_t idx = 0;
-                for (int j = k - 1; j >= 0; j--) idx = idx * N + pdb_find<N>(w, set.pat[pi].tiles[j]);  // every digit < N
-                idx = idx * N + blank;                                                                    // < N^(k+1)
-                v[q] = set.table[pi][idx];
-            }
-        }
-        sum += v[0] + v[1] + v[2] + v[3];
-    }
-    return sum;
-}
-
-template <int DIM, int W>
-__global__ __launch_bounds__(kPdbThreads) void pdb_eval_kernel(const uint8_t* __restrict__ states, int64_t n, int64_t ld, PdbSet set,
-                                                               float* __restrict__ out) {
-    constexpr int N = DIM * DIM;
-    const int64_t stride = (int64_t)gridDim.x * kPdbThreads;
-    for (int64_t i = (int64_t)blockIdx.x * kPdbThreads + threadIdx.x; i < n; i += stride) {
-        uint32_t w[(N + 3) / 4];
-        pdb_load_row<N, W>(states + i * ld, w);
-        out[i] = (float)pdb_row_value<N>(w, set);  // <= 24 * 255: exact
-    }
-}
-
+// what pdb_eval_kernel / pdb_eval_launch (dca_pdb_shared.h) take for a DIM x DIM board
 template <int DIM>
-static int pdb_eval_launch(const uint8_t* states, int64_t n, int64_t ld, const PdbSet& set, float* out, hipStream_t st) {
-    const unsigned blocks = pdb_blocks((uint64_t)n, kPdbMaxEvalBlocks);
-    if ((((uintptr_t)states | (uintptr_t)ld) & 3) == 0)
-        hipLaunchKernelGGL((pdb_eval_kernel<DIM, 4>), dim3(blocks), dim3(kPdbThreads), 0, st, states, n, ld, set, out);
-    else
-        hipLaunchKernelGGL((pdb_eval_kernel<DIM, 1>), dim3(blocks), dim3(kPdbThreads), 0, st, states, n, ld, set, out);
-    return launch_check("pdb_eval_kernel");
-}
+struct PdbEval {
+    static constexpr int N = DIM * DIM;
+    using Set = PdbSet;
+    static constexpr const char* kernel_name = "pdb_eval_kernel";
+
+    // one row's value: the sum over the set's patterns of table[blank + N (pos(tile 0) + N (pos(tile 1) + ...))]
+    __host__ __device__ static inline uint32_t row_value(const uint32_t (&w)[(N + 3) / 4], const PdbSet& set) {
+        const uint64_t blank = pdb_find<N>(w, 0u);
+        uint32_t sum = 0;
+        for (int p0 = 0; p0 < set.np; p0 += 4) {  // four independent gathers in flight
+            uint32_t v[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                v[q] = 0;
+                const int pi = p0 + q;
+                if (pi < set.np) {
+                    const int k = set.k[pi];
+                    uint64_t idx = 0;
+                    for (int j = k - 1; j >= 0; j--) idx = idx * N + pdb_find<N>(w, set.pat[pi].id[j]);  // every digit < N
+                    idx = idx * N + blank;                                                               // < N^(k+1)
+                    v[q] = set.table[pi][idx];
+                }
+            }
+            sum += v[0] + v[1] + v[2] + v[3];
+        }
+        return sum;
+    }
+};
 
 // N^(k+1), or a negative code with the message set
 static int64_t pdb_bytes_checked(const char* who, int dim, int k) {
@@ -279,8 +218,7 @@ int dca_pdb_build(int dim, const uint8_t* tiles, int k, uint8_t* table, int* swe
     DCA_ARG(table != nullptr);
     uint64_t seen = 0;
     if (int rc = pdb_check_tiles(__func__, dim * dim, tiles, k, seen)) return rc;
-    PdbPattern pat{};
-    for (int j = 0; j < k; j++) pat.tiles[j] = tiles[j];
+    const PdbPattern pat = pdb_pattern(tiles, k);
     hipStream_t st = (hipStream_t)stream;
     switch (dim) {
         case 3: return pdb_build_launch<3>(table, (uint64_t)total, k, pat, sweeps, st);
@@ -303,32 +241,22 @@ int dca_pdb_eval(int dim, const uint8_t* states, int64_t n, int64_t ld, int num_
     DCA_ARG(num_patterns >= 1 && num_patterns <= 24);
     DCA_ARG(tiles != nullptr && ks != nullptr && tables != nullptr);
     PdbSet set{};
-    set.np = num_patterns;
-    uint64_t seen = 0;
-    const uint8_t* t = tiles;
-    for (int p = 0; p < num_patterns; p++) {
-        const int64_t b = pdb_bytes_checked(__func__, dim, ks[p]);
-        if (b < 0) return (int)b;
-        if (int rc = pdb_check_tiles(__func__, N, t, ks[p], seen)) return rc;
-        if (tables[p] == nullptr) {
-            set_error("bad argument: %s: tables: table %d is NULL", __func__, p);
-            return DCA_E_BADARG;
-        }
-        set.table[p] = tables[p];
-        set.k[p] = (uint8_t)ks[p];
-        for (int j = 0; j < ks[p]; j++) set.pat[p].tiles[j] = t[j];
-        t += ks[p];
-    }
+    uint64_t seen = 0;  // across the whole set: the patterns are disjoint
+    const char* who = __func__;
+    if (int rc = pdb_fill_set(
+            who, set, num_patterns, tiles, ks, tables, [&](int p) { return pdb_bytes_checked(who, dim, ks[p]); },
+            [&](int p, const uint8_t* t) { return pdb_check_tiles(who, N, t, ks[p], seen); }))
+        return rc;
     if (n == 0) return 0;
     DCA_ARG(states != nullptr && out != nullptr);
     DCA_ARG(((uintptr_t)out & 3) == 0);
     hipStream_t st = (hipStream_t)stream;
     switch (dim) {
-        case 3: return pdb_eval_launch<3>(states, n, ld, set, out, st);
-        case 4: return pdb_eval_launch<4>(states, n, ld, set, out, st);
-        case 5: return pdb_eval_launch<5>(states, n, ld, set, out, st);
-        case 6: return pdb_eval_launch<6>(states, n, ld, set, out, st);
-        default: return pdb_eval_launch<7>(states, n, ld, set, out, st);
+        case 3: return pdb_eval_launch<PdbEval<3>>(states, n, ld, set, out, st);
+        case 4: return pdb_eval_launch<PdbEval<4>>(states, n, ld, set, out, st);
+        case 5: return pdb_eval_launch<PdbEval<5>>(states, n, ld, set, out, st);
+        case 6: return pdb_eval_launch<PdbEval<6>>(states, n, ld, set, out, st);
+        default: return pdb_eval_launch<PdbEval<7>>(states, n, ld, set, out, st);
     }
 }
 

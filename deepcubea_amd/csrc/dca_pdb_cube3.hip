@@ -16,20 +16,12 @@
 //           index inside the table.  One byte gather per pattern, four in flight, max, written as fp32.
 //
 // What bounds either kernel has not been measured (profiles/cube3_pdb_probe.txt holds only wall-clock times).
-#include "dca_common.h"
-#include "dca_pdb_row.h"
+#include "dca_pdb_shared.h"
 
 namespace dca {
 
-constexpr int kC3Threads = 256;
-constexpr int kC3MaxPatterns = 24;
-constexpr int kC3MaxK = 8;
-constexpr int kC3MaxBuildBlocks = 1 << 16;
-constexpr int kC3MaxEvalBlocks = 1 << 14;
 constexpr int kC3MaxSweeps = 64;  // far above any pattern's depth, far below the 0xFE byte
-constexpr uint8_t kC3Inf = 0xFE;
-constexpr int64_t kC3MaxBytes = (int64_t)1 << 34;
-constexpr int kC3Locs = 24;  // n * o of either kind: 8 * 3 corners, 12 * 2 edges
+constexpr int kC3Locs = 24;       // n * o of either kind: 8 * 3 corners, 12 * 2 edges
 
 template <int KIND>
 struct C3Kind {
@@ -87,15 +79,8 @@ static_assert(kC3.pos[0][0] == 0 && kC3.pos[0][1] == 26 && kC3.pos[0][2] == 47 &
               "corner lists");
 static_assert(kC3.pos[1][0] == 1 && kC3.pos[1][1] == 23 && kC3.pos[1][22] == 34 && kC3.pos[1][23] == 37, "edge lists");
 
-struct C3Pattern {
-    uint8_t cubies[kC3MaxK];
-};
-
-struct C3Set {
-    const uint8_t* table[kC3MaxPatterns];
-    C3Pattern pat[kC3MaxPatterns];
-    uint8_t k[kC3MaxPatterns];
-    uint8_t kind[kC3MaxPatterns];
+struct C3Set : PdbTables {
+    uint8_t kind[kPdbMaxPatterns];
     int np;
     int kinds_used;  // bit kind = some pattern is of that kind
 };
@@ -108,11 +93,11 @@ struct C3MoveTable {
 // index of k locations (slot * o + r each, < 24): include/dca.h "index rule".  A digit is clamped below its radix, so locations
 // that are no partial permutation (any-bytes rule) still give an index inside the table.
 template <int KIND>
-__host__ __device__ inline uint64_t c3_rank(const uint32_t (&loc)[kC3MaxK], int k) {
+__host__ __device__ inline uint64_t c3_rank(const uint32_t (&loc)[kPdbMaxK], int k) {
     constexpr int n = C3Kind<KIND>::n, o = C3Kind<KIND>::o;
     uint32_t seen = 0, rank = 0, orient = 0, ok = 1;
 #pragma unroll
-    for (int j = 0; j < kC3MaxK; j++)
+    for (int j = 0; j < kPdbMaxK; j++)
         if (j < k) {
             const uint32_t s = loc[j] / o, r = loc[j] - s * o;
             uint32_t d = s - (uint32_t)__builtin_popcount(seen & ((1u << s) - 1u));
@@ -127,11 +112,11 @@ __host__ __device__ inline uint64_t c3_rank(const uint32_t (&loc)[kC3MaxK], int 
 
 // the k locations of table entry e (every entry is a partial permutation with orientations: no invalid indices)
 template <int KIND, typename IdxT>
-__host__ __device__ inline void c3_unrank(IdxT e, int k, uint32_t (&loc)[kC3MaxK]) {
+__host__ __device__ inline void c3_unrank(IdxT e, int k, uint32_t (&loc)[kPdbMaxK]) {
     constexpr int n = C3Kind<KIND>::n, o = C3Kind<KIND>::o;
-    uint32_t r[kC3MaxK], s[kC3MaxK];
+    uint32_t r[kPdbMaxK], s[kPdbMaxK];
 #pragma unroll
-    for (int j = kC3MaxK - 1; j >= 0; j--) {
+    for (int j = kPdbMaxK - 1; j >= 0; j--) {
         r[j] = 0;
         if (j < k) {
             r[j] = (uint32_t)(e % (IdxT)o);
@@ -140,7 +125,7 @@ __host__ __device__ inline void c3_unrank(IdxT e, int k, uint32_t (&loc)[kC3MaxK
     }
     uint32_t rank = (uint32_t)e;
 #pragma unroll
-    for (int j = kC3MaxK - 1; j >= 0; j--) {
+    for (int j = kPdbMaxK - 1; j >= 0; j--) {
         s[j] = 0;
         if (j < k) {
             s[j] = rank % (uint32_t)(n - j);
@@ -149,17 +134,17 @@ __host__ __device__ inline void c3_unrank(IdxT e, int k, uint32_t (&loc)[kC3MaxK
     }
     // digits -> slots: d_j counts the slots below s_j that are still free after cubies 0 .. j-1 took theirs
 #pragma unroll
-    for (int i = kC3MaxK - 2; i >= 0; i--)
+    for (int i = kPdbMaxK - 2; i >= 0; i--)
 #pragma unroll
-        for (int j = i + 1; j < kC3MaxK; j++)
+        for (int j = i + 1; j < kPdbMaxK; j++)
             if (j < k && s[j] >= s[i]) s[j]++;
 #pragma unroll
-    for (int j = 0; j < kC3MaxK; j++) loc[j] = j < k ? s[j] * o + r[j] : 0u;
+    for (int j = 0; j < kPdbMaxK; j++) loc[j] = j < k ? s[j] * o + r[j] : 0u;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- build
 template <int KIND, typename IdxT>
-__global__ __launch_bounds__(kC3Threads) void c3_sweep_kernel(uint8_t* table, uint64_t total, int k, uint32_t depth, C3MoveTable mt,
+__global__ __launch_bounds__(kPdbThreads) void c3_sweep_kernel(uint8_t* table, uint64_t total, int k, uint32_t depth, C3MoveTable mt,
                                                               uint32_t* __restrict__ filled) {
     __shared__ uint32_t mvw[12 * kC3Locs / 4];
     if (threadIdx.x == 0) {  // (constant indices into the kernel argument: scalar loads, no private copy of the struct)
@@ -168,11 +153,11 @@ __global__ __launch_bounds__(kC3Threads) void c3_sweep_kernel(uint8_t* table, ui
     }
     __syncthreads();
     const uint8_t* mv = (const uint8_t*)mvw;
-    const uint64_t stride = (uint64_t)gridDim.x * kC3Threads;
+    const uint64_t stride = (uint64_t)gridDim.x * kPdbThreads;
     bool any = false;
-    for (uint64_t e = (uint64_t)blockIdx.x * kC3Threads + threadIdx.x; e < total; e += stride) {
-        if (__hip_atomic_load(table + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kC3Inf) continue;
-        uint32_t loc[kC3MaxK];
+    for (uint64_t e = (uint64_t)blockIdx.x * kPdbThreads + threadIdx.x; e < total; e += stride) {
+        if (__hip_atomic_load(table + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kPdbInf) continue;
+        uint32_t loc[kPdbMaxK];
         c3_unrank<KIND, IdxT>((IdxT)e, k, loc);
         bool hit = false;
 #pragma unroll
@@ -180,9 +165,9 @@ __global__ __launch_bounds__(kC3Threads) void c3_sweep_kernel(uint8_t* table, ui
             uint32_t v[4];
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                uint32_t nl[kC3MaxK];
+                uint32_t nl[kPdbMaxK];
 #pragma unroll
-                for (int j = 0; j < kC3MaxK; j++) nl[j] = j < k ? (uint32_t)mv[(a0 + q) * kC3Locs + loc[j]] : 0u;  // loc < 24
+                for (int j = 0; j < kPdbMaxK; j++) nl[j] = j < k ? (uint32_t)mv[(a0 + q) * kC3Locs + loc[j]] : 0u;  // loc < 24
                 const uint64_t ne = c3_rank<KIND>(nl, k);  // a move permutes locations: distinct slots stay distinct, ne < total
                 v[q] = __hip_atomic_load(table + ne, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -196,55 +181,28 @@ __global__ __launch_bounds__(kC3Threads) void c3_sweep_kernel(uint8_t* table, ui
     if (any) __hip_atomic_store(filled, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-static unsigned c3_blocks(uint64_t n, int cap) {
-    const uint64_t b = (n + kC3Threads - 1) / kC3Threads;
-    return (unsigned)(b < (uint64_t)cap ? b : (uint64_t)cap);
-}
-
 template <int KIND>
-static int c3_build_launch(uint8_t* table, uint64_t total, int k, const C3Pattern& pat, int* sweeps, hipStream_t st) {
+static int c3_build_launch(uint8_t* table, uint64_t total, int k, const PdbPattern& pat, int* sweeps, hipStream_t st) {
     constexpr int o = C3Kind<KIND>::o;
-    uint32_t home[kC3MaxK] = {};
-    for (int j = 0; j < k; j++) home[j] = (uint32_t)pat.cubies[j] * o;
+    uint32_t home[kPdbMaxK] = {};
+    for (int j = 0; j < k; j++) home[j] = (uint32_t)pat.id[j] * o;
     const uint64_t goal = c3_rank<KIND>(home, k);
     C3MoveTable mt{};
     for (int a = 0; a < 12; a++)
         for (int l = 0; l < kC3Locs; l++) mt.w[(a * kC3Locs + l) >> 2] |= (uint32_t)kC3.move[KIND][a][l] << (8 * (l & 3));
-    uint32_t* filled = nullptr;
-    DCA_HIP(hipMalloc((void**)&filled, sizeof(uint32_t)));
-    const unsigned blocks = c3_blocks(total, kC3MaxBuildBlocks);
-    int rc = 0, done = 0;
-    hipError_t e = hipMemsetAsync(table, kC3Inf, total, st);
+    const unsigned blocks = pdb_blocks(total, kPdbMaxBuildBlocks);
+    hipError_t e = hipMemsetAsync(table, kPdbInf, total, st);
     if (e == hipSuccess) e = hipMemsetAsync(table + goal, 0, 1, st);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemsetAsync(cube3 pdb table)");
-    bool complete = false;
-    while (rc == 0 && !complete && done < kC3MaxSweeps) {
-        uint32_t flag = 0;
-        e = hipMemsetAsync(filled, 0, sizeof(uint32_t), st);
-        if (e != hipSuccess) {
-            rc = hip_fail(e, "hipMemsetAsync(cube3 pdb filled flag)");
-            break;
-        }
-        const uint32_t depth = (uint32_t)done + 1;
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(cube3 pdb table)");
+    int done = 0;
+    const int rc = pdb_sweep_until_quiet(st, kC3MaxSweeps, "dca_cube3_pdb_build", [&](int depth, uint32_t* filled) {
         if (total <= 0xFFFFFFFFull)
-            hipLaunchKernelGGL((c3_sweep_kernel<KIND, uint32_t>), dim3(blocks), dim3(kC3Threads), 0, st, table, total, k, depth, mt, filled);
+            hipLaunchKernelGGL((c3_sweep_kernel<KIND, uint32_t>), dim3(blocks), dim3(kPdbThreads), 0, st, table, total, k, (uint32_t)depth, mt, filled);
         else
-            hipLaunchKernelGGL((c3_sweep_kernel<KIND, uint64_t>), dim3(blocks), dim3(kC3Threads), 0, st, table, total, k, depth, mt, filled);
-        if ((rc = launch_check("c3_sweep_kernel")) != 0) break;
-        e = hipMemcpyAsync(&flag, filled, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            rc = hip_fail(e, "cube3 pdb filled flag read-back");
-            break;
-        }
-        done++;
-        complete = flag == 0;
-    }
-    (void)hipFree(filled);
-    if (rc == 0 && !complete) {
-        set_error("dca_cube3_pdb_build: levels still filling after %d sweeps", done);
-        return DCA_E_STATE;
-    }
+            hipLaunchKernelGGL((c3_sweep_kernel<KIND, uint64_t>), dim3(blocks), dim3(kPdbThreads), 0, st, table, total, k, (uint32_t)depth, mt, filled);
+        return launch_check("c3_sweep_kernel");
+    }, done);
+    if (rc == DCA_E_STATE) set_error("dca_cube3_pdb_build: levels still filling after %d sweeps", done);
     if (rc == 0 && sweeps) *sweeps = done;
     return rc;
 }
@@ -287,57 +245,44 @@ __host__ __device__ inline uint64_t c3_row_locs(const uint32_t (&w)[14]) {
 }
 
 template <int KIND>
-__host__ __device__ inline uint64_t c3_index(uint64_t locs, const C3Pattern& pat, int k) {
-    uint32_t loc[kC3MaxK];
+__host__ __device__ inline uint64_t c3_index(uint64_t locs, const PdbPattern& pat, int k) {
+    uint32_t loc[kPdbMaxK];
 #pragma unroll
-    for (int j = 0; j < kC3MaxK; j++) loc[j] = j < k ? (uint32_t)(locs >> (5 * pat.cubies[j])) & 31u : 0u;  // cubie < 12, location < 24
+    for (int j = 0; j < kPdbMaxK; j++) loc[j] = j < k ? (uint32_t)(locs >> (5 * pat.id[j])) & 31u : 0u;  // cubie < 12, location < 24
     return c3_rank<KIND>(loc, k);
 }
 
+// what pdb_eval_kernel / pdb_eval_launch (dca_pdb_shared.h) take for rows of sticker ids or of colours
 template <int ROWS>
-__host__ __device__ inline uint32_t c3_row_value(const uint32_t (&w)[14], const C3Set& set) {
-    const uint64_t corner = (set.kinds_used & 1) ? c3_row_locs<DCA_CUBE3_CORNERS, ROWS>(w) : 0ull;
-    const uint64_t edge = (set.kinds_used & 2) ? c3_row_locs<DCA_CUBE3_EDGES, ROWS>(w) : 0ull;
-    uint32_t best = 0;
-    for (int p0 = 0; p0 < set.np; p0 += 4) {  // four independent gathers in flight
-        uint32_t v[4];
+struct C3Eval {
+    static constexpr int N = 54;
+    using Set = C3Set;
+    static constexpr const char* kernel_name = "c3_eval_kernel";
+
+    // one row's value: the largest of the set's patterns' table bytes
+    __host__ __device__ static inline uint32_t row_value(const uint32_t (&w)[14], const C3Set& set) {
+        const uint64_t corner = (set.kinds_used & 1) ? c3_row_locs<DCA_CUBE3_CORNERS, ROWS>(w) : 0ull;
+        const uint64_t edge = (set.kinds_used & 2) ? c3_row_locs<DCA_CUBE3_EDGES, ROWS>(w) : 0ull;
+        uint32_t best = 0;
+        for (int p0 = 0; p0 < set.np; p0 += 4) {  // four independent gathers in flight
+            uint32_t v[4];
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-            v[q] = 0;
-            const int pi = p0 + q;
-            if (pi < set.np) {
-                const uint64_t idx = set.kind[pi] == DCA_CUBE3_CORNERS ? c3_index<DCA_CUBE3_CORNERS>(corner, set.pat[pi], set.k[pi])
-                                                                       : c3_index<DCA_CUBE3_EDGES>(edge, set.pat[pi], set.k[pi]);
-                v[q] = set.table[pi][idx];
+            for (int q = 0; q < 4; q++) {
+                v[q] = 0;
+                const int pi = p0 + q;
+                if (pi < set.np) {
+                    const uint64_t idx = set.kind[pi] == DCA_CUBE3_CORNERS ? c3_index<DCA_CUBE3_CORNERS>(corner, set.pat[pi], set.k[pi])
+                                                                           : c3_index<DCA_CUBE3_EDGES>(edge, set.pat[pi], set.k[pi]);
+                    v[q] = set.table[pi][idx];
+                }
             }
+            const uint32_t a = v[0] > v[1] ? v[0] : v[1], b = v[2] > v[3] ? v[2] : v[3];
+            best = best > a ? best : a;
+            best = best > b ? best : b;
         }
-        const uint32_t a = v[0] > v[1] ? v[0] : v[1], b = v[2] > v[3] ? v[2] : v[3];
-        best = best > a ? best : a;
-        best = best > b ? best : b;
+        return best;
     }
-    return best;
-}
-
-template <int ROWS, int W>
-__global__ __launch_bounds__(kC3Threads) void c3_eval_kernel(const uint8_t* __restrict__ states, int64_t n, int64_t ld, C3Set set,
-                                                             float* __restrict__ out) {
-    const int64_t stride = (int64_t)gridDim.x * kC3Threads;
-    for (int64_t i = (int64_t)blockIdx.x * kC3Threads + threadIdx.x; i < n; i += stride) {
-        uint32_t w[14];
-        pdb_load_row<54, W>(states + i * ld, w);
-        out[i] = (float)c3_row_value<ROWS>(w, set);  // <= 255: exact
-    }
-}
-
-template <int ROWS>
-static int c3_eval_launch(const uint8_t* states, int64_t n, int64_t ld, const C3Set& set, float* out, hipStream_t st) {
-    const unsigned blocks = c3_blocks((uint64_t)n, kC3MaxEvalBlocks);
-    if ((((uintptr_t)states | (uintptr_t)ld) & 3) == 0)
-        hipLaunchKernelGGL((c3_eval_kernel<ROWS, 4>), dim3(blocks), dim3(kC3Threads), 0, st, states, n, ld, set, out);
-    else
-        hipLaunchKernelGGL((c3_eval_kernel<ROWS, 1>), dim3(blocks), dim3(kC3Threads), 0, st, states, n, ld, set, out);
-    return launch_check("c3_eval_kernel");
-}
+};
 
 // ---------------------------------------------------------------------------------------------------------------- checks
 // P(n, k) * o^k, or a negative code with the message set
@@ -346,14 +291,14 @@ static int64_t c3_bytes_checked(const char* who, int kind, int k) {
         set_error("bad argument: %s: kind = %d is neither 0 (corners) nor 1 (edges)", who, kind);
         return DCA_E_BADARG;
     }
-    if (k < 1 || k > kC3MaxK) {
-        set_error("bad argument: %s: k = %d is not in 1..%d", who, k, kC3MaxK);
+    if (k < 1 || k > kPdbMaxK) {
+        set_error("bad argument: %s: k = %d is not in 1..%d", who, k, kPdbMaxK);
         return DCA_E_BADARG;
     }
     const int n = kind == DCA_CUBE3_CORNERS ? 8 : 12, o = kind == DCA_CUBE3_CORNERS ? 3 : 2;
     int64_t b = 1;
     for (int j = 0; j < k; j++) b *= (int64_t)(n - j) * o;  // <= 12^8 * 2^8: no overflow
-    if (b > kC3MaxBytes) {
+    if (b > kPdbMaxBytes) {
         set_error("bad argument: %s: k = %d: a table of %lld bytes is over the 2^34 limit", who, k, (long long)b);
         return DCA_E_BADARG;
     }
@@ -379,7 +324,7 @@ static int c3_check_cubies(const char* who, int kind, const uint8_t* cubies, int
 }
 
 template <int ROWS>
-static int64_t c3_host_index(int kind, const C3Pattern& pat, int k, const uint8_t* row) {
+static int64_t c3_host_index(int kind, const PdbPattern& pat, int k, const uint8_t* row) {
     uint32_t w[14];
     pdb_load_row<54, 1>(row, w);
     return kind == DCA_CUBE3_CORNERS ? (int64_t)c3_index<DCA_CUBE3_CORNERS>(c3_row_locs<DCA_CUBE3_CORNERS, ROWS>(w), pat, k)
@@ -412,9 +357,8 @@ int dca_cube3_pdb_index(int kind, const uint8_t* cubies, int k, const uint8_t* r
     DCA_ARG(row_kind == DCA_ROWS_STATE || row_kind == DCA_ROWS_NNET);
     DCA_ARG(index != nullptr);
     if (int rc = c3_check_cubies(__func__, kind, cubies, k)) return rc;
-    C3Pattern pat{};
-    for (int j = 0; j < k; j++) pat.cubies[j] = cubies[j];
-    *index = row_kind == DCA_ROWS_STATE ? c3_host_index<DCA_ROWS_STATE>(kind, pat, k, row) : c3_host_index<DCA_ROWS_NNET>(kind, pat, k, row);
+    const PdbPattern pat = pdb_pattern(cubies, k);
+    *index =row_kind == DCA_ROWS_STATE ? c3_host_index<DCA_ROWS_STATE>(kind, pat, k, row) : c3_host_index<DCA_ROWS_NNET>(kind, pat, k, row);
     return 0;
 }
 
@@ -424,8 +368,7 @@ int dca_cube3_pdb_build(int kind, const uint8_t* cubies, int k, uint8_t* table, 
     DCA_ARG(cubies != nullptr);
     DCA_ARG(table != nullptr);
     if (int rc = c3_check_cubies(__func__, kind, cubies, k)) return rc;
-    C3Pattern pat{};
-    for (int j = 0; j < k; j++) pat.cubies[j] = cubies[j];
+    const PdbPattern pat = pdb_pattern(cubies, k);
     hipStream_t st = (hipStream_t)stream;
     return kind == DCA_CUBE3_CORNERS ? c3_build_launch<DCA_CUBE3_CORNERS>(table, (uint64_t)total, k, pat, sweeps, st)
                                      : c3_build_launch<DCA_CUBE3_EDGES>(table, (uint64_t)total, k, pat, sweeps, st);
@@ -439,29 +382,21 @@ int dca_cube3_pdb_eval(const uint8_t* states, int64_t n, int64_t ld, int row_kin
     DCA_ARG(num_patterns >= 1 && num_patterns <= 24);
     DCA_ARG(kinds != nullptr && cubies != nullptr && ks != nullptr && tables != nullptr);
     C3Set set{};
-    set.np = num_patterns;
-    const uint8_t* c = cubies;
+    const char* who = __func__;
+    if (int rc = pdb_fill_set(
+            who, set, num_patterns, cubies, ks, tables, [&](int p) { return c3_bytes_checked(who, kinds[p], ks[p]); },
+            [&](int p, const uint8_t* c) { return c3_check_cubies(who, kinds[p], c, ks[p]); }))
+        return rc;
     for (int p = 0; p < num_patterns; p++) {
-        const int64_t b = c3_bytes_checked(__func__, kinds[p], ks[p]);
-        if (b < 0) return (int)b;
-        if (int rc = c3_check_cubies(__func__, kinds[p], c, ks[p])) return rc;
-        if (tables[p] == nullptr) {
-            set_error("bad argument: %s: tables: table %d is NULL", __func__, p);
-            return DCA_E_BADARG;
-        }
-        set.table[p] = tables[p];
-        set.k[p] = (uint8_t)ks[p];
         set.kind[p] = (uint8_t)kinds[p];
         set.kinds_used |= 1 << kinds[p];
-        for (int j = 0; j < ks[p]; j++) set.pat[p].cubies[j] = c[j];
-        c += ks[p];
     }
     if (n == 0) return 0;
     DCA_ARG(states != nullptr && out != nullptr);
     DCA_ARG(((uintptr_t)out & 3) == 0);
     hipStream_t st = (hipStream_t)stream;
-    return row_kind == DCA_ROWS_STATE ? c3_eval_launch<DCA_ROWS_STATE>(states, n, ld, set, out, st)
-                                      : c3_eval_launch<DCA_ROWS_NNET>(states, n, ld, set, out, st);
+    return row_kind == DCA_ROWS_STATE ? pdb_eval_launch<C3Eval<DCA_ROWS_STATE>>(states, n, ld, set, out, st)
+                                      : pdb_eval_launch<C3Eval<DCA_ROWS_NNET>>(states, n, ld, set, out, st);
 }
 
 }  // extern "C"

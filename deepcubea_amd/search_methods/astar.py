@@ -49,34 +49,30 @@ def _is_pdb(args) -> bool:
     return str(getattr(args, "model_dir", "")).startswith("pdb:")
 
 
+def _pattern_database(args):
+    """`--model_dir pdb:SPEC`, no network: additive tables for the sliding puzzles (utils/pattern_db.py), corner / edge tables
+    combined by max for cube3 (utils/cube3_pdb.py).  Not built yet; ValueError for a spec the environment cannot have."""
+    spec = str(args.model_dir).split(":", 1)[1]
+    if str(args.env).lower() == "cube3":
+        from ..utils.cube3_pdb import Cube3PatternDatabase
+        return Cube3PatternDatabase(spec)
+    from ..utils.pattern_db import PatternDatabase
+    return PatternDatabase(args.env, spec)
+
+
 def _load_heuristic(args, env):
     """Device heuristic closure.  `--model_dir synthetic:SEED` builds the environment's network with
     deterministic synthetic weights (the reference checkpoints are not redistributable here)."""
-    if _is_pdb(args):
-        # no network: pattern databases — additive ones for the sliding puzzles (utils/pattern_db.py), corner / edge tables
-        # combined by max for cube3 (utils/cube3_pdb.py).  The spec is checked before any device work; the closure reads the
-        # packed uint8 rows of the dedup-first path (stride 0 = no one-hot rows)
-        spec = str(args.model_dir).split(":", 1)[1]
-        if str(args.env).lower() == "cube3":
-            from ..utils.cube3_pdb import Cube3PatternDatabase, parse_cube3_pdb_spec
-            partition = parse_cube3_pdb_spec(spec)
-        else:
-            from ..utils.pattern_db import PatternDatabase, parse_pdb_spec
-            partition = parse_pdb_spec(args.env, spec)
+    pdb = _pattern_database(args) if _is_pdb(args) else None  # the spec is checked here, before any device work
     device, devices, on_gpu = nnet_utils.get_device()
     print("device: %s, devices: %s, on_gpu: %s" % (device, devices, on_gpu))
     if not on_gpu:
         raise _lib.DcaError("--language hip needs an MI355X: no HIP device visible")
-    if _is_pdb(args):
+    if pdb is not None:
         start = time.time()
-        if str(args.env).lower() == "cube3":
-            pdb = Cube3PatternDatabase(partition).build()
-            name = pdb.spec
-        else:
-            pdb = PatternDatabase(args.env, partition).build()
-            name = "/".join(",".join(str(t) for t in g) for g in pdb.partition)
-        print("pattern database %s: %d bytes, sweeps %s, built in %.2f s" % (name, pdb.bytes, pdb.sweeps, time.time() - start))
-        return pdb.heuristic_fn_dev(), 0
+        pdb.build()
+        print("pattern database %s: %d bytes, sweeps %s, built in %.2f s" % (pdb.spec, pdb.bytes, pdb.sweeps, time.time() - start))
+        return pdb.heuristic_fn_dev(), 0  # the closure reads the packed uint8 rows of the dedup-first path (stride 0 = no one-hot rows)
     nnet = env.get_nnet_model()
     if str(args.model_dir).startswith("synthetic:"):
         from ..utils.synthetic_weights import load_synthetic_weights

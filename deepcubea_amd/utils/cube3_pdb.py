@@ -9,12 +9,12 @@ from __future__ import annotations
 
 import re
 from math import perm
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Tuple
 
-import numpy as np
 import torch
 
 from .. import _lib
+from .pattern_db import _TableSet
 
 Pattern = Tuple[int, Tuple[int, ...]]
 PatternSet = Tuple[Pattern, ...]
@@ -86,90 +86,35 @@ def table_bytes(patterns: PatternSet) -> List[int]:
     return [pattern_bytes(kind, len(g)) for kind, g in patterns]
 
 
-class Cube3PatternDatabase:
-    """The tables of one pattern set on the current device.  build() fills them one pattern after another; save() / load() keep
-    them in an .npz; heuristic_fn_dev() is the closure BwasEngine.step calls (it reads the network-input colour rows)."""
+class Cube3PatternDatabase(_TableSet):
+    """The tables of one cube3 pattern set, combined by max; the engine's closure reads the network-input colour rows."""
 
     env_name = "cube3"
+    _engine_rows = "network-input"
 
     def __init__(self, patterns):
+        super().__init__()
         self.patterns = parse_cube3_pdb_spec(patterns) if isinstance(patterns, str) else check_patterns(patterns)
-        self.tables: List[torch.Tensor] = []
-        self.sweeps: List[int] = []
 
     @property
     def spec(self) -> str:
         return spec_of(self.patterns)
 
-    @property
-    def bytes(self) -> int:
-        return sum(table_bytes(self.patterns))
+    def _table_bytes(self) -> List[int]:
+        return table_bytes(self.patterns)
 
-    def build(self) -> "Cube3PatternDatabase":
-        _lib.require_gpu()
-        self.tables, self.sweeps = [], []
-        for kind, group in self.patterns:
-            table, sweeps = _lib.cube3_pdb_build(kind, group)
-            self.tables.append(table)
-            self.sweeps.append(sweeps)
-        return self
-
-    def set_tables(self, tables: Sequence[np.ndarray]) -> "Cube3PatternDatabase":
-        """Adopt host-made tables (one uint8 array of P(n, k) * o^k bytes per pattern)."""
-        want = table_bytes(self.patterns)
-        if len(tables) != len(want):
-            raise ValueError("%d tables for %d patterns" % (len(tables), len(want)))
-        host = [np.ascontiguousarray(t, dtype=np.uint8).reshape(-1) for t in tables]
-        for t, b in zip(host, want):
-            if t.size != b:
-                raise ValueError("a table of %d bytes where the pattern needs %d" % (t.size, b))
-        dev = _lib.require_gpu()
-        self.tables = [torch.from_numpy(t if t.flags.writeable else t.copy()).to(dev) for t in host]
-        self.sweeps = [0] * len(host)
-        return self
+    def _build_one(self, i: int):
+        return _lib.cube3_pdb_build(*self.patterns[i])
 
     def heuristic(self, states: torch.Tensor, row_kind: int = _lib.ROWS_STATE) -> torch.Tensor:
-        if len(self.tables) != len(self.patterns):
-            raise _lib.DcaError("Cube3PatternDatabase: build() or load() first")
+        self._ready("build() or load() first")
         return _lib.cube3_pdb_eval(states, row_kind, self.patterns, self.tables)
 
-    def heuristic_fn_dev(self):
-        """(uint8 colour rows [m, 54] on the device, is_onehot=False) -> float32 [m]: the closure form of BwasEngine.step /
-        solve, which hand a cube3 closure the network-input rows (sticker // 9)."""
-        def fn(states: torch.Tensor, is_onehot: bool = False) -> torch.Tensor:
-            if is_onehot:
-                raise ValueError("a pattern database reads the uint8 network-input rows, not one-hot rows")
-            return self.heuristic(states, _lib.ROWS_NNET)
-        return fn
-
-    def save(self, path: str, tables: Optional[Sequence[np.ndarray]] = None) -> None:
-        """Write the pattern set and the tables to an .npz (`tables`: host arrays to write instead of the device's)."""
-        if tables is None:
-            if len(self.tables) != len(self.patterns):
-                raise _lib.DcaError("Cube3PatternDatabase: nothing to save, build() first")
-            tables = [t.cpu().numpy() for t in self.tables]
-        want = table_bytes(self.patterns)
-        if [int(np.asarray(t).size) for t in tables] != want:
-            raise ValueError("table sizes %s, the pattern set needs %s" % ([int(np.asarray(t).size) for t in tables], want))
-        arrays = {"table_%d" % i: np.ascontiguousarray(t, dtype=np.uint8).reshape(-1) for i, t in enumerate(tables)}
-        arrays["env_name"] = np.array(self.env_name)
-        arrays["partition"] = np.array(self.spec)
-        with open(path, "wb") as f:
-            np.savez(f, **arrays)
+    def _engine_heuristic(self, states: torch.Tensor) -> torch.Tensor:
+        return self.heuristic(states, _lib.ROWS_NNET)  # BwasEngine.step / solve hand a cube3 closure the rows sticker // 9
 
     @classmethod
-    def load_host(cls, path: str):
-        """-> (Cube3PatternDatabase without device tables, [host tables]); needs no device."""
-        with np.load(path) as z:
-            if str(z["env_name"]) != cls.env_name:
-                raise ValueError("%s holds tables of %s, not of cube3" % (path, z["env_name"]))
-            pdb = cls(str(z["partition"]))
-            tables = [z["table_%d" % i] for i in range(len(pdb.patterns))]
-        if [int(t.size) for t in tables] != table_bytes(pdb.patterns):
-            raise ValueError("%s: table sizes do not match the pattern set" % path)
-        return pdb, tables
-
-    @classmethod
-    def load(cls, path: str) -> "Cube3PatternDatabase":
-        pdb, tables = cls.load_host(path)
-        return pdb.set_tables(tables)
+    def _from_header(cls, path: str, env_name: str, spec: str):
+        if env_name != cls.env_name:
+            raise ValueError("%s holds tables of %s, not of cube3" % (path, env_name))
+        return cls(spec)

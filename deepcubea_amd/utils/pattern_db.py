@@ -88,33 +88,32 @@ def table_bytes(dim: int, partition: Partition) -> List[int]:
     return [(dim * dim) ** (len(g) + 1) for g in partition]
 
 
-class PatternDatabase:
-    """The tables of one partition on the current device.  build() fills them one pattern after another; save() / load() keep
-    them in an .npz (a 6-6-6-6 set need not be rebuilt); heuristic_fn_dev() is the closure BwasEngine.step calls."""
+class _TableSet:
+    """What the pattern databases of every family share (PatternDatabase below, cube3_pdb.Cube3PatternDatabase): the tables of
+    one pattern set on the current device.  build() fills them one pattern after another; save() / load() keep them in an .npz;
+    heuristic_fn_dev() is the closure BwasEngine.step calls.  A family supplies env_name, spec (the string save() writes),
+    _table_bytes(), _build_one(i), _engine_heuristic(rows), _engine_rows and _from_header(path, env_name, spec)."""
 
-    def __init__(self, env_name: str, partition):
-        self.env_name = str(env_name).lower()
-        self.dim = puzzle_dim(env_name)
-        self.partition = parse_pdb_spec(env_name, partition) if isinstance(partition, str) else check_partition(self.dim, partition)
+    def __init__(self):
         self.tables: List[torch.Tensor] = []
         self.sweeps: List[int] = []
 
     @property
     def bytes(self) -> int:
-        return sum(table_bytes(self.dim, self.partition))
+        return sum(self._table_bytes())
 
-    def build(self) -> "PatternDatabase":
+    def build(self):
         _lib.require_gpu()
         self.tables, self.sweeps = [], []
-        for group in self.partition:
-            table, sweeps = _lib.pdb_build(self.dim, group)
+        for i in range(len(self._table_bytes())):
+            table, sweeps = self._build_one(i)
             self.tables.append(table)
             self.sweeps.append(sweeps)
         return self
 
-    def set_tables(self, tables: Sequence[np.ndarray]) -> "PatternDatabase":
-        """Adopt host-made tables (one uint8 array of N^(k+1) bytes per pattern)."""
-        want = table_bytes(self.dim, self.partition)
+    def set_tables(self, tables: Sequence[np.ndarray]):
+        """Adopt host-made tables (one uint8 array per pattern, of the pattern's table size)."""
+        want = self._table_bytes()
         if len(tables) != len(want):
             raise ValueError("%d tables for %d patterns" % (len(tables), len(want)))
         host = [np.ascontiguousarray(t, dtype=np.uint8).reshape(-1) for t in tables]
@@ -122,49 +121,79 @@ class PatternDatabase:
             if t.size != b:
                 raise ValueError("a table of %d bytes where the pattern needs %d" % (t.size, b))
         dev = _lib.require_gpu()
-        self.tables = [torch.from_numpy(t).to(dev) for t in host]
+        self.tables = [torch.from_numpy(t if t.flags.writeable else t.copy()).to(dev) for t in host]
         self.sweeps = [0] * len(host)
         return self
 
-    def heuristic(self, states: torch.Tensor) -> torch.Tensor:
-        if len(self.tables) != len(self.partition):
-            raise _lib.DcaError("PatternDatabase: build() or load() first")
-        return _lib.pdb_eval(self.dim, states, self.partition, self.tables)
+    def _ready(self, otherwise: str) -> None:
+        if len(self.tables) != len(self._table_bytes()):
+            raise _lib.DcaError("%s: %s" % (type(self).__name__, otherwise))
 
     def heuristic_fn_dev(self):
-        """(uint8 rows [m, D] on the device, is_onehot=False) -> float32 [m]: the closure form of BwasEngine.step / solve."""
+        """(uint8 rows on the device, is_onehot=False) -> float32 [m]: the closure form of BwasEngine.step / solve."""
         def fn(states: torch.Tensor, is_onehot: bool = False) -> torch.Tensor:
             if is_onehot:
-                raise ValueError("a pattern database reads the uint8 state rows, not one-hot rows")
-            return self.heuristic(states)
+                raise ValueError("a pattern database reads the uint8 %s rows, not one-hot rows" % self._engine_rows)
+            return self._engine_heuristic(states)
         return fn
 
     def save(self, path: str, tables: Optional[Sequence[np.ndarray]] = None) -> None:
-        """Write the partition and the tables to an .npz (`tables`: host arrays to write instead of the device's)."""
+        """Write the pattern set and the tables to an .npz (`tables`: host arrays to write instead of the device's)."""
         if tables is None:
-            if len(self.tables) != len(self.partition):
-                raise _lib.DcaError("PatternDatabase: nothing to save, build() first")
+            self._ready("nothing to save, build() first")
             tables = [t.cpu().numpy() for t in self.tables]
-        want = table_bytes(self.dim, self.partition)
+        want = self._table_bytes()
         if [int(np.asarray(t).size) for t in tables] != want:
-            raise ValueError("table sizes %s, the partition needs %s" % ([int(np.asarray(t).size) for t in tables], want))
+            raise ValueError("table sizes %s, the pattern set needs %s" % ([int(np.asarray(t).size) for t in tables], want))
         arrays = {"table_%d" % i: np.ascontiguousarray(t, dtype=np.uint8).reshape(-1) for i, t in enumerate(tables)}
         arrays["env_name"] = np.array(self.env_name)
-        arrays["partition"] = np.array("/".join(",".join(str(t) for t in g) for g in self.partition))
+        arrays["partition"] = np.array(self.spec)
         with open(path, "wb") as f:
             np.savez(f, **arrays)
 
     @classmethod
     def load_host(cls, path: str):
-        """-> (PatternDatabase without device tables, [host tables]); needs no device."""
+        """-> (the database without device tables, [host tables]); needs no device."""
         with np.load(path) as z:
-            pdb = cls(str(z["env_name"]), str(z["partition"]))
-            tables = [z["table_%d" % i] for i in range(len(pdb.partition))]
-        if [int(t.size) for t in tables] != table_bytes(pdb.dim, pdb.partition):
-            raise ValueError("%s: table sizes do not match the partition" % path)
+            pdb = cls._from_header(path, str(z["env_name"]), str(z["partition"]))
+            tables = [z["table_%d" % i] for i in range(len(pdb._table_bytes()))]
+        if [int(t.size) for t in tables] != pdb._table_bytes():
+            raise ValueError("%s: table sizes do not match the pattern set" % path)
         return pdb, tables
 
     @classmethod
-    def load(cls, path: str) -> "PatternDatabase":
+    def load(cls, path: str):
         pdb, tables = cls.load_host(path)
         return pdb.set_tables(tables)
+
+
+class PatternDatabase(_TableSet):
+    """The additive tables of one partition of a sliding puzzle (a 6-6-6-6 set, once saved, need not be rebuilt)."""
+
+    _engine_rows = "state"
+
+    def __init__(self, env_name: str, partition):
+        super().__init__()
+        self.env_name = str(env_name).lower()
+        self.dim = puzzle_dim(env_name)
+        self.partition = parse_pdb_spec(env_name, partition) if isinstance(partition, str) else check_partition(self.dim, partition)
+
+    @property
+    def spec(self) -> str:
+        return "/".join(",".join(str(t) for t in g) for g in self.partition)
+
+    def _table_bytes(self) -> List[int]:
+        return table_bytes(self.dim, self.partition)
+
+    def _build_one(self, i: int):
+        return _lib.pdb_build(self.dim, self.partition[i])
+
+    def heuristic(self, states: torch.Tensor) -> torch.Tensor:
+        self._ready("build() or load() first")
+        return _lib.pdb_eval(self.dim, states, self.partition, self.tables)
+
+    _engine_heuristic = heuristic  # the engine hands the closure the state rows [m, D]
+
+    @classmethod
+    def _from_header(cls, path: str, env_name: str, spec: str):
+        return cls(env_name, spec)  # (a file of another family: no sliding puzzle, ValueError)

@@ -299,3 +299,43 @@ def test_save_load_round_trip_of_a_host_made_table(tmp_path):
         PatternDatabase("puzzle8", partition).save(path, tables=[tables[0], tables[0]])
     with pytest.raises(ValueError):
         PatternDatabase("puzzle8", partition).save(path, tables=tables[:1])
+
+
+def test_build_refuses_ids_outside_a_byte_before_any_device_call():
+    """Both builds convert their ids through one helper: a value outside 0..255 is a ValueError, not a wrapped tile or cubie, and it
+    comes before the table is allocated or the library is called (no device here)."""
+    from deepcubea_amd import _lib
+    for ids in ((1, 256), (-1,)):
+        with pytest.raises(ValueError):
+            _lib.pdb_build(4, ids)
+        with pytest.raises(ValueError):
+            _lib.cube3_pdb_build(0, ids)
+
+
+def test_npz_files_written_by_hand_load_in_both_families(tmp_path):
+    """The file format, pinned without save(): the keys env_name, partition and table_%d, written here with np.savez."""
+    from deepcubea_amd.utils.cube3_pdb import Cube3PatternDatabase
+    from deepcubea_amd.utils.pattern_db import PatternDatabase
+    rng = np.random.default_rng(5)
+    p8, c3 = rng.integers(0, 256, 81).astype(np.uint8), rng.integers(0, 256, 528).astype(np.uint8)
+    puzzle, cube = str(tmp_path / "p8.npz"), str(tmp_path / "c3.npz")
+    with open(puzzle, "wb") as f:
+        np.savez(f, env_name=np.array("puzzle8"), partition=np.array("1"), table_0=p8)
+    with open(cube, "wb") as f:
+        np.savez(f, env_name=np.array("cube3"), partition=np.array("e11,e0"), table_0=c3)
+    pdb, tables = PatternDatabase.load_host(puzzle)
+    assert (pdb.env_name, pdb.dim, pdb.partition, pdb.spec, pdb.bytes) == ("puzzle8", 3, ((1,),), "1", 81)
+    assert len(tables) == 1 and tables[0].dtype == np.uint8 and np.array_equal(tables[0], p8)
+    pdb, tables = Cube3PatternDatabase.load_host(cube)
+    assert (pdb.env_name, pdb.patterns, pdb.spec, pdb.bytes) == ("cube3", ((1, (11, 0)),), "e11,e0", 528)
+    assert len(tables) == 1 and tables[0].dtype == np.uint8 and np.array_equal(tables[0], c3)
+    for cls, other in ((PatternDatabase, cube), (Cube3PatternDatabase, puzzle)):  # the other family's file is refused
+        with pytest.raises(ValueError):
+            cls.load_host(other)
+
+
+def test_spec_is_the_string_save_writes_and_parses_back():
+    from deepcubea_amd.utils import pattern_db as pd
+    pdb = pd.PatternDatabase("puzzle15", "5-5-5")
+    assert pdb.spec == "1,2,3,5,6/4,7,8,11,12/9,10,13,14,15"
+    assert pd.parse_pdb_spec("puzzle15", pdb.spec) == pdb.partition == pd.PRESETS["puzzle15"]["5-5-5"]

@@ -288,3 +288,23 @@ def test_refusals_through_the_c_abi_launch_nothing(L):
     assert build() == 0 and evaluate() == 0
     torch.cuda.synchronize()
     assert np.array_equal(table.cpu().numpy(), ref.host_table(4, (1, 2, 3))) and bool((out >= 0).all())
+
+
+def test_eval_refuses_tables_that_do_not_fit_their_pattern_before_any_launch(L):
+    """pdb_eval checks what the library cannot see — a table's size and dtype, one table per pattern — in Python, before the
+    call: ValueError, `out` untouched, and the valid call that follows returns exactly the host reference."""
+    good = ref.host_table(3, (1,))
+    assert good.size == 81
+    rows = perms(64, 9, 3)
+    want = ref.host_eval(3, rows, ((1,),), [good])
+    states, table = dev(rows), dev(good)
+    refused = {"80 bytes": [table[:80].clone()], "82 bytes": [torch.cat([table, table[:1]])],
+               "int8": [table.to(torch.int8)], "two tables for one pattern": [table, table]}
+    for what, tables in refused.items():
+        out = torch.full((64,), -1.0, dtype=torch.float32, device="cuda")
+        with pytest.raises(ValueError):
+            L.pdb_eval(3, states, ((1,),), tables, out=out)
+        got = L.pdb_eval(3, states, ((1,),), [table])
+        torch.cuda.synchronize()
+        assert bool((out == -1.0).all()), what
+        assert np.array_equal(got.cpu().numpy(), want), what
