@@ -990,6 +990,17 @@ def l1_kpad(state_dim: int, depth: int) -> int:
     return lib().dca_l1_kpad(state_dim, depth)
 
 
+def _l1_out(x: torch.Tensor, n_pad: int, out_dtype, split):
+    """Output tensor and DCA_DT_* code of a layer-1 forward on the rows x: the two fp16 planes [2, m, n_pad] for split="planes",
+    else [m, n_pad] in out_dtype (e4m3: the caller has folded the activation scale into the weights and bias)."""
+    m = x.shape[0]
+    if split == "planes":
+        return torch.empty((2, m, n_pad), dtype=torch.float16, device=x.device), DT_F16_PLANES
+    if out_dtype == E4M3:
+        return torch.empty((m, n_pad), dtype=E4M3, device=x.device), DT_E4M3
+    return torch.empty((m, n_pad), dtype=out_dtype, device=x.device), _TORCH_DT[out_dtype]
+
+
 def l1_onehot_gemm(states_nnet: torch.Tensor, depth: int, w_tiles: torch.Tensor, planes: int, bias: torch.Tensor,
                    relu: bool, out_dtype, split=False, overflow: Optional[torch.Tensor] = None) -> torch.Tensor:
     """relu?(onehot(states_nnet) @ W1^T + b1) from the uint8 rows, [m, n_pad] in out_dtype (dca_l1_onehot_gemm);
@@ -1000,15 +1011,7 @@ def l1_onehot_gemm(states_nnet: torch.Tensor, depth: int, w_tiles: torch.Tensor,
     x = _u8(states_nnet)
     m, d = x.shape
     n_pad = bias.numel()
-    if split == "planes":
-        out = torch.empty((2, m, n_pad), dtype=torch.float16, device=x.device)
-        code = DT_F16_PLANES
-    elif out_dtype == E4M3:  # (planes == 1; the caller has folded the activation scale into the weights and bias)
-        out = torch.empty((m, n_pad), dtype=E4M3, device=x.device)
-        code = DT_E4M3
-    else:
-        out = torch.empty((m, n_pad), dtype=out_dtype, device=x.device)
-        code = _TORCH_DT[out_dtype]
+    out, code = _l1_out(x, n_pad, out_dtype, split)  # (e4m3: planes == 1)
     check(lib().dca_l1_onehot_gemm(ptr(x), m, d, depth, ptr(w_tiles), planes, n_pad, ptr(bias), relu, ptr(out), code, ptr(overflow),
                                    stream_ptr()), "dca_l1_onehot_gemm")
     return out
@@ -1051,16 +1054,8 @@ def l1_embed(states_nnet: torch.Tensor, depth: int, w_t: torch.Tensor, bias: tor
     m, d = x.shape
     n_pad = bias.numel()
     assert w_t.dtype == torch.float32 and bias.dtype == torch.float32 and w_t.is_contiguous() and tuple(w_t.shape) == (d * depth, n_pad)
-    if split == "planes":
-        out = torch.empty((2, m, n_pad), dtype=torch.float16, device=x.device)
-        code = DT_F16_PLANES
-    elif out_dtype == E4M3:  # (the caller has folded the activation scale into the weights and bias)
-        out = torch.empty((m, n_pad), dtype=E4M3, device=x.device)
-        code = DT_E4M3
-    else:
-        assert not split and out_dtype in (torch.float32, torch.bfloat16)
-        out = torch.empty((m, n_pad), dtype=out_dtype, device=x.device)
-        code = _TORCH_DT[out_dtype]
+    assert split == "planes" or out_dtype == E4M3 or (not split and out_dtype in (torch.float32, torch.bfloat16))
+    out, code = _l1_out(x, n_pad, out_dtype, split)
     if m == 0:
         return out
     check(lib().dca_l1_embed(ptr(x), m, d, depth, ptr(w_t), n_pad, ptr(bias), relu, ptr(out), code, ptr(overflow), stream_ptr()),

@@ -18,6 +18,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 // ---- LDS images.  An LDS-DMA instruction writes 64 lanes x 16 B linearly, so an image stays linear in LDS and the XOR swizzle
 // that makes the ds_read_b128 fragment reads conflict-free is applied to each lane's GLOBAL source address.

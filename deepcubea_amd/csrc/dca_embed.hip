@@ -33,9 +33,21 @@
 // conflicts, but the restaging and the per-slice state loads made it 1.5-2.2x SLOWER (puzzle48 9.5-14.2 ms against 6.5).
 // Per 409 600 rows x 5120 units (profiles/r06_l1_embed_bench.txt), one-hot MFMA kernel -> this kernel, fp16 planes out:
 // puzzle15 3.0 -> 2.1 ms, puzzle24 9.2 -> 3.7, puzzle35 17.3 -> 5.2, puzzle48 30.1 -> 6.5; cube3 3.9 -> 6.0 (stays on MFMA).
-#include "dca_common.h"
+#include "dca_l1.h"
 
 namespace dca {
+
+// the column tile NT, waves per workgroup and states per lane and step T of each geometry (what fits LDS next to the [K][NT] table)
+template <int NT_, int WAVES_, int T_>
+struct EmbTileOf { static constexpr bool built = true; static constexpr int NT = NT_, WAVES = WAVES_, T = T_; };
+template <int D, int DEPTH> struct EmbTile : L1NotBuilt {};
+template <> struct EmbTile<54, 6> : EmbTileOf<64, 16, 4> {};
+template <> struct EmbTile<9, 9> : EmbTileOf<64, 16, 16> {};
+template <> struct EmbTile<16, 16> : EmbTileOf<64, 16, 8> {};
+template <> struct EmbTile<25, 25> : EmbTileOf<64, 12, 2> {};
+template <> struct EmbTile<36, 36> : EmbTileOf<16, 16, 1> {};
+template <> struct EmbTile<49, 49> : EmbTileOf<16, 12, 1> {};
+template <> struct EmbTile<49, 6> : EmbTileOf<64, 16, 4> {};
 
 template <int D, int DEPTH, int NT, int WAVES, int T>
 struct EmbGeo {
@@ -65,15 +77,13 @@ __device__ __forceinline__ bool emb_store(const float4& acc, int relu, int64_t r
         if constexpr (OUT == 0) {
             *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + o) = make_float4(u[0], u[1], u[2], u[3]);
         } else if constexpr (OUT == 2) {
-            typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-            typedef float f2 __attribute__((ext_vector_type(2)));
-            const f2 a = {u[0], u[1]}, b = {u[2], u[3]};
-            const bf2 pa = __builtin_convertvector(a, bf2), pb = __builtin_convertvector(b, bf2);
+            const f32x2 a = {u[0], u[1]}, b = {u[2], u[3]};
+            const bf16x2 pa = __builtin_convertvector(a, bf16x2), pb = __builtin_convertvector(b, bf16x2);
             uint2 q;
             __builtin_memcpy(&q.x, &pa, 4);
             __builtin_memcpy(&q.y, &pb, 4);
             *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + o) = q;
-        } else if constexpr (OUT == 5) {  // e4m3fn has no infinity: saturate at +-448
+        } else if constexpr (OUT == 5) {  // e4m3fn has no infinity: saturate at +-448 (pack_e4m3 written out: see DESIGN §4.5)
             auto sat = [](float f) { return fminf(fmaxf(f, -448.f), 448.f); };
             uint32_t q = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(sat(u[0]), sat(u[1]), 0, false);
             q = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(sat(u[2]), sat(u[3]), (int)q, true);
@@ -83,9 +93,9 @@ __device__ __forceinline__ bool emb_store(const float4& acc, int relu, int64_t r
             h4 hi, lo;
 #pragma unroll
             for (int e = 0; e < 4; e++) {
-                ovf |= !(fabsf(u[e]) <= 60000.0f);
+                ovf |= f16_unsafe(u[e]);
                 hi[e] = (_Float16)u[e];
-                lo[e] = (_Float16)(u[e] - (float)hi[e]);
+                lo[e] = f16_low_plane(u[e], hi[e]);
             }
             _Float16* q = reinterpret_cast<_Float16*>(out) + o;
             *reinterpret_cast<h4*>(q) = hi;
@@ -163,11 +173,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_l1_embed(const uint8_t* __restri
             if (q + 16 <= total) {
                 v = *reinterpret_cast<const uint4*>(nn + q);
             } else if (q < total) {
-                uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int e = 0; e < 16; e++)
-                    if (q + e < total) w[e >> 2] |= (uint32_t)nn[q + e] << (8 * (e & 3));
-                v = make_uint4(w[0], w[1], w[2], w[3]);
+                v = l1_load16_clipped(nn, q, total);
             }
         }
         return v;
@@ -248,12 +254,11 @@ int launch_embed(const uint8_t* nn, int64_t m, const float* wt, int64_t n_pad, c
     if (gy * WAVES > steps) gy = (steps + WAVES - 1) / WAVES;
     if (gy < 1) gy = 1;
     const dim3 grid((unsigned)tiles, (unsigned)gy), block(WAVES * 64);
-#define DCA_EMB_LAUNCH(OUTV)                                                                                            \
-    do {                                                                                                                \
-        auto kern = k_l1_embed<D, DEPTH, NT, WAVES, T, OUTV, NT == 64>;                                                 \
-        DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS)); \
-        hipLaunchKernelGGL(kern, grid, block, G::LDS, s, nn, m, wt, n_pad, bias, relu, out, overflow);                  \
-    } while (0)
+#define DCA_EMB_KERNEL(OUTV) reinterpret_cast<const void*>(k_l1_embed<D, DEPTH, NT, WAVES, T, OUTV, NT == 64>)
+#define DCA_EMB_LAUNCH(OUTV) \
+    hipLaunchKernelGGL((k_l1_embed<D, DEPTH, NT, WAVES, T, OUTV, NT == 64>), grid, block, G::LDS, s, nn, m, wt, n_pad, bias, relu, out, overflow)
+    static std::atomic<uint64_t> attr_devs{0};
+    if (int rc = dynamic_lds_once(attr_devs, {DCA_EMB_KERNEL(0), DCA_EMB_KERNEL(2), DCA_EMB_KERNEL(5), DCA_EMB_KERNEL(4)}, G::LDS)) return rc;
     if (out_dtype == DCA_DT_F32)
         DCA_EMB_LAUNCH(0);
     else if (out_dtype == DCA_DT_BF16)
@@ -263,6 +268,7 @@ int launch_embed(const uint8_t* nn, int64_t m, const float* wt, int64_t n_pad, c
     else
         DCA_EMB_LAUNCH(4);
 #undef DCA_EMB_LAUNCH
+#undef DCA_EMB_KERNEL
     return launch_check("k_l1_embed");
 }
 
@@ -272,10 +278,7 @@ using namespace dca;
 
 extern "C" {
 
-int dca_l1_embed_supported(int state_dim, int depth) {
-    return (state_dim == 54 && depth == 6) || (state_dim == depth && (depth == 9 || depth == 16 || depth == 25 || depth == 36 || depth == 49)) ||
-           (state_dim == 49 && depth == 6);
-}
+int dca_l1_embed_supported(int state_dim, int depth) { return l1_built<EmbTile>(state_dim, depth); }
 
 int dca_l1_embed(const uint8_t* nnet_in, int64_t m, int state_dim, int depth, const float* w_t, int64_t n_pad, const float* bias,
                  int relu, void* out, int out_dtype, int* overflow, void* stream) {
@@ -288,13 +291,10 @@ int dca_l1_embed(const uint8_t* nnet_in, int64_t m, int state_dim, int depth, co
     }
     if (m == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (state_dim == 54) return launch_embed<54, 6, 64, 16, 4>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);
-    if (state_dim == 9) return launch_embed<9, 9, 64, 16, 16>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);
-    if (state_dim == 16) return launch_embed<16, 16, 64, 16, 8>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);
-    if (state_dim == 25) return launch_embed<25, 25, 64, 12, 2>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);
-    if (state_dim == 36) return launch_embed<36, 36, 16, 16, 1>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);
-    if (depth == 49) return launch_embed<49, 49, 16, 12, 1>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);
-    return launch_embed<49, 6, 64, 16, 4>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);
+    return l1_dispatch<EmbTile>(state_dim, depth, DCA_E_BADARG, [&](auto g) {
+        using E = EmbTile<g.D, g.DEPTH>;
+        return launch_embed<g.D, g.DEPTH, E::NT, E::WAVES, E::T>(nnet_in, m, w_t, n_pad, bias, relu, out, out_dtype, overflow, s);
+    });
 }
 
 }  // extern "C"

@@ -22,7 +22,7 @@
 // read, table write; ~11 LDS cycles), 13 waves per CU for puzzle48.  Built, measured, removed: the table reads of four rows issued
 // together with a repeated address taking the earlier row's sum (one latency per four rows instead of four) — puzzle48 1.44 -> 1.56 ms
 // per 10 000 x 5000, slower on every geometry (profiles/l1_train_probe.txt has the shipped form).
-#include "dca_common.h"
+#include "dca_l1.h"
 
 namespace dca {
 
@@ -70,11 +70,7 @@ __global__ __launch_bounds__(G::THREADS) void k_l1_embed_wgrad(const uint8_t* __
             if (nn_aligned && b + 16 <= st_end) {
                 pre_s = *reinterpret_cast<const uint4*>(nn + b);
             } else {  // the slice's last piece, or a state matrix off the 16-byte grid: byte by byte, nothing read past the slice
-                uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int e = 0; e < 16; e++)
-                    if (b + e < st_end) w[e >> 2] |= (uint32_t)nn[b + e] << (8 * (e & 3));
-                pre_s = make_uint4(w[0], w[1], w[2], w[3]);
+                pre_s = l1_load16_clipped(nn, b, st_end);
             }
         }
         if (t < G::DY_PIECES) {
@@ -177,15 +173,9 @@ __global__ __launch_bounds__(256) void k_l1_wgrad_fold(const float* __restrict__
 template <class G>
 int launch_wgrad(const uint8_t* nn, int64_t m, const float* dy, int64_t ld_dy, int64_t n, float* dW, int64_t ldw, float* db,
                  void* workspace, hipStream_t s) {
-    // the dynamic-LDS limit is a property of the function on a device: raised once per instantiation and device, not per launch
-    static bool raised[64] = {};
-    int dev = 0;
-    DCA_HIP(hipGetDevice(&dev));
     auto kern = k_l1_embed_wgrad<G>;
-    if (dev < 0 || dev >= 64 || !__atomic_load_n(&raised[dev], __ATOMIC_ACQUIRE)) {
-        DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        if (dev >= 0 && dev < 64) __atomic_store_n(&raised[dev], true, __ATOMIC_RELEASE);
-    }
+    static std::atomic<uint64_t> attr_devs{0};
+    if (int rc = dynamic_lds_once(attr_devs, {reinterpret_cast<const void*>(kern)}, G::LDS)) return rc;
     const int64_t tiles = (n + G::NT - 1) / G::NT, nslices = (m + G::S - 1) / G::S, K = G::K;
     if (tiles * nslices > 0x7fffffffll) {
         set_error("dca_l1_embed_wgrad: %lld column tiles x %lld row slices exceed the grid", (long long)tiles, (long long)nslices);
@@ -212,23 +202,21 @@ int launch_wgrad(const uint8_t* nn, int64_t m, const float* dy, int64_t ld_dy, i
     return launch_check("k_l1_wgrad_fold");
 }
 
-//                     D  DEPTH NT CW  R    S
-using WgCube3 = WgradGeo<54, 6, 64, 4, 32, 1024>;
-using WgPuzzle8 = WgradGeo<9, 9, 64, 1, 32, 1024>;
-using WgPuzzle15 = WgradGeo<16, 16, 64, 1, 32, 1024>;
-using WgPuzzle24 = WgradGeo<25, 25, 32, 1, 64, 2048>;
-using WgPuzzle35 = WgradGeo<36, 36, 16, 1, 64, 2048>;
-using WgPuzzle48 = WgradGeo<49, 49, 16, 1, 64, 2048>;
-using WgLights7 = WgradGeo<49, 6, 64, 4, 32, 1024>;
+// the tile of each geometry: column tile NT, columns per owner thread CW, rows per chunk R, rows per slice S
+template <int D, int DEPTH> struct WgTile : L1NotBuilt {};
+template <int D, int DEPTH, int NT, int CW, int R, int S>
+struct WgTileOf { static constexpr bool built = true; using G = WgradGeo<D, DEPTH, NT, CW, R, S>; };
+//                                                       D  DEPTH NT CW  R    S
+template <> struct WgTile<54, 6> : WgTileOf<54, 6, 64, 4, 32, 1024> {};    // cube3
+template <> struct WgTile<9, 9> : WgTileOf<9, 9, 64, 1, 32, 1024> {};      // puzzle8
+template <> struct WgTile<16, 16> : WgTileOf<16, 16, 64, 1, 32, 1024> {};  // puzzle15
+template <> struct WgTile<25, 25> : WgTileOf<25, 25, 32, 1, 64, 2048> {};  // puzzle24
+template <> struct WgTile<36, 36> : WgTileOf<36, 36, 16, 1, 64, 2048> {};  // puzzle35
+template <> struct WgTile<49, 49> : WgTileOf<49, 49, 16, 1, 64, 2048> {};  // puzzle48
+template <> struct WgTile<49, 6> : WgTileOf<49, 6, 64, 4, 32, 1024> {};    // lightsout7
 
 static int64_t wgrad_slice_rows(int state_dim, int depth) {
-    if (!dca_l1_embed_supported(state_dim, depth)) return -1;
-    if (state_dim == 54) return WgCube3::S;
-    if (state_dim == 9) return WgPuzzle8::S;
-    if (state_dim == 16) return WgPuzzle15::S;
-    if (state_dim == 25) return WgPuzzle24::S;
-    if (state_dim == 36) return WgPuzzle35::S;
-    return depth == 49 ? WgPuzzle48::S : WgLights7::S;
+    return l1_dispatch<WgTile>(state_dim, depth, (int64_t)-1, [](auto g) { return (int64_t)WgTile<g.D, g.DEPTH>::G::S; });
 }
 
 }  // namespace dca
@@ -259,7 +247,7 @@ int64_t dca_l1_embed_wgrad_workspace_bytes(int64_t m, int state_dim, int depth, 
 
 int dca_l1_embed_wgrad(const uint8_t* nnet_in, int64_t m, int state_dim, int depth, const float* dy, int64_t ld_dy, int64_t n, float* dW,
                        int64_t ldw, float* db, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (!dca_l1_embed_supported(state_dim, depth)) {
+    if (!l1_built<WgTile>(state_dim, depth)) {
         set_error("dca_l1_embed_wgrad: geometry (%d, %d) not instantiated", state_dim, depth);
         return DCA_E_BADARG;
     }
@@ -275,13 +263,9 @@ int dca_l1_embed_wgrad(const uint8_t* nnet_in, int64_t m, int state_dim, int dep
     }
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (state_dim == 54) return launch_wgrad<WgCube3>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);
-    if (state_dim == 9) return launch_wgrad<WgPuzzle8>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);
-    if (state_dim == 16) return launch_wgrad<WgPuzzle15>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);
-    if (state_dim == 25) return launch_wgrad<WgPuzzle24>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);
-    if (state_dim == 36) return launch_wgrad<WgPuzzle35>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);
-    if (depth == 49) return launch_wgrad<WgPuzzle48>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);
-    return launch_wgrad<WgLights7>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);
+    return l1_dispatch<WgTile>(state_dim, depth, DCA_E_BADARG, [&](auto g) {
+        return launch_wgrad<typename WgTile<g.D, g.DEPTH>::G>(nnet_in, m, dy, ld_dy, n, dW, ldw, db, workspace, s);
+    });
 }
 
 }  // extern "C"

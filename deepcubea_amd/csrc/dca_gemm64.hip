@@ -15,7 +15,7 @@
 //     out[r, j] = relu?(bias[j] + sum_pos w_t[pos * depth + s[r, pos]][j]), bias first, positions ascending.  One generic kernel for
 //     every geometry: a workgroup keeps NT columns of the transposed table in LDS (the widest NT of 64 / 32 / 16 / 8 that fits),
 //     stages blocks of state rows into LDS and sums with NT lanes per state, two states per lane.
-#include "dca_common.h"
+#include "dca_dense.h"
 
 namespace dca {
 
@@ -203,7 +203,8 @@ int launch_embed64(const uint8_t* nn, int64_t m, int d, int depth, const double*
     int64_t gy = (2048 + tiles - 1) / tiles;
     if (gy > steps) gy = steps;
     if (gy < 1) gy = 1;
-    DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_l1_embed64<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    static std::atomic<uint64_t> attr_devs{0};  // (lds follows the geometry at run time: raised once to the ceiling embed64_rows() fills up to)
+    if (int rc = dynamic_lds_once(attr_devs, {reinterpret_cast<const void*>(k_l1_embed64<NT>)}, E64_LDS_MAX)) return rc;
     hipLaunchKernelGGL(k_l1_embed64<NT>, dim3((unsigned)tiles, (unsigned)gy), dim3(E64_THREADS), lds, s, nn, m, d, depth, wt, n_pad,
                        bias, relu, out, rows);
     return launch_check("k_l1_embed64");

@@ -23,9 +23,6 @@
 
 namespace dca {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-
 constexpr int EBM = 256, EBN = 256, EBK = 128, ETHREADS = 512;
 constexpr int ESLOT = 128 * 128;  // one half-tile: 128 rows x 128 B
 constexpr int EBUF = 4 * ESLOT;   // one K-tile: A01 | A23 | B0 | B1

@@ -18,12 +18,16 @@
 // ([plane][k/8][column][8] => 512 contiguous bytes per half-wave, conflict-free), then the workgroup walks over row
 // chunks of 512 (64 rows per wave = 2x2 tiles of v_mfma_f32_32x32x16_bf16, 64 accumulator VGPRs).  Per K-step a wave
 // issues 4*P MFMAs for 2 A-fragment rebuilds and 2*P ds_read_b128: the MFMA pipe is the limiter.
-#include "dca_dense.h"
+#include "dca_l1.h"
 
 namespace dca {
 
 constexpr int kL1Threads = 512;  // 8 waves = 2 per SIMD: one wave's mask build / epilogue hides under the other's MFMAs
 constexpr int kL1Rows = kL1Threads;  // rows per chunk (64 per wave)
+
+// built for every geometry of the table except lightsout7 (49 x 6), which the embedding sum and the fp8 kernel serve
+template <int D, int DEPTH>
+struct L1MfmaBuilt { static constexpr bool built = !(D == 49 && DEPTH == 6); };
 
 template <int D, int DEPTH>
 struct L1Geo {
@@ -41,8 +45,9 @@ struct L1Geo {
 };
 
 template <int D, int DEPTH, int P,
-          int OUT /*0 f32, 1 f16, 2 bf16, (3 unused,) 4 two fp16 planes (high, then low at +m*ldo),
-                    5 e4m3 bytes (saturating), 6 e4m3 bytes with one E8M0 block scale per row and 64 columns (out_scale)*/>
+          int OUT /*0 f32 (the direct-store tail), 1 f16, 2 bf16, (3 unused,) 4 two fp16 planes (high, then low at +m*ldo),
+                    5 e4m3 bytes (saturating) (1, 2, 4, 5: the lean tail), 6 e4m3 bytes with one E8M0 block scale per row and
+                    64 columns (out_scale) (the transposition tail)*/>
 __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __restrict__ nn, int64_t m,
                                                         const uint8_t* __restrict__ wt /*[ntile][P][KC][64][8] bf16*/,
                                                         const float* __restrict__ bias, int relu, void* __restrict__ out,
@@ -72,11 +77,13 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
     // operand — so that a lane holds a piece of ONE output row, and the weight column that feeds MFMA row i is chosen (bits 2
     // and 3 of the fragment's column index swapped: the same 32 chunks per lane group, still conflict-free) such that a
     // lane's 8 consecutive accumulator registers are 8 CONSECUTIVE output columns: bias, ReLU and the rounding work on
-    // register octets, packed pieces change hands through the wave's 4 KB of LDS, 8 lanes store one row segment.  The
-    // accumulator-layout tail it replaces (one LDS word per element: 128 ds_write_b32 + 16 ds_read_b128 + 16 eight-byte
-    // stores per wave and 64 x 64 tile) was half the kernel's time with one weight plane (csrc/dca_gemm16.hip has the story).
+    // register octets, packed pieces change hands through the wave's 4 KB of LDS, 8 lanes store one row segment.  These four
+    // outputs used to leave through the accumulator-layout transposition that the block-scaled output (OUT 6) still uses (one
+    // LDS word per element: 128 ds_write_b32 + 16 ds_read_b128 + 16 stores per wave and 64 x 64 tile), which was half the kernel's
+    // time with one weight plane (csrc/dca_gemm16.hip has the story).  fp32 (OUT 0) stores straight from the accumulator layout.
     constexpr bool LEAN = OUT == 1 || OUT == 2 || OUT == 4 || OUT == 5;
-    const int wcol = LEAN ? ((l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1)) : l31;
+    static_assert(LEAN || OUT == 0 || OUT == 6, "no such output form");
+    const int wcol = LEAN ? DCA_L1_LEAN_WCOL(l31) : l31;
     float bv[2];
     bv[0] = bias[n0 + l31];
     bv[1] = bias[n0 + 32 + l31];
@@ -178,8 +185,6 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
             uint8_t* tl = lw + G::CHKC * P * 64 * 16 + wv * 4096;
             const int tg = l31 >> 2, tx = l31 & 3;
             constexpr int PB = OUT == 5 ? 8 : 16;        // bytes of a packed piece (8 values)
-            constexpr int RB = 8 * PB;                   // bytes of a row of the wave's 64 columns
-            auto addr = [&](int row, int c16) { return tl + row * RB + ((c16 ^ (row & 7)) * PB); };
             bool ovf = false;
             constexpr int NPASS = OUT == 4 ? 2 : 1;      // two fp16 planes: the high halves, then the low halves
 #pragma unroll
@@ -202,17 +207,17 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
                         for (int e = 0; e < 8; e++) {
                             float v = acc[i][X >> 1][8 * (X & 1) + e] + bb[e];
                             if (relu) v = fmaxf(v, 0.f);
-                            if constexpr (OUT == 4) ovf |= !(fabsf(v) <= 60000.0f);
+                            if constexpr (OUT == 4) ovf |= f16_unsafe(v);
                             u[e] = v;
                         }
-                        if constexpr (OUT == 5) {  // e4m3fn has no infinity: saturate at +-448
+                        if constexpr (OUT == 5) {  // e4m3fn has no infinity: saturate at +-448 (pack_e4m3 written out: DESIGN §4.5)
                             uint32_t w0 = 0, w1 = 0;
                             auto sat = [](float f) { return fminf(fmaxf(f, -448.f), 448.f); };
                             w0 = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(sat(u[0]), sat(u[1]), 0, false);
                             w0 = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(sat(u[2]), sat(u[3]), (int)w0, true);
                             w1 = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(sat(u[4]), sat(u[5]), 0, false);
                             w1 = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(sat(u[6]), sat(u[7]), (int)w1, true);
-                            *reinterpret_cast<uint2*>(addr(l31, X * 2 + h)) = make_uint2(w0, w1);
+                            *reinterpret_cast<uint2*>(l1_lean_piece<PB>(tl, l31, X * 2 + h)) = make_uint2(w0, w1);
                         } else {
                             uint32_t w[4];
 #pragma unroll
@@ -223,8 +228,8 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
                                 } else {
                                     _Float16 h0 = (_Float16)a0, h1 = (_Float16)a1;
                                     if (OUT == 4 && pass == 1) {  // the low plane: what the high halves left over
-                                        h0 = (_Float16)(a0 - (float)h0);
-                                        h1 = (_Float16)(a1 - (float)h1);
+                                        h0 = f16_low_plane(a0, h0);
+                                        h1 = f16_low_plane(a1, h1);
                                     }
                                     uint16_t c0, c1;
                                     __builtin_memcpy(&c0, &h0, 2);
@@ -232,7 +237,7 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
                                     w[e] = (uint32_t)c0 | ((uint32_t)c1 << 16);
                                 }
                             }
-                            *reinterpret_cast<uint4*>(addr(l31, X * 2 + h)) = make_uint4(w[0], w[1], w[2], w[3]);
+                            *reinterpret_cast<uint4*>(l1_lean_piece<PB>(tl, l31, X * 2 + h)) = make_uint4(w[0], w[1], w[2], w[3]);
                         }
                     }
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private slice: only the wave's own writes
@@ -242,10 +247,10 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
                         const int64_t r = rw + 32 * i + 4 * tg + j;
                         const int c16 = tx * 2 + h;
                         if constexpr (OUT == 5) {
-                            const uint2 q = *reinterpret_cast<const uint2*>(addr(4 * tg + j, c16));
+                            const uint2 q = *reinterpret_cast<const uint2*>(l1_lean_piece<PB>(tl, 4 * tg + j, c16));
                             if (r < m) *reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(out) + r * ldo + n0 + c16 * 8) = q;
                         } else {
-                            const uint4 q = *reinterpret_cast<const uint4*>(addr(4 * tg + j, c16));
+                            const uint4 q = *reinterpret_cast<const uint4*>(l1_lean_piece<PB>(tl, 4 * tg + j, c16));
                             uint16_t* q0 = reinterpret_cast<uint16_t*>(out) + r * ldo + n0 + c16 * 8 + (pass ? m * ldo : 0);
                             if (r < m) *reinterpret_cast<uint4*>(q0) = q;
                         }
@@ -256,15 +261,12 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
             if (OUT == 4 && ovf && overflow) *overflow = 1;
         } else
         // epilogue: C/D layout col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-        if constexpr (OUT == 1 || OUT == 2 || OUT == 4 || OUT == 5 || OUT == 6) {
-            // 16-bit outputs: straight from the accumulator layout every store instruction would write 2 bytes per lane,
-            // 64 contiguous bytes per row (3.1 ms for the 204 800 x 5120 planes, the fp32 output of the same tile 2.3 ms).
-            // Each wave transposes 16 rows x 64 columns at a time through 4 KB of its own LDS — one word per element:
-            // value in the low half, split residual (planes) in the high half — and leaves with 8-byte stores: 16 lanes
-            // cover a row's 128 contiguous bytes of a plane.
+        if constexpr (OUT == 6) {
+            // block-scaled e4m3: a row's 64 values must meet before they can be quantised, and straight from the accumulator
+            // layout every store instruction would write 1 byte per lane.  Each wave transposes 16 rows x 64 columns at a time
+            // through 4 KB of its own LDS — one fp32 word per element — and leaves with 4-byte stores: 16 lanes cover a row's
+            // 64 contiguous bytes.
             uint32_t* sl = reinterpret_cast<uint32_t*>(lw + G::CHKC * P * 64 * 16 + wv * 4096);
-            typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
-            bool ovf = false;
 #pragma unroll
             for (int i = 0; i < 2; i++)
 #pragma unroll
@@ -276,25 +278,8 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
                             const int reg = 8 * half + rr;
                             float v = acc[i][jn][reg] + bv[jn];
                             if (relu) v = fmaxf(v, 0.f);
-                            uint32_t w;
-                            if constexpr (OUT == 2) {
-                                w = f32_to_bf16(v);
-                            } else if constexpr (OUT == 5) {  // e4m3fn has no infinity: saturate at +-448
-                                w = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(v, -448.f), 448.f), 0.f, 0, false) & 0xFFu;
-                            } else if constexpr (OUT == 6) {  // quantised after the transposition, once the row's block scale is known
-                                w = __float_as_uint(v);
-                            } else {
-                                const _Float16 hh = (_Float16)v;
-                                uint16_t hb, lb = 0;
-                                __builtin_memcpy(&hb, &hh, 2);
-                                if constexpr (OUT == 4) {
-                                    ovf |= !(fabsf(v) <= 60000.0f);
-                                    const _Float16 ll = (_Float16)(v - (float)hh);
-                                    __builtin_memcpy(&lb, &ll, 2);
-                                }
-                                w = (uint32_t)hb | ((uint32_t)lb << 16);
-                            }
-                            sl[((rr & 3) + 8 * (rr >> 2) + 4 * h) * 64 + jn * 32 + l31] = w;
+                            // (quantised after the transposition, once the row's block scale is known)
+                            sl[((rr & 3) + 8 * (rr >> 2) + 4 * h) * 64 + jn * 32 + l31] = __float_as_uint(v);
                         }
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private slice: only the wave's own writes
 #pragma unroll
@@ -302,47 +287,31 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
                         const int rl = q * 4 + (lane >> 4), c4 = (lane & 15) * 4;
                         const uint4 pk = *reinterpret_cast<const uint4*>(sl + rl * 64 + c4);
                         const int64_t r = rw + 32 * i + 16 * half + rl;
-                        if constexpr (OUT == 5) {  // one byte per element: 4-byte stores, 16 lanes cover 64 contiguous bytes of a row
-                            if (r < m)
-                                *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(out) + r * ldo + n0 + c4) =
-                                    (pk.x & 0xFFu) | ((pk.y & 0xFFu) << 8) | ((pk.z & 0xFFu) << 16) | (pk.w << 24);
-                        } else if constexpr (OUT == 6) {
-                            // the workgroup's 64 columns ARE one scale block of the next layer's K: largest magnitude of the row's 64
-                            // values (16 lanes x 4), the power of two that brings it to e4m3's range, then the bytes
-                            const float u0 = __uint_as_float(pk.x), u1 = __uint_as_float(pk.y), u2 = __uint_as_float(pk.z),
-                                        u3 = __uint_as_float(pk.w);
-                            float am = fmaxf(fmaxf(fabsf(u0), fabsf(u1)), fmaxf(fabsf(u2), fabsf(u3)));
-                            // (over the DPP row of 16 lanes that holds this row's 64 columns: rotate-and-max on the VALU)
-                            am = fmaxf(am, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(am), 0x128, 0xF, 0xF, false)));
-                            am = fmaxf(am, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(am), 0x124, 0xF, 0xF, false)));
-                            am = fmaxf(am, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(am), 0x122, 0xF, 0xF, false)));
-                            am = fmaxf(am, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(am), 0x121, 0xF, 0xF, false)));
-                            const float t = am * (1.0f / 448.0f);
-                            const uint32_t tb = __float_as_uint(t);
-                            int e = (int)((tb >> 23) & 0xFFu) - 127 + ((tb & 0x7FFFFFu) ? 1 : 0);
-                            e = e < -126 ? -126 : (e > 126 ? 126 : e);
-                            const float inv = __uint_as_float((uint32_t)(127 - e) << 23);
-                            if (r < m) {
-                                uint32_t q8 = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(fminf(u0 * inv, 448.f), fminf(u1 * inv, 448.f), 0, false);
-                                q8 = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(fminf(u2 * inv, 448.f), fminf(u3 * inv, 448.f), (int)q8, true);
-                                *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(out) + r * ldo + n0 + c4) = q8;
-                                if ((lane & 15) == 0) out_scale[r * ld_sc + blockIdx.x] = (uint8_t)(e + 127);
-                            }
-                        } else if (r < m) {
-                            const u16x4 hi = {(uint16_t)pk.x, (uint16_t)pk.y, (uint16_t)pk.z, (uint16_t)pk.w};
-                            uint16_t* q0 = reinterpret_cast<uint16_t*>(out) + r * ldo + n0 + c4;
-                            *reinterpret_cast<u16x4*>(q0) = hi;
-                            if constexpr (OUT == 4) {
-                                const u16x4 lo = {(uint16_t)(pk.x >> 16), (uint16_t)(pk.y >> 16), (uint16_t)(pk.z >> 16),
-                                                  (uint16_t)(pk.w >> 16)};
-                                *reinterpret_cast<u16x4*>(q0 + m * ldo) = lo;
-                            }
+                        // the workgroup's 64 columns ARE one scale block of the next layer's K: largest magnitude of the row's 64
+                        // values (16 lanes x 4), the power of two that brings it to e4m3's range, then the bytes
+                        const float u0 = __uint_as_float(pk.x), u1 = __uint_as_float(pk.y), u2 = __uint_as_float(pk.z),
+                                    u3 = __uint_as_float(pk.w);
+                        float am = fmaxf(fmaxf(fabsf(u0), fabsf(u1)), fmaxf(fabsf(u2), fabsf(u3)));
+                        // (over the DPP row of 16 lanes that holds this row's 64 columns: rotate-and-max on the VALU)
+                        am = fmaxf(am, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(am), 0x128, 0xF, 0xF, false)));
+                        am = fmaxf(am, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(am), 0x124, 0xF, 0xF, false)));
+                        am = fmaxf(am, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(am), 0x122, 0xF, 0xF, false)));
+                        am = fmaxf(am, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(am), 0x121, 0xF, 0xF, false)));
+                        const float t = am * (1.0f / 448.0f);
+                        const uint32_t tb = __float_as_uint(t);
+                        int e = (int)((tb >> 23) & 0xFFu) - 127 + ((tb & 0x7FFFFFu) ? 1 : 0);
+                        e = e < -126 ? -126 : (e > 126 ? 126 : e);
+                        const float inv = __uint_as_float((uint32_t)(127 - e) << 23);
+                        if (r < m) {
+                            uint32_t q8 = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(fminf(u0 * inv, 448.f), fminf(u1 * inv, 448.f), 0, false);
+                            q8 = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(fminf(u2 * inv, 448.f), fminf(u3 * inv, 448.f), (int)q8, true);
+                            *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(out) + r * ldo + n0 + c4) = q8;
+                            if ((lane & 15) == 0) out_scale[r * ld_sc + blockIdx.x] = (uint8_t)(e + 127);
                         }
                     }
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the reads are done before the slice is rewritten
                 }
-            if (OUT == 4 && ovf && overflow) *overflow = 1;
-        } else
+        } else  // fp32: straight from the accumulator layout (a store instruction writes 128 contiguous bytes of each of its 2 rows)
 #pragma unroll
         for (int i = 0; i < 2; i++)
 #pragma unroll
@@ -354,19 +323,7 @@ __global__ __launch_bounds__(kL1Threads) void k_l1_onehot_gemm(const uint8_t* __
                     if (r < m) {
                         float v = acc[i][jn][reg] + bv[jn];
                         if (relu) v = fmaxf(v, 0.f);
-                        if constexpr (OUT == 0)
-                            reinterpret_cast<float*>(out)[r * ldo + col] = v;
-                        else if constexpr (OUT == 1)
-                            reinterpret_cast<_Float16*>(out)[r * ldo + col] = (_Float16)v;
-                        else if constexpr (OUT == 2)
-                            reinterpret_cast<uint16_t*>(out)[r * ldo + col] = f32_to_bf16(v);
-                        else {  // the two fp16 planes dca_f16x3_gemm reads: high halves, then (m*ldo further) low halves
-                            _Float16* q = reinterpret_cast<_Float16*>(out) + r * ldo + col;
-                            if (!(fabsf(v) <= 60000.0f) && overflow) *overflow = 1;
-                            const _Float16 hh = (_Float16)v;
-                            q[0] = hh;
-                            q[m * ldo] = (_Float16)(v - (float)hh);
-                        }
+                        reinterpret_cast<float*>(out)[r * ldo + col] = v;
                     }
                 }
             }
@@ -381,12 +338,19 @@ int launch_l1_out(const uint8_t* nn, int64_t m, const uint8_t* wt, const float* 
     static_assert(LDS <= 160 * 1024, "weight tile does not fit LDS");
     const int64_t chunks = (m + kL1Rows - 1) / kL1Rows;
     const dim3 grid((unsigned)(n_pad / 64), (unsigned)(chunks < 16 ? (chunks < 1 ? 1 : chunks) : 16)), block(kL1Threads);
-#define DCA_L1_LAUNCH(OUTV)                                                                                          \
-    do {                                                                                                             \
-        auto kern = k_l1_onehot_gemm<D, DEPTH, P, OUTV>;                                                             \
-        DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); \
-        hipLaunchKernelGGL(kern, grid, block, LDS, s, nn, m, wt, bias, relu, out, n_pad, overflow, out_scale, ld_sc);          \
-    } while (0)
+#define DCA_L1_KERNEL(OUTV) reinterpret_cast<const void*>(k_l1_onehot_gemm<D, DEPTH, P, OUTV>)
+#define DCA_L1_LAUNCH(OUTV) \
+    hipLaunchKernelGGL((k_l1_onehot_gemm<D, DEPTH, P, OUTV>), grid, block, LDS, s, nn, m, wt, bias, relu, out, n_pad, overflow, out_scale, ld_sc)
+    if (P != 1 && out_dtype == DCA_DT_E4M3) {  // (the fp8 mode keeps layer 1's weights as ONE bf16 plane: no other combination is built)
+        set_error("dca_l1_onehot_gemm: e4m3 output takes planes == 1");
+        return DCA_E_BADARG;
+    }
+    static std::atomic<uint64_t> attr_devs{0};  // every output form of this (geometry, planes) has the same dynamic-LDS limit
+    if constexpr (P == 1) {
+        if (int rc = dynamic_lds_once(attr_devs, {DCA_L1_KERNEL(0), DCA_L1_KERNEL(1), DCA_L1_KERNEL(2), DCA_L1_KERNEL(4), DCA_L1_KERNEL(5), DCA_L1_KERNEL(6)}, LDS)) return rc;
+    } else {
+        if (int rc = dynamic_lds_once(attr_devs, {DCA_L1_KERNEL(0), DCA_L1_KERNEL(1), DCA_L1_KERNEL(2), DCA_L1_KERNEL(4)}, LDS)) return rc;
+    }
     if (out_dtype == DCA_DT_F32)
         DCA_L1_LAUNCH(0);
     else if (out_dtype == DCA_DT_F16)
@@ -394,18 +358,16 @@ int launch_l1_out(const uint8_t* nn, int64_t m, const uint8_t* wt, const float* 
     else if (out_dtype == DCA_DT_BF16)
         DCA_L1_LAUNCH(2);
     else if (out_dtype == DCA_DT_E4M3) {
-        if constexpr (P == 1) {  // (the fp8 mode keeps layer 1's weights as ONE bf16 plane: no other combination is built)
+        if constexpr (P == 1) {
             if (out_scale != nullptr)
                 DCA_L1_LAUNCH(6);
             else
                 DCA_L1_LAUNCH(5);
-        } else {
-            set_error("dca_l1_onehot_gemm: e4m3 output takes planes == 1");
-            return DCA_E_BADARG;
         }
     } else
         DCA_L1_LAUNCH(4);
 #undef DCA_L1_LAUNCH
+#undef DCA_L1_KERNEL
     return launch_check("k_l1_onehot_gemm");
 }
 
@@ -429,8 +391,6 @@ int launch_l1(int planes, const uint8_t* nn, int64_t m, const uint8_t* wt, const
 // the weight rows carry their own power-of-two scale —, bias, residual add, ReLU — utils/pytorch_models.py:57-86 with
 // BatchNorm folded): one pass, read 4-8 B, write 4-8 B per element.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr float kF16Safe = 60000.0f;  // |v| above this cannot be split into fp16 halves (fp16 max 65504)
-
 __global__ __launch_bounds__(256) void k_act_split(const float* __restrict__ y, const float* __restrict__ bias,
                                                    const float* __restrict__ skip, const float* __restrict__ col_scale,
                                                    float alpha, int relu, int64_t m, int64_t n,
@@ -466,10 +426,10 @@ __global__ __launch_bounds__(256) void k_act_split(const float* __restrict__ y, 
             float u = v[k] * al[k] + b[k] + sk[k];
             if (relu) u = fmaxf(u, 0.f);
             v[k] = u;
-            if (!(fabsf(u) <= kF16Safe) && overflow) *overflow = 1;  // beyond fp16 (or NaN): the caller redoes the batch in fp32
+            if (f16_unsafe(u) && overflow) *overflow = 1;  // beyond fp16 (or NaN): the caller redoes the batch in fp32
             const _Float16 hh = (_Float16)u;
             hi[k] = hh;
-            lo[k] = (_Float16)(u - (float)hh);
+            lo[k] = f16_low_plane(u, hh);
         }
         if (x_out) *reinterpret_cast<float4*>(x_out + r * n + col) = make_float4(v[0], v[1], v[2], v[3]);
         if (planes) {  // dca_f16x3_gemm's operand: the high halves [m,n], then the low halves [m,n]
@@ -561,9 +521,7 @@ using namespace dca;
 
 extern "C" {
 
-int dca_l1_supported(int state_dim, int depth) {
-    return (state_dim == 54 && depth == 6) || (state_dim == depth && (depth == 9 || depth == 16 || depth == 25 || depth == 36 || depth == 49));
-}
+int dca_l1_supported(int state_dim, int depth) { return l1_built<L1MfmaBuilt>(state_dim, depth); }
 
 int64_t dca_l1_kpad(int state_dim, int depth) { return (((int64_t)state_dim * depth + 15) / 16) * 16; }
 
@@ -582,14 +540,9 @@ int dca_l1_onehot_gemm(const uint8_t* nnet_in, int64_t m, int state_dim, int dep
     if (m == 0) return 0;
     const uint8_t* wt = reinterpret_cast<const uint8_t*>(w_tiles);
     hipStream_t s = (hipStream_t)stream;
-    switch (state_dim) {
-        case 9: return launch_l1<9, 9>(planes, nnet_in, m, wt, bias, relu, out, out_dtype, n_pad, overflow, s);
-        case 54: return launch_l1<54, 6>(planes, nnet_in, m, wt, bias, relu, out, out_dtype, n_pad, overflow, s);
-        case 16: return launch_l1<16, 16>(planes, nnet_in, m, wt, bias, relu, out, out_dtype, n_pad, overflow, s);
-        case 25: return launch_l1<25, 25>(planes, nnet_in, m, wt, bias, relu, out, out_dtype, n_pad, overflow, s);
-        case 36: return launch_l1<36, 36>(planes, nnet_in, m, wt, bias, relu, out, out_dtype, n_pad, overflow, s);
-        default: return launch_l1<49, 49>(planes, nnet_in, m, wt, bias, relu, out, out_dtype, n_pad, overflow, s);
-    }
+    return l1_dispatch<L1MfmaBuilt>(state_dim, depth, DCA_E_BADARG, [&](auto g) {
+        return launch_l1<g.D, g.DEPTH>(planes, nnet_in, m, wt, bias, relu, out, out_dtype, n_pad, overflow, s);
+    });
 }
 
 int dca_l1_onehot_gemm_mx(const uint8_t* nnet_in, int64_t m, int state_dim, int depth, const void* w_tiles, int64_t n_pad,
@@ -603,14 +556,9 @@ int dca_l1_onehot_gemm_mx(const uint8_t* nnet_in, int64_t m, int state_dim, int 
     const uint8_t* wt = reinterpret_cast<const uint8_t*>(w_tiles);
     uint8_t* sc = reinterpret_cast<uint8_t*>(out_scale);
     hipStream_t s = (hipStream_t)stream;
-    switch (state_dim) {
-        case 9: return launch_l1<9, 9>(1, nnet_in, m, wt, bias, relu, out8, DCA_DT_E4M3, n_pad, nullptr, s, sc, ld_sc);
-        case 54: return launch_l1<54, 6>(1, nnet_in, m, wt, bias, relu, out8, DCA_DT_E4M3, n_pad, nullptr, s, sc, ld_sc);
-        case 16: return launch_l1<16, 16>(1, nnet_in, m, wt, bias, relu, out8, DCA_DT_E4M3, n_pad, nullptr, s, sc, ld_sc);
-        case 25: return launch_l1<25, 25>(1, nnet_in, m, wt, bias, relu, out8, DCA_DT_E4M3, n_pad, nullptr, s, sc, ld_sc);
-        case 36: return launch_l1<36, 36>(1, nnet_in, m, wt, bias, relu, out8, DCA_DT_E4M3, n_pad, nullptr, s, sc, ld_sc);
-        default: return launch_l1<49, 49>(1, nnet_in, m, wt, bias, relu, out8, DCA_DT_E4M3, n_pad, nullptr, s, sc, ld_sc);
-    }
+    return l1_dispatch<L1MfmaBuilt>(state_dim, depth, DCA_E_BADARG, [&](auto g) {
+        return launch_l1<g.D, g.DEPTH>(1, nnet_in, m, wt, bias, relu, out8, DCA_DT_E4M3, n_pad, nullptr, s, sc, ld_sc);
+    });
 }
 
 int dca_act_split(const float* y, const float* bias, const float* skip, const float* col_scale, double alpha, int relu,

@@ -24,13 +24,9 @@
 //     registers under the K loop;
 //   * tail: scale / bias from LDS, ReLU + saturation as one v_med3, v_cvt_pk_fp8_f32, 8-byte pieces exchanged inside the wave
 //     through 4 KB of LDS so that 8 lanes store one 128-byte row segment (full lines).
-#include "dca_common.h"
+#include "dca_l1.h"
 
 namespace dca {
-
-typedef int l8_i32x4 __attribute__((ext_vector_type(4)));
-typedef int l8_i32x8 __attribute__((ext_vector_type(8)));
-typedef float l8_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kL8Threads = 512;
 constexpr int kL8Cols = 128;
@@ -47,6 +43,9 @@ struct L8Geo {
     static constexpr int MISC_BYTES = 2 * kL8Cols * 4 + 256 * 8;  // scale, bias, the byte -> eight e4m3 bytes table
     static constexpr int NPRE = (64 * D + 1023) / 1024;              // 16-byte row pieces per lane of a wave's 64 rows
     static constexpr int LDS = W_BYTES + MISC_BYTES + (kL8Threads / 64) * (4096 + ROW_BYTES);
+    // built where the whole weight tile (128 columns x KPAD bytes) fits LDS next to the waves' slices: cube3 (KPAD 384: 48 KB),
+    // puzzle8 (128: 16 KB), puzzle15 (256: 32 KB), puzzle24 (640: 80 KB), lightsout7 (320: 40 KB); not puzzle35 (1344: 168 KB), puzzle48
+    static constexpr bool built = LDS <= 160 * 1024;
 };
 
 template <int D, int DEPTH>
@@ -103,7 +102,7 @@ __global__ __launch_bounds__(kL8Threads) void k_l1_onehot_gemm8(const uint8_t* _
         }
     }
     __syncthreads();
-    const int wcol = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
+    const int wcol = DCA_L1_LEAN_WCOL(l31);
     for (int64_t chunk = blockIdx.y; chunk * kL8Threads < m; chunk += gridDim.y) {
         const int64_t rw = chunk * kL8Threads + wv * 64;  // first row of this wave (no workgroup barrier below: waves run free)
         if (rw >= m) continue;
@@ -163,7 +162,7 @@ __global__ __launch_bounds__(kL8Threads) void k_l1_onehot_gemm8(const uint8_t* _
         }
         __builtin_amdgcn_wave_barrier();  // (every lane has read its row: the slice may be rewritten by the next chunk)
         prefetch(chunk + gridDim.y);      // the next chunk's rows fly under this chunk's K loop and tail
-        l8_f32x16 acc[2][4];
+        f32x16 acc[2][4];
 #pragma unroll
         for (int i = 0; i < 2; i++)
 #pragma unroll
@@ -172,7 +171,7 @@ __global__ __launch_bounds__(kL8Threads) void k_l1_onehot_gemm8(const uint8_t* _
                 for (int e = 0; e < 16; e++) acc[i][jn][e] = 0.f;
 #pragma unroll
         for (int s = 0; s < G::KSTEPS; s++) {
-            l8_i32x8 bf[2];
+            i32x8 bf[2];
 #pragma unroll
             for (int i = 0; i < 2; i++)
 #pragma unroll
@@ -184,9 +183,9 @@ __global__ __launch_bounds__(kL8Threads) void k_l1_onehot_gemm8(const uint8_t* _
 #pragma unroll
             for (int jn = 0; jn < 4; jn++) {
                 const uint8_t* p = lw + ((size_t)((s * 4 + h * 2) * kL8Cols + jn * 32 + wcol)) * 16;
-                const l8_i32x4 w0 = *reinterpret_cast<const l8_i32x4*>(p);
-                const l8_i32x4 w1 = *reinterpret_cast<const l8_i32x4*>(p + kL8Cols * 16);
-                const l8_i32x8 wf = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
+                const i32x4 w0 = *reinterpret_cast<const i32x4*>(p);
+                const i32x4 w1 = *reinterpret_cast<const i32x4*>(p + kL8Cols * 16);
+                const i32x8 wf = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
                 acc[0][jn] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf, bf[0], acc[0][jn], 0, 0, 0, 0, 0, 0);
                 acc[1][jn] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf, bf[1], acc[1][jn], 0, 0, 0, 0, 0, 0);
             }
@@ -216,8 +215,8 @@ __global__ __launch_bounds__(kL8Threads) void k_l1_onehot_gemm8(const uint8_t* _
                     q0 = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(u[2], u[3], (int)q0, true);
                     uint32_t q1 = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(u[4], u[5], 0, false);
                     q1 = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(u[6], u[7], (int)q1, true);
-                    const int c8 = jn * 4 + x * 2 + h;
-                    *reinterpret_cast<uint2*>(lx + l31 * 128 + (((c8 >> 1) ^ (l31 & 7)) << 4) + ((c8 & 1) << 3)) = make_uint2(q0, q1);
+                    const int c8 = jn * 4 + x * 2 + h;  // (a half of the 16-byte piece c8 >> 1)
+                    *reinterpret_cast<uint2*>(l1_lean_piece<16>(lx, l31, c8 >> 1) + ((c8 & 1) << 3)) = make_uint2(q0, q1);
                 }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private slice: only the wave's own writes
             __builtin_amdgcn_wave_barrier();
@@ -225,7 +224,7 @@ __global__ __launch_bounds__(kL8Threads) void k_l1_onehot_gemm8(const uint8_t* _
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int row = 4 * tg + j, c16 = tx * 2 + h;
-                const uint4 q = *reinterpret_cast<const uint4*>(lx + row * 128 + ((c16 ^ (row & 7)) << 4));
+                const uint4 q = *reinterpret_cast<const uint4*>(l1_lean_piece<16>(lx, row, c16));
                 const int64_t r = rw + 32 * i + row;
                 if (r < m) *reinterpret_cast<uint4*>(out + r * ldo + n0 + c16 * 16) = q;
             }
@@ -247,7 +246,8 @@ int launch_l1_8(const uint8_t* nn, int64_t m, const uint8_t* wt, const float* sc
     if (gy < 1) gy = 1;
     if (gy > chunks) gy = chunks;
     auto kern = k_l1_onehot_gemm8<D, DEPTH>;
-    DCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
+    static std::atomic<uint64_t> attr_devs{0};
+    if (int rc = dynamic_lds_once(attr_devs, {reinterpret_cast<const void*>(kern)}, G::LDS)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)gy), dim3(kL8Threads), G::LDS, s, nn, m, wt, scale, bias, relu, out, n_pad);
     return launch_check("k_l1_onehot_gemm8");
 }
@@ -258,12 +258,7 @@ using namespace dca;
 
 extern "C" {
 
-// geometries whose whole weight tile (128 columns x KPAD bytes) fits LDS next to the waves' slices: cube3 (384: 48 KB),
-// puzzle8 (128: 16 KB), puzzle15 (256: 32 KB), puzzle24 (640: 80 KB), lightsout7 (320: 40 KB)
-int dca_l1_supported8(int state_dim, int depth) {
-    return (state_dim == 54 && depth == 6) || (state_dim == 9 && depth == 9) || (state_dim == 16 && depth == 16) || (state_dim == 25 && depth == 25) ||
-           (state_dim == 49 && depth == 6);
-}
+int dca_l1_supported8(int state_dim, int depth) { return l1_built<L8Geo>(state_dim, depth); }
 
 int64_t dca_l1_kpad8(int state_dim, int depth) { return (((int64_t)state_dim * depth + 63) / 64) * 64; }
 
@@ -279,11 +274,8 @@ int dca_l1_onehot_gemm8(const uint8_t* nnet_in, int64_t m, int state_dim, int de
     const uint8_t* wt = reinterpret_cast<const uint8_t*>(w_tiles);
     uint8_t* o = reinterpret_cast<uint8_t*>(out8);
     hipStream_t s = (hipStream_t)stream;
-    if (state_dim == 54) return launch_l1_8<54, 6>(nnet_in, m, wt, scale, bias, relu, o, n_pad, s);
-    if (state_dim == 9) return launch_l1_8<9, 9>(nnet_in, m, wt, scale, bias, relu, o, n_pad, s);
-    if (state_dim == 16) return launch_l1_8<16, 16>(nnet_in, m, wt, scale, bias, relu, o, n_pad, s);
-    if (state_dim == 25) return launch_l1_8<25, 25>(nnet_in, m, wt, scale, bias, relu, o, n_pad, s);
-    return launch_l1_8<49, 6>(nnet_in, m, wt, scale, bias, relu, o, n_pad, s);
+    return l1_dispatch<L8Geo>(state_dim, depth, DCA_E_BADARG,
+                              [&](auto g) { return launch_l1_8<g.D, g.DEPTH>(nnet_in, m, wt, scale, bias, relu, o, n_pad, s); });
 }
 
 }  // extern "C"

@@ -121,6 +121,52 @@ def test_embed_rejects_what_it_cannot_do():
     assert torch.equal(_lib.l1_embed(xc[3:], 25, wt, bc, True), _lib.l1_embed(xc, 25, wt, bc, True)[3:])
 
 
+def test_every_layer1_entry_point_refuses_a_geometry_its_own_family_has_not_built():
+    """Each entry point that dispatches on (state_dim, depth), called with a pair its own family does not instantiate — one that
+    another family does, or none: DCA_E_BADARG, the entry point's own name in the message, nothing launched (the output's fill
+    pattern is intact).  Then two launches of the MFMA kernel in a row — the once-per-device dynamic-LDS limit set (if no earlier
+    test did), then skipped — give the same bits, and they are the layer."""
+    from deepcubea_amd import _lib
+    from deepcubea_amd.utils.pytorch_models import l1_weight_tiles
+    _lib.require_gpu()
+    L = _lib.lib()
+    m, n_pad, fill = 64, 128, 0xA5
+    x = torch.zeros((m, 64), dtype=torch.uint8, device="cuda")
+    w = torch.zeros(1 << 20, dtype=torch.uint8, device="cuda")       # stands for any weight / scale / bias / dy operand: never read
+    out = torch.full((2 * m * n_pad * 4,), fill, dtype=torch.uint8, device="cuda")
+    px, pw, po, st = _lib.ptr(x), _lib.ptr(w), _lib.ptr(out), _lib.stream_ptr()
+    assert px % 16 == 0 and pw % 16 == 0 and po % 16 == 0
+    calls = [
+        ("dca_l1_onehot_gemm", 49, 6, lambda d, k: L.dca_l1_onehot_gemm(px, m, d, k, pw, 1, n_pad, pw, 1, po, _lib.DT_F32, None, st)),
+        ("dca_l1_onehot_gemm_mx", 49, 6, lambda d, k: L.dca_l1_onehot_gemm_mx(px, m, d, k, pw, n_pad, pw, 1, po, po + m * n_pad, n_pad // 64, st)),
+        ("dca_l1_onehot_gemm8", 36, 36, lambda d, k: L.dca_l1_onehot_gemm8(px, m, d, k, pw, n_pad, pw, pw, 1, po, st)),
+        ("dca_l1_embed", 54, 7, lambda d, k: L.dca_l1_embed(px, m, d, k, pw, n_pad, pw, 1, po, _lib.DT_F32, None, st)),
+        ("dca_l1_embed_wgrad", 54, 7, lambda d, k: L.dca_l1_embed_wgrad(px, m, d, k, pw, n_pad, n_pad, po, d * k, None, None, 0, st)),
+    ]
+    for name, d, k, call in calls:
+        assert call(d, k) == -1, name  # DCA_E_BADARG
+        assert ("%s: geometry (%d, %d) not instantiated" % (name, d, k)) in L.dca_last_error().decode(), (name, L.dca_last_error())
+    torch.cuda.synchronize()
+    assert bool((out == fill).all()), "a refused call launches nothing"
+    # (49, 6) and (36, 36) are pairs other families build; the same calls are accepted where the family has the pair
+    assert _lib.l1_embed_supported(49, 6) and _lib.l1_supported8(49, 6) and not _lib.l1_supported(49, 6)
+    assert _lib.l1_supported(36, 36) and not _lib.l1_supported8(36, 36)
+
+    D = depth = 9
+    m = 65
+    wf, b, xs = _case(D, depth, m, n_pad, 99)
+    tiles = l1_weight_tiles(wf, 3, _lib.l1_kpad(D, depth)).cuda()
+    y0 = _lib.l1_onehot_gemm(xs.cuda(), depth, tiles, 3, b.cuda(), True, torch.float32)
+    y1 = _lib.l1_onehot_gemm(xs.cuda(), depth, tiles, 3, b.cuda(), True, torch.float32)
+    assert y0.shape == (m, n_pad) and torch.equal(y0.view(torch.int32), y1.view(torch.int32))
+    # three bf16 planes carry 24 mantissa bits of each weight and the sum is accumulated in fp32: D + 1 roundings of 2^-24 of the
+    # magnitudes summed, with the factor 4 test_embed_against_the_onehot_mfma_kernel_and_float64 allows this kernel
+    onehot = torch.nn.functional.one_hot(xs.long(), depth).double().view(m, D * depth)
+    want = torch.relu(onehot @ wf.double().t() + b.double())
+    mag = onehot @ wf.double().abs().t() + b.double().abs()
+    assert bool(((y0.cpu().double() - want).abs() <= 4 * (D + 1) * 2.0 ** -24 * mag).all())
+
+
 @pytest.mark.parametrize("D,depth", [(16, 16), (49, 49), (54, 6)])
 def test_embed_against_the_onehot_mfma_kernel_and_float64(D, depth):
     """Same layer, two kernels: both within a few fp32 roundings of the float64 value; the embedding sum (exact fp32 operands,

@@ -789,3 +789,25 @@ def test_bench_reads_the_committed_pmc_traffic_of_this_round():
         b = bench.expand_pmc_traffic(oh, 1_000_000)
         assert b is not None and alg <= b <= 1.03 * alg, (oh, b)  # no re-reads: measured traffic = algorithmic bytes (+ hash / solved)
     assert bench.expand_pmc_traffic("f32", 12345) is None
+
+
+def test_layer1_geometry_table_is_the_literal_list():
+    """The three layer-1 `supported` answers over 1..64 x 1..64 are exactly these lists (6, 5 and 7 pairs) and nothing else, and the
+    padded K of the two MFMA kernels is what the weight-tile builders were written against."""
+    from deepcubea_amd import _lib
+    L = _lib.lib()
+    table = [(54, 6), (9, 9), (16, 16), (25, 25), (36, 36), (49, 49), (49, 6)]
+    want = {"dca_l1_supported": set(table) - {(49, 6)},
+            "dca_l1_supported8": set(table) - {(36, 36), (49, 49)},
+            "dca_l1_embed_supported": set(table)}
+    assert [len(want[k]) for k in ("dca_l1_supported", "dca_l1_supported8", "dca_l1_embed_supported")] == [6, 5, 7]
+    for name, pairs in want.items():
+        fn = getattr(L, name)
+        got = {(d, k): fn(d, k) for d in range(1, 65) for k in range(1, 65)}
+        assert set(got.values()) <= {0, 1}, name
+        assert {p for p, v in got.items() if v} == pairs, name
+    kpad = {(54, 6): (336, 384), (9, 9): (96, 128), (16, 16): (256, 256), (25, 25): (640, 640), (36, 36): (1296, 1344),
+            (49, 49): (2416, 2432), (49, 6): (304, 320)}
+    assert set(kpad) == set(table)
+    for (d, k), (k16, k64) in kpad.items():
+        assert (L.dca_l1_kpad(d, k), L.dca_l1_kpad8(d, k)) == (k16, k64), (d, k)
