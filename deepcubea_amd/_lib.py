@@ -681,21 +681,48 @@ def absmax_bits(x: torch.Tensor, m: Optional[int] = None, n: Optional[int] = Non
     return out
 
 
+def _plane_ptrs(out: torch.Tensor):
+    """Device addresses of the planes of a contiguous fp16 [planes, rows, ld] tensor (no view per plane: this runs per launch)."""
+    base = _raw(out)
+    return [base + p * out.shape[1] * out.shape[2] * 2 for p in range(out.shape[0])]
+
+
+def _planes_scaled(planes: int, x, amax, n_pad, ldo, out, m, n, ld) -> torch.Tensor:
+    """split_planes_scaled (planes = 2) and cast_planes_scaled (1): the defaults, the [planes, m, ldo] buffer, the call."""
+    m, n, ld = _rows_cols_ld(x, m, n, ld)
+    n_pad = n if n_pad is None else int(n_pad)
+    ldo = n_pad if ldo is None else int(ldo)
+    if out is None:
+        out = torch.empty((planes, m, ldo), dtype=torch.float16, device=x.device)
+    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (planes, m, ldo)
+    name = "dca_split_planes_scaled" if planes == 2 else "dca_cast_planes_scaled"
+    check(getattr(lib(), name)(_raw(x), m, n, ld, _raw(amax), *_plane_ptrs(out), ldo, n_pad, stream_ptr()), name)
+    return out
+
+
+def _rows_scaled(planes: int, w, other_amax, k_pad, ldo, out, col_scale, n, k, ld):
+    """split_rows_scaled (planes = 2) and cast_rows_scaled (1): the defaults, the [planes, n, ldo] buffer, col_scale, the call."""
+    n, k, ld = _rows_cols_ld(w, n, k, ld)
+    k_pad = k if k_pad is None else int(k_pad)
+    ldo = k_pad if ldo is None else int(ldo)
+    if out is None:
+        out = torch.empty((planes, n, ldo), dtype=torch.float16, device=w.device)
+    if col_scale is None:
+        col_scale = torch.empty(n, dtype=torch.float32, device=w.device)
+    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (planes, n, ldo)
+    assert col_scale.dtype == torch.float32 and col_scale.is_contiguous() and col_scale.numel() >= n
+    name = "dca_split_rows_scaled" if planes == 2 else "dca_cast_rows_scaled"
+    check(getattr(lib(), name)(_raw(w), n, k, ld, *_plane_ptrs(out), ldo, k_pad, _raw(col_scale), _raw(other_amax), stream_ptr()), name)
+    return out, col_scale
+
+
 def split_planes_scaled(x: torch.Tensor, amax: Optional[torch.Tensor] = None, n_pad: Optional[int] = None,
                         ldo: Optional[int] = None, out: Optional[torch.Tensor] = None, m: Optional[int] = None,
                         n: Optional[int] = None, ld: Optional[int] = None) -> torch.Tensor:
     """fp32 [m, n] (row stride ld) * 2^e -> its fp16 planes out[0] (high) / out[1] (low), [2, m, ldo] (dca_split_planes_scaled):
     2^e takes the |max| whose bits `amax` holds into [2^14, 2^15) (amax None: unscaled); columns n..n_pad are written as zeros,
     columns n_pad..ldo are not touched.  n_pad defaults to n, ldo to n_pad; `out` may be a buffer of the caller's."""
-    m, n, ld = _rows_cols_ld(x, m, n, ld)
-    n_pad = n if n_pad is None else int(n_pad)
-    ldo = n_pad if ldo is None else int(ldo)
-    if out is None:
-        out = torch.empty((2, m, ldo), dtype=torch.float16, device=x.device)
-    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (2, m, ldo)
-    check(lib().dca_split_planes_scaled(_raw(x), m, n, ld, _raw(amax), _raw(out[0]), _raw(out[1]), ldo, n_pad, stream_ptr()),
-          "dca_split_planes_scaled")
-    return out
+    return _planes_scaled(2, x, amax, n_pad, ldo, out, m, n, ld)
 
 
 def split_rows_scaled(w: torch.Tensor, other_amax: Optional[torch.Tensor] = None, k_pad: Optional[int] = None,
@@ -704,18 +731,7 @@ def split_rows_scaled(w: torch.Tensor, other_amax: Optional[torch.Tensor] = None
     """Per row of w [n, k] fp32 (row stride ld): the row's own power-of-two scale 2^e (its |max| into [2^14, 2^15)), the fp16
     planes of row * 2^e in out [2, n, ldo] (columns k..k_pad zero, k_pad..ldo untouched) and col_scale[row] = 1 / (2^e * the scale
     of the OTHER operand, whose |max| bits `other_amax` holds; None: 1) (dca_split_rows_scaled).  -> (out, col_scale)."""
-    n, k, ld = _rows_cols_ld(w, n, k, ld)
-    k_pad = k if k_pad is None else int(k_pad)
-    ldo = k_pad if ldo is None else int(ldo)
-    if out is None:
-        out = torch.empty((2, n, ldo), dtype=torch.float16, device=w.device)
-    if col_scale is None:
-        col_scale = torch.empty(n, dtype=torch.float32, device=w.device)
-    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (2, n, ldo)
-    assert col_scale.dtype == torch.float32 and col_scale.is_contiguous() and col_scale.numel() >= n
-    check(lib().dca_split_rows_scaled(_raw(w), n, k, ld, _raw(out[0]), _raw(out[1]), ldo, k_pad, _raw(col_scale), _raw(other_amax),
-                                      stream_ptr()), "dca_split_rows_scaled")
-    return out, col_scale
+    return _rows_scaled(2, w, other_amax, k_pad, ldo, out, col_scale, n, k, ld)
 
 
 def fill_inv_pow2(amax: torch.Tensor, n: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -732,14 +748,7 @@ def cast_planes_scaled(x: torch.Tensor, amax: Optional[torch.Tensor] = None, n_p
                        n: Optional[int] = None, ld: Optional[int] = None) -> torch.Tensor:
     """The HIGH plane alone of split_planes_scaled, bit for bit, as a [1, m, ldo] fp16 tensor (dca_cast_planes_scaled): what the
     one-product kernels read (f16_gemm; wgrad_f16 with products = 1 takes the tensor as it is).  Same arguments and padding."""
-    m, n, ld = _rows_cols_ld(x, m, n, ld)
-    n_pad = n if n_pad is None else int(n_pad)
-    ldo = n_pad if ldo is None else int(ldo)
-    if out is None:
-        out = torch.empty((1, m, ldo), dtype=torch.float16, device=x.device)
-    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (1, m, ldo)
-    check(lib().dca_cast_planes_scaled(_raw(x), m, n, ld, _raw(amax), _raw(out), ldo, n_pad, stream_ptr()), "dca_cast_planes_scaled")
-    return out
+    return _planes_scaled(1, x, amax, n_pad, ldo, out, m, n, ld)
 
 
 def cast_rows_scaled(w: torch.Tensor, other_amax: Optional[torch.Tensor] = None, k_pad: Optional[int] = None,
@@ -747,18 +756,7 @@ def cast_rows_scaled(w: torch.Tensor, other_amax: Optional[torch.Tensor] = None,
                      n: Optional[int] = None, k: Optional[int] = None, ld: Optional[int] = None):
     """The HIGH plane alone of split_rows_scaled, bit for bit, as a [1, n, ldo] fp16 tensor, and the same col_scale
     (dca_cast_rows_scaled).  -> (out, col_scale)."""
-    n, k, ld = _rows_cols_ld(w, n, k, ld)
-    k_pad = k if k_pad is None else int(k_pad)
-    ldo = k_pad if ldo is None else int(ldo)
-    if out is None:
-        out = torch.empty((1, n, ldo), dtype=torch.float16, device=w.device)
-    if col_scale is None:
-        col_scale = torch.empty(n, dtype=torch.float32, device=w.device)
-    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (1, n, ldo)
-    assert col_scale.dtype == torch.float32 and col_scale.is_contiguous() and col_scale.numel() >= n
-    check(lib().dca_cast_rows_scaled(_raw(w), n, k, ld, _raw(out), ldo, k_pad, _raw(col_scale), _raw(other_amax), stream_ptr()),
-          "dca_cast_rows_scaled")
-    return out, col_scale
+    return _rows_scaled(1, w, other_amax, k_pad, ldo, out, col_scale, n, k, ld)
 
 
 def f16_gemm(a_h: torch.Tensor, w_h: torch.Tensor, col_scale: Optional[torch.Tensor], alpha: float,
@@ -780,17 +778,16 @@ def f16_gemm(a_h: torch.Tensor, w_h: torch.Tensor, col_scale: Optional[torch.Ten
     return out
 
 
-def _linear_f16_from_plane(ah: torch.Tensor, amax: Optional[torch.Tensor], w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    """The GEMM of the one-product mode on a high plane of `a` that exists already (ah [m, pad64(k)], scaled by `amax`)."""
-    wh, cs = cast_rows_scaled(w, amax, k_pad=ah.shape[1])
-    return f16_gemm(ah, wh[0], cs, 1.0, None if bias is None else bias.contiguous())
-
-
-def _linear_from_planes(ap: torch.Tensor, amax: Optional[torch.Tensor], w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    """The GEMM of linear_f16x3 on planes of `a` that exist already (ap [2, m, pad64(k)], scaled by `amax`; None: unscaled)."""
-    wp, cs = split_rows_scaled(w, amax, k_pad=ap.shape[2])
-    _, out = f16x3_gemm(ap, wp[0], wp[1], cs, 1.0, None if bias is None else bias.contiguous(), None, False, False, True)
-    return out
+def _train_gemm(planes: torch.Tensor, amax: Optional[torch.Tensor], w: torch.Tensor, bias: Optional[torch.Tensor], gemm: str) -> torch.Tensor:
+    """a . w^T (+ bias) -> fp32 [m, n] on planes of `a` that exist already ([1 or 2, m, pad64(k)], scaled by `amax`; None: unscaled):
+    the rows of w [n, k] prepared on the spot, then the GEMM.  gemm "f16x3": split_rows_scaled + dca_f16x3_gemm on both planes;
+    "f16": cast_rows_scaled + dca_f16_gemm on plane 0.  Every forward and input-gradient GEMM of linear_train is one call of this."""
+    bias = None if bias is None else bias.contiguous()
+    if gemm == "f16x3":
+        wp, cs = split_rows_scaled(w, amax, k_pad=planes.shape[2])
+        return f16x3_gemm(planes, wp[0], wp[1], cs, 1.0, bias, None, False, False, True)[1]
+    wh, cs = cast_rows_scaled(w, amax, k_pad=planes.shape[2])
+    return f16_gemm(planes[0], wh[0], cs, 1.0, bias)
 
 
 def linear_f16x3(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], scale_a: bool,
@@ -810,13 +807,11 @@ def linear_f16x3(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
         amax = absmax_bits(a)
     if not scale_a:
         amax = None
-    ap = split_planes_scaled(a, amax, n_pad=kp)
-    wp, cs = split_rows_scaled(w, amax, k_pad=kp)
-    _, out = f16x3_gemm(ap, wp[0], wp[1], cs, 1.0, None if bias is None else bias.contiguous(), None, False, False, True)
-    return out
+    return _train_gemm(split_planes_scaled(a, amax, n_pad=kp), amax, w, bias, "f16x3")
 
 
 WGRAD_MODES = ("library", "f16x3", "f16")  # how the training step computes nn.Linear's weight gradient (linear_train)
+TRAIN_GEMM_MODES = ("f16x3", "f16")  # how the training step runs nn.Linear's forward and input-gradient GEMMs (linear_train)
 
 
 def wgrad_splits(m: int, n: int, k: int) -> int:
@@ -856,80 +851,33 @@ def wgrad_f16(dy_planes: torch.Tensor, x_planes: torch.Tensor, n: int, k: int, a
 
 
 class _LinearTrainFn(torch.autograd.Function):
-    """nn.Linear for the training step (reference nnet_utils.py:53-118 runs it as the library's fp32 GEMMs): forward and input
-    gradient on dca_f16x3_gemm (2/3 of the layer's flops, ~3x the library's fp32 rate at fp32 accuracy).  The weight gradient
-    dy^T . x contracts over the BATCH dimension.  wgrad = "library" (default): the library's fp32 GEMM, as the reference.
-    "f16x3" / "f16": dca_wgrad_f16 on the fp16 planes the step has anyway — the forward keeps the planes of x and their amax
-    word instead of x, the backward makes the planes of dy once for the input gradient and the weight gradient — with three
-    products (fp32-accurate) or the high planes alone (non-parity).  The kernel reads the row-major planes with the transposing
-    LDS read: the two transposes that made round 4's split-K form a draw do not exist."""
+    """nn.Linear for the training step (reference nnet_utils.py:53-118 runs it as the library's fp32 GEMMs), in every mode of
+    gemm (TRAIN_GEMM_MODES) x wgrad (WGRAD_MODES).  Three facts make the table:
+
+      * planes made of an activation or gradient tensor: 2 (split_planes_scaled) if gemm or wgrad is "f16x3", else 1
+        (cast_planes_scaled: half the bytes).  One power-of-two scale per tensor from its own magnitude (absmax_bits: one extra
+        pass; without it a value beyond 65504 turns into inf in its fp16 plane and the loss into NaN without a word).
+      * weight rows and the GEMM of y = x . W^T + b and dx = dy . W (_train_gemm; 2/3 of the layer's flops): "f16x3" =
+        split_rows_scaled + dca_f16x3_gemm, fp32-accurate at ~3x the library's fp32 rate; "f16" = cast_rows_scaled + dca_f16_gemm
+        on plane 0 — 11-bit operands, one product instead of three, NOT a parity mode.
+      * kept for the backward pass: (x, weight) for wgrad "library" — dW = dy^T . x is the library's fp32 GEMM, as the reference —
+        else (planes of x, their amax word, weight): dW on dca_wgrad_f16 from those and the planes of dy, which the backward
+        makes once for both gradients, with three products ("f16x3", fp32-accurate) or the high planes alone ("f16").  The
+        kernel contracts over the BATCH dimension reading the row-major planes with the transposing LDS read."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, wgrad="library"):
+    def forward(ctx, x, weight, bias, wgrad, gemm):
         ctx.has_bias = bias is not None
-        ctx.wgrad = wgrad
-        # scale_a: the activations get one power-of-two scale from their own magnitude, like the gradients (one extra pass
-        # over x; without it a value beyond 65504 turns into inf in its fp16 plane and the loss into NaN without a word)
-        if wgrad == "library":
-            ctx.save_for_backward(x, weight)
-            return linear_f16x3(x, weight, bias, scale_a=True)
-        x, w = x.contiguous(), weight.contiguous()
-        amax_x = absmax_bits(x)
-        xp = split_planes_scaled(x, amax_x, n_pad=_pad64(x.shape[1]))
-        ctx.save_for_backward(xp, amax_x, weight)
-        return _linear_from_planes(xp, amax_x, w, bias)
-
-    @staticmethod
-    def backward(ctx, dy):
-        if ctx.wgrad == "library":
-            x, weight = ctx.saved_tensors
-            dy = dy.contiguous()
-            amax = absmax_bits(dy) if ctx.needs_input_grad[0] else None
-            dx = linear_f16x3(dy, weight.t().contiguous(), None, scale_a=True, amax=amax) if ctx.needs_input_grad[0] else None
-            dw = None
-            if ctx.needs_input_grad[1]:
-                dw = dy.t().mm(x)
-            db = dy.sum(0) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-            return dx, dw, db, None
-        xp, amax_x, weight = ctx.saved_tensors
-        dy = dy.contiguous()
-        n, k = weight.shape
-        dx = dw = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:  # (fc1 has no input gradient: the planes serve dW alone)
-            amax = absmax_bits(dy)
-            dyp = split_planes_scaled(dy, amax, n_pad=_pad64(n))
-            if ctx.needs_input_grad[0]:
-                dx = _linear_from_planes(dyp, amax, weight.t().contiguous(), None)
-            if ctx.needs_input_grad[1]:
-                dw = wgrad_f16(dyp, xp, n, k, amax, amax_x, 3 if ctx.wgrad == "f16x3" else 1)
-        db = dy.sum(0) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        return dx, dw, db, None
-
-
-TRAIN_GEMM_MODES = ("f16x3", "f16")  # how the training step runs nn.Linear's forward and input-gradient GEMMs (linear_train)
-
-
-class _LinearTrainF16Fn(torch.autograd.Function):
-    """nn.Linear for the training step in the NON-parity GEMM mode (gemm = "f16"): forward y = x . W^T + b and input gradient
-    dx = dy . W on dca_f16_gemm — the scaled HIGH fp16 planes alone, 11-bit operands, one product instead of three, fp32
-    accumulation and output.  The weight gradient goes by `wgrad` as in _LinearTrainFn: "library" keeps fp32 x for dy^T . x;
-    "f16" keeps only the high plane of x and its amax word (cast_planes_scaled writes half the bytes of the split) and hands
-    [1, m, ld] tensors to wgrad_f16(..., products = 1); "f16x3" makes both planes of x and dy with the existing split — the GEMM
-    reads plane 0, wgrad_f16(..., 3) reads both."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, wgrad):
-        ctx.has_bias = bias is not None
-        ctx.wgrad = wgrad
-        x, w = x.contiguous(), weight.contiguous()
-        amax_x = absmax_bits(x)
-        prep = split_planes_scaled if wgrad == "f16x3" else cast_planes_scaled
-        xp = prep(x, amax_x, n_pad=_pad64(x.shape[1]))
+        ctx.wgrad, ctx.gemm = wgrad, gemm
+        ctx.planes = split_planes_scaled if "f16x3" in (gemm, wgrad) else cast_planes_scaled
+        xc = x.contiguous()
+        amax_x = absmax_bits(xc)
+        xp = ctx.planes(xc, amax_x, n_pad=_pad64(x.shape[1]))
         if wgrad == "library":
             ctx.save_for_backward(x, weight)
         else:
             ctx.save_for_backward(xp, amax_x, weight)
-        return _linear_f16_from_plane(xp[0], amax_x, w, bias)
+        return _train_gemm(xp, amax_x, weight.contiguous(), bias, gemm)
 
     @staticmethod
     def backward(ctx, dy):
@@ -938,12 +886,11 @@ class _LinearTrainF16Fn(torch.autograd.Function):
         n, k = weight.shape
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dx = dw = None
-        if need_dx or (need_dw and ctx.wgrad != "library"):
+        if need_dx or (need_dw and ctx.wgrad != "library"):  # (fc1 has no input gradient: its planes of dy serve dW alone)
             amax = absmax_bits(dy)
-            prep = split_planes_scaled if ctx.wgrad == "f16x3" else cast_planes_scaled
-            dyp = prep(dy, amax, n_pad=_pad64(n))
+            dyp = ctx.planes(dy, amax, n_pad=_pad64(n))
             if need_dx:
-                dx = _linear_f16_from_plane(dyp[0], amax, weight.t().contiguous(), None)
+                dx = _train_gemm(dyp, amax, weight.t().contiguous(), None, ctx.gemm)
         if need_dw:
             if ctx.wgrad == "library":
                 dw = dy.t().mm(ctx.saved_tensors[0])
@@ -951,7 +898,7 @@ class _LinearTrainF16Fn(torch.autograd.Function):
                 xp, amax_x = ctx.saved_tensors[0], ctx.saved_tensors[1]
                 dw = wgrad_f16(dyp, xp, n, k, amax, amax_x, 3 if ctx.wgrad == "f16x3" else 1)
         db = dy.sum(0) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
 def linear_train(x: torch.Tensor, lin: "torch.nn.Linear", wgrad: str = "library", gemm: str = "f16x3") -> torch.Tensor:
@@ -966,11 +913,7 @@ def linear_train(x: torch.Tensor, lin: "torch.nn.Linear", wgrad: str = "library"
         raise ValueError("gemm must be one of %s, not %r" % ("/".join(TRAIN_GEMM_MODES), gemm))
     if (x.is_cuda and x.dtype == torch.float32 and lin.weight.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 256
             and lin.in_features % 4 == 0 and lin.out_features % 4 == 0 and lin.in_features >= 64 and TRAIN_F16X3):
-        if gemm == "f16":
-            return _LinearTrainF16Fn.apply(x, lin.weight, lin.bias, wgrad)
-        if wgrad == "library":
-            return _LinearTrainFn.apply(x, lin.weight, lin.bias)
-        return _LinearTrainFn.apply(x, lin.weight, lin.bias, wgrad)
+        return _LinearTrainFn.apply(x, lin.weight, lin.bias, wgrad, gemm)
     return torch.nn.functional.linear(x, lin.weight, lin.bias)
 
 

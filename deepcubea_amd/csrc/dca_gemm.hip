@@ -528,6 +528,21 @@ __global__ __launch_bounds__(HTHREADS, 2) void k_f16_gemm(const GemmArgs p) {
     f16x3_epilogue(p, lds, acc, m0, n0, w, wm, wn, lane, l31, h);
 }
 
+typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+
+// four floats -> their high fp16 plane at oh + at and, for PLANES == 2, what the rounding left as the low plane at ol + at
+template <int PLANES>
+__device__ __forceinline__ void store_planes(const float (&u)[4], _Float16* __restrict__ oh, _Float16* __restrict__ ol, int64_t at) {
+    h4 hi, lo;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        hi[q] = (_Float16)u[q];
+        lo[q] = (_Float16)(u[q] - (float)hi[q]);
+    }
+    *reinterpret_cast<h4*>(oh + at) = hi;
+    if constexpr (PLANES == 2) *reinterpret_cast<h4*>(ol + at) = lo;
+}
+
 // fp32 [m, n] (row stride ld) -> its two fp16 planes (and the overflow flag): the entry into an f16x3 layer for
 // activations that did not come out of an f16x3 epilogue
 __global__ __launch_bounds__(256) void k_split_planes(const float* __restrict__ x, int64_t m, int64_t n, int64_t ld,
@@ -535,14 +550,13 @@ __global__ __launch_bounds__(256) void k_split_planes(const float* __restrict__ 
                                                       int64_t ldo, int* __restrict__ overflow) {
     const int64_t n4 = n / 4;
     const int64_t total = m * n4;
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t r = i / n4, c = (i - r * n4) * 4;
         const float4 v = *reinterpret_cast<const float4*>(x + r * ld + c);
         const float u[4] = {v.x, v.y, v.z, v.w};
         h4 hi, lo;
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
+        for (int k = 0; k < 4; k++) {  // (store_planes<2> with the overflow test in its loop)
             if (!(fabsf(u[k]) <= 60000.0f) && overflow) *overflow = 1;
             hi[k] = (_Float16)u[k];
             lo[k] = (_Float16)(u[k] - (float)hi[k]);
@@ -559,130 +573,74 @@ __global__ __launch_bounds__(256) void k_split_planes(const float* __restrict__ 
 // split (exact: only the exponent moves), bringing its largest element into [2^14, 2^15): the low plane of everything
 // within 2^-10 of that is a normal fp16 number, what lies below is held to 2^-39 of the largest element.  The inverse scales
 // come back through the GEMM's per-column factor.  (pow2_scale_of: dca_dense.h — the weight-gradient kernel undoes the same scales.)
+// PLANES == 1 is the HIGH plane alone (the one-product GEMM and products = 1 of dca_wgrad_f16 read nothing else): the same
+// scale, the same rounding (bit for bit plane 0 of PLANES == 2), the same zero pad, half the bytes written; ol is not looked at.
 
-// max |x| over the matrix as float bits (non-negative floats order like their bit patterns); out zeroed by the host
+// max |x| as float bits (non-negative floats order like their bit patterns): four elements folded into a thread's maximum,
+// and the maxima of a workgroup's 256 threads into one word that every thread gets back (wave shuffle, then 4 words of LDS)
+__device__ __forceinline__ uint32_t absmax_fold(uint32_t mx, const float4 v) {
+    return max(max(mx, __float_as_uint(fabsf(v.x))), max(__float_as_uint(fabsf(v.y)), max(__float_as_uint(fabsf(v.z)), __float_as_uint(fabsf(v.w)))));
+}
+__device__ __forceinline__ uint32_t absmax_block(uint32_t mx) {
+    __shared__ uint32_t sh[4];
+    uint32_t* mine = &sh[threadIdx.x >> 6];  // (taken in front of the shuffles: behind them the compiler places one shift elsewhere)
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+    if ((threadIdx.x & 63) == 0) *mine = mx;
+    __syncthreads();
+    return max(max(sh[0], sh[1]), max(sh[2], sh[3]));
+}
+
+// max |x| over the matrix; out zeroed by the host
 __global__ __launch_bounds__(256) void k_absmax_bits(const float* __restrict__ x, int64_t m, int64_t n, int64_t ld,
                                                      uint32_t* __restrict__ out) {
     const int64_t n4 = n / 4, total = m * n4;
     uint32_t mx = 0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t r = i / n4, c = (i - r * n4) * 4;
-        const float4 v = *reinterpret_cast<const float4*>(x + r * ld + c);
-        mx = max(max(mx, __float_as_uint(fabsf(v.x))), max(__float_as_uint(fabsf(v.y)), max(__float_as_uint(fabsf(v.z)), __float_as_uint(fabsf(v.w)))));
+        mx = absmax_fold(mx, *reinterpret_cast<const float4*>(x + r * ld + c));
     }
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
-    __shared__ uint32_t sh[4];
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(out, max(max(sh[0], sh[1]), max(sh[2], sh[3])));
+    mx = absmax_block(mx);
+    if (threadIdx.x == 0) atomicMax(out, mx);
 }
 
 // x * 2^e -> planes, columns n..n_pad zero.  amax_bits == nullptr: no scaling.
-__global__ __launch_bounds__(256) void k_split_planes_scaled(const float* __restrict__ x, int64_t m, int64_t n, int64_t ld,
-                                                             const uint32_t* __restrict__ amax_bits, _Float16* __restrict__ oh,
-                                                             _Float16* __restrict__ ol, int64_t ldo, int64_t n_pad) {
+template <int PLANES>
+__global__ __launch_bounds__(256) void k_planes_scaled(const float* __restrict__ x, int64_t m, int64_t n, int64_t ld,
+                                                       const uint32_t* __restrict__ amax_bits, _Float16* __restrict__ oh,
+                                                       _Float16* __restrict__ ol, int64_t ldo, int64_t n_pad) {
     const float s = amax_bits ? pow2_scale_of(*amax_bits) : 1.0f;
     const int64_t n4 = n_pad / 4, total = m * n4;
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t r = i / n4, c = (i - r * n4) * 4;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c < n) v = *reinterpret_cast<const float4*>(x + r * ld + c);
         const float u[4] = {v.x * s, v.y * s, v.z * s, v.w * s};
-        h4 hi, lo;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            hi[k] = (_Float16)u[k];
-            lo[k] = (_Float16)(u[k] - (float)hi[k]);
-        }
-        *reinterpret_cast<h4*>(oh + r * ldo + c) = hi;
-        *reinterpret_cast<h4*>(ol + r * ldo + c) = lo;
+        store_planes<PLANES>(u, oh, ol, r * ldo + c);
     }
 }
 
 // one workgroup per row of w [n, k]: the row's own power-of-two scale, its planes (columns k..k_pad zero), and
 // col_scale[row] = 1 / (row scale * scale of the OTHER operand, if its |max| is given)
-__global__ __launch_bounds__(256) void k_split_rows_scaled(const float* __restrict__ w, int64_t k, int64_t ld,
-                                                           _Float16* __restrict__ oh, _Float16* __restrict__ ol, int64_t ldo,
-                                                           int64_t k_pad, float* __restrict__ col_scale,
-                                                           const uint32_t* __restrict__ other_amax_bits) {
+template <int PLANES>
+__global__ __launch_bounds__(256) void k_rows_scaled(const float* __restrict__ w, int64_t k, int64_t ld,
+                                                     _Float16* __restrict__ oh, _Float16* __restrict__ ol, int64_t ldo,
+                                                     int64_t k_pad, float* __restrict__ col_scale,
+                                                     const uint32_t* __restrict__ other_amax_bits) {
     const int64_t r = blockIdx.x;
     const float* row = w + r * ld;
     const int64_t k4 = k / 4;
     uint32_t mx = 0;
-    for (int64_t i = threadIdx.x; i < k4; i += 256) {
-        const float4 v = *reinterpret_cast<const float4*>(row + i * 4);
-        mx = max(max(mx, __float_as_uint(fabsf(v.x))), max(__float_as_uint(fabsf(v.y)), max(__float_as_uint(fabsf(v.z)), __float_as_uint(fabsf(v.w)))));
-    }
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
-    __shared__ uint32_t sh[4];
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    const float s = pow2_scale_of(max(max(sh[0], sh[1]), max(sh[2], sh[3])));
+    for (int64_t i = threadIdx.x; i < k4; i += 256) mx = absmax_fold(mx, *reinterpret_cast<const float4*>(row + i * 4));
+    const float s = pow2_scale_of(absmax_block(mx));
     if (threadIdx.x == 0) {
         const float so = other_amax_bits ? pow2_scale_of(*other_amax_bits) : 1.0f;
         col_scale[r] = (1.0f / s) * (1.0f / so);  // powers of two: exact (2^-15-100 .. 2^+100: far inside fp32)
     }
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
     for (int64_t i = threadIdx.x; i < k_pad / 4; i += 256) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (i < k4) v = *reinterpret_cast<const float4*>(row + i * 4);  // (second read of the row: L2)
         const float u[4] = {v.x * s, v.y * s, v.z * s, v.w * s};
-        h4 hi, lo;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            hi[q] = (_Float16)u[q];
-            lo[q] = (_Float16)(u[q] - (float)hi[q]);
-        }
-        *reinterpret_cast<h4*>(oh + r * ldo + i * 4) = hi;
-        *reinterpret_cast<h4*>(ol + r * ldo + i * 4) = lo;
-    }
-}
-
-// The HIGH planes alone of the two kernels above (the one-product GEMM and products = 1 of dca_wgrad_f16 read nothing else):
-// the same scale, the same rounding (bit for bit their plane 0), the same zero pad, half the bytes written.
-__global__ __launch_bounds__(256) void k_cast_planes_scaled(const float* __restrict__ x, int64_t m, int64_t n, int64_t ld,
-                                                            const uint32_t* __restrict__ amax_bits, _Float16* __restrict__ oh,
-                                                            int64_t ldo, int64_t n_pad) {
-    const float s = amax_bits ? pow2_scale_of(*amax_bits) : 1.0f;
-    const int64_t n4 = n_pad / 4, total = m * n4;
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t r = i / n4, c = (i - r * n4) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < n) v = *reinterpret_cast<const float4*>(x + r * ld + c);
-        const h4 hi = {(_Float16)(v.x * s), (_Float16)(v.y * s), (_Float16)(v.z * s), (_Float16)(v.w * s)};
-        *reinterpret_cast<h4*>(oh + r * ldo + c) = hi;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_cast_rows_scaled(const float* __restrict__ w, int64_t k, int64_t ld,
-                                                          _Float16* __restrict__ oh, int64_t ldo, int64_t k_pad,
-                                                          float* __restrict__ col_scale,
-                                                          const uint32_t* __restrict__ other_amax_bits) {
-    const int64_t r = blockIdx.x;
-    const float* row = w + r * ld;
-    const int64_t k4 = k / 4;
-    uint32_t mx = 0;
-    for (int64_t i = threadIdx.x; i < k4; i += 256) {
-        const float4 v = *reinterpret_cast<const float4*>(row + i * 4);
-        mx = max(max(mx, __float_as_uint(fabsf(v.x))), max(__float_as_uint(fabsf(v.y)), max(__float_as_uint(fabsf(v.z)), __float_as_uint(fabsf(v.w)))));
-    }
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
-    __shared__ uint32_t sh[4];
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    const float s = pow2_scale_of(max(max(sh[0], sh[1]), max(sh[2], sh[3])));
-    if (threadIdx.x == 0) {
-        const float so = other_amax_bits ? pow2_scale_of(*other_amax_bits) : 1.0f;
-        col_scale[r] = (1.0f / s) * (1.0f / so);
-    }
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    for (int64_t i = threadIdx.x; i < k_pad / 4; i += 256) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < k4) v = *reinterpret_cast<const float4*>(row + i * 4);
-        const h4 hi = {(_Float16)(v.x * s), (_Float16)(v.y * s), (_Float16)(v.z * s), (_Float16)(v.w * s)};
-        *reinterpret_cast<h4*>(oh + r * ldo + i * 4) = hi;
+        store_planes<PLANES>(u, oh, ol, r * ldo + i * 4);
     }
 }
 
@@ -706,6 +664,43 @@ static int launch_gemm(const char* entry, void (*kernel)(GemmArgs), const char* 
                                               reinterpret_cast<const void*>(k_f16_gemm)}, HLDS)) return rc;
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(HTHREADS), HLDS, (hipStream_t)stream, p);
     return launch_check(kernel_name);
+}
+
+// DCA_ARG in the name of the entry point that handed its arguments on
+#define DCA_ARG_OF(entry, cond)                                        \
+    do {                                                               \
+        if (!(cond)) {                                                 \
+            ::dca::set_error("bad argument: %s: %s", entry, #cond);    \
+            return DCA_E_BADARG;                                       \
+        }                                                              \
+    } while (0)
+
+// what dca_split_planes_scaled (PLANES == 2) and dca_cast_planes_scaled (1: no out_l) do: argument clauses, grid, launch
+template <int PLANES>
+static int launch_planes_scaled(const char* entry, const float* x, int64_t m, int64_t n, int64_t ld, const uint32_t* amax_bits,
+                                void* out_h, void* out_l, int64_t ldo, int64_t n_pad, void* stream) {
+    DCA_ARG_OF(entry, x && out_h && (out_l || PLANES == 1) && m >= 0 && n >= 4 && n % 4 == 0 && ld >= n && ld % 4 == 0 && n_pad >= n &&
+                          n_pad % 4 == 0 && ldo >= n_pad && ldo % 4 == 0);
+    DCA_ARG_OF(entry, (uintptr_t)x % 16 == 0 && ((uintptr_t)out_h | (uintptr_t)out_l) % 8 == 0);  // float4 loads, 8-byte plane stores
+    if (m == 0) return 0;
+    int64_t blocks = (m * (n_pad / 4) + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_planes_scaled<PLANES>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, m, n, ld, amax_bits,
+                       reinterpret_cast<_Float16*>(out_h), reinterpret_cast<_Float16*>(out_l), ldo, n_pad);
+    return launch_check(PLANES == 2 ? "k_planes_scaled<2>" : "k_planes_scaled<1>");
+}
+
+// the same for dca_split_rows_scaled and dca_cast_rows_scaled: one workgroup per row
+template <int PLANES>
+static int launch_rows_scaled(const char* entry, const float* w, int64_t n, int64_t k, int64_t ld, void* out_h, void* out_l, int64_t ldo,
+                              int64_t k_pad, float* col_scale, const uint32_t* other_amax_bits, void* stream) {
+    DCA_ARG_OF(entry, w && out_h && (out_l || PLANES == 1) && col_scale && n >= 0 && n < (1ll << 31) && k >= 4 && k % 4 == 0 && ld >= k &&
+                          ld % 4 == 0 && k_pad >= k && k_pad % 4 == 0 && ldo >= k_pad && ldo % 4 == 0);
+    DCA_ARG_OF(entry, (uintptr_t)w % 16 == 0 && ((uintptr_t)out_h | (uintptr_t)out_l) % 8 == 0);
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_rows_scaled<PLANES>, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, w, k, ld,
+                       reinterpret_cast<_Float16*>(out_h), reinterpret_cast<_Float16*>(out_l), ldo, k_pad, col_scale, other_amax_bits);
+    return launch_check(PLANES == 2 ? "k_rows_scaled<2>" : "k_rows_scaled<1>");
 }
 
 extern "C" {
@@ -774,30 +769,6 @@ int dca_f16_gemm(const void* a_h, int64_t m, int k, int64_t lda, const void* w_h
     return launch_gemm(__func__, k_f16_gemm, "k_f16_gemm", p, stream);
 }
 
-int dca_cast_planes_scaled(const float* x, int64_t m, int64_t n, int64_t ld, const uint32_t* amax_bits, void* out_h, int64_t ldo,
-                           int64_t n_pad, void* stream) {
-    DCA_ARG(x && out_h && m >= 0 && n >= 4 && n % 4 == 0 && ld >= n && ld % 4 == 0 && n_pad >= n && n_pad % 4 == 0 &&
-            ldo >= n_pad && ldo % 4 == 0);
-    DCA_ARG((uintptr_t)x % 16 == 0 && (uintptr_t)out_h % 8 == 0);
-    if (m == 0) return 0;
-    int64_t blocks = (m * (n_pad / 4) + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_cast_planes_scaled, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, m, n, ld, amax_bits,
-                       reinterpret_cast<_Float16*>(out_h), ldo, n_pad);
-    return launch_check("k_cast_planes_scaled");
-}
-
-int dca_cast_rows_scaled(const float* w, int64_t n, int64_t k, int64_t ld, void* out_h, int64_t ldo, int64_t k_pad, float* col_scale,
-                         const uint32_t* other_amax_bits, void* stream) {
-    DCA_ARG(w && out_h && col_scale && n >= 0 && n < (1ll << 31) && k >= 4 && k % 4 == 0 && ld >= k && ld % 4 == 0 &&
-            k_pad >= k && k_pad % 4 == 0 && ldo >= k_pad && ldo % 4 == 0);
-    DCA_ARG((uintptr_t)w % 16 == 0 && (uintptr_t)out_h % 8 == 0);
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(k_cast_rows_scaled, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, w, k, ld,
-                       reinterpret_cast<_Float16*>(out_h), ldo, k_pad, col_scale, other_amax_bits);
-    return launch_check("k_cast_rows_scaled");
-}
-
 int dca_split_planes(const float* x, int64_t m, int64_t n, int64_t ld, void* out_h, void* out_l, int64_t ldo, int* overflow,
                      void* stream) {
     DCA_ARG(x && out_h && out_l && m >= 0 && n >= 4 && n % 4 == 0 && ld >= n && ld % 4 == 0 && ldo >= n && ldo % 4 == 0);
@@ -822,26 +793,22 @@ int dca_absmax_bits(const float* x, int64_t m, int64_t n, int64_t ld, uint32_t* 
 
 int dca_split_planes_scaled(const float* x, int64_t m, int64_t n, int64_t ld, const uint32_t* amax_bits, void* out_h, void* out_l,
                             int64_t ldo, int64_t n_pad, void* stream) {
-    DCA_ARG(x && out_h && out_l && m >= 0 && n >= 4 && n % 4 == 0 && ld >= n && ld % 4 == 0 && n_pad >= n && n_pad % 4 == 0 &&
-            ldo >= n_pad && ldo % 4 == 0);
-    DCA_ARG((uintptr_t)x % 16 == 0 && ((uintptr_t)out_h | (uintptr_t)out_l) % 8 == 0);
-    if (m == 0) return 0;
-    int64_t blocks = (m * (n_pad / 4) + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_split_planes_scaled, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, m, n, ld, amax_bits,
-                       reinterpret_cast<_Float16*>(out_h), reinterpret_cast<_Float16*>(out_l), ldo, n_pad);
-    return launch_check("k_split_planes_scaled");
+    return launch_planes_scaled<2>(__func__, x, m, n, ld, amax_bits, out_h, out_l, ldo, n_pad, stream);
+}
+
+int dca_cast_planes_scaled(const float* x, int64_t m, int64_t n, int64_t ld, const uint32_t* amax_bits, void* out_h, int64_t ldo,
+                           int64_t n_pad, void* stream) {
+    return launch_planes_scaled<1>(__func__, x, m, n, ld, amax_bits, out_h, nullptr, ldo, n_pad, stream);
 }
 
 int dca_split_rows_scaled(const float* w, int64_t n, int64_t k, int64_t ld, void* out_h, void* out_l, int64_t ldo, int64_t k_pad,
                           float* col_scale, const uint32_t* other_amax_bits, void* stream) {
-    DCA_ARG(w && out_h && out_l && col_scale && n >= 0 && n < (1ll << 31) && k >= 4 && k % 4 == 0 && ld >= k && ld % 4 == 0 &&
-            k_pad >= k && k_pad % 4 == 0 && ldo >= k_pad && ldo % 4 == 0);
-    DCA_ARG((uintptr_t)w % 16 == 0 && ((uintptr_t)out_h | (uintptr_t)out_l) % 8 == 0);
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(k_split_rows_scaled, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, w, k, ld,
-                       reinterpret_cast<_Float16*>(out_h), reinterpret_cast<_Float16*>(out_l), ldo, k_pad, col_scale, other_amax_bits);
-    return launch_check("k_split_rows_scaled");
+    return launch_rows_scaled<2>(__func__, w, n, k, ld, out_h, out_l, ldo, k_pad, col_scale, other_amax_bits, stream);
+}
+
+int dca_cast_rows_scaled(const float* w, int64_t n, int64_t k, int64_t ld, void* out_h, int64_t ldo, int64_t k_pad, float* col_scale,
+                         const uint32_t* other_amax_bits, void* stream) {
+    return launch_rows_scaled<1>(__func__, w, n, k, ld, out_h, nullptr, ldo, k_pad, col_scale, other_amax_bits, stream);
 }
 
 int dca_fill_inv_pow2(float* out, int64_t n, const uint32_t* amax_bits, void* stream) {

@@ -327,7 +327,7 @@ def counters(monkeypatch, wgrad_calls):
     from deepcubea_amd import _lib
     from deepcubea_amd.utils.pytorch_models import ResnetModel
     counts = {"linear_f16x3": 0, "onehot": 0, "encode": 0, "wgrad": wgrad_calls}
-    real_lin, real_onehot, real_encode = _lib.linear_f16x3, _lib.onehot, ResnetModel.encode
+    real_lin, real_onehot, real_encode = _lib._train_gemm, _lib.onehot, ResnetModel.encode
 
     def lin(*a, **kw):
         counts["linear_f16x3"] += 1
@@ -341,7 +341,7 @@ def counters(monkeypatch, wgrad_calls):
         counts["encode"] += 1
         return real_encode(self, x)
 
-    monkeypatch.setattr(_lib, "linear_f16x3", lin)
+    monkeypatch.setattr(_lib, "_train_gemm", lin)  # (every forward and input-gradient GEMM of linear_train; the key keeps its name)
     monkeypatch.setattr(_lib, "onehot", onehot)
     monkeypatch.setattr(ResnetModel, "encode", encode)
     return counts
