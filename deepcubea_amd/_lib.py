@@ -70,6 +70,9 @@ _SIGNATURES = {
     "dca_cube3_pdb_index": "i ipipip",
     "dca_cube3_pdb_build": "i ipippp",
     "dca_cube3_pdb_eval": "i plliipppppp",
+    "dca_lightsout_exact_matrix": "i ip",
+    "dca_lightsout_exact_eval": "i ipllpp",
+    "dca_lightsout_exact_solve": "i ipllpp",
     "dca_engine_create": "i piidilii",
     "dca_engine_create_multi": "i piidiliii",
     "dca_engine_num_instances": "i p",
@@ -602,6 +605,37 @@ def cube3_pdb_eval(states: torch.Tensor, row_kind: int, patterns, tables, out: O
     return _pdb_eval("cube3_pdb_eval", "dca_cube3_pdb_eval", states, 54, [g for _, g in patterns], [kind for kind, _ in patterns],
                      _cube3_table_bytes, tables, out,
                      lambda s, n, ld, m, *rest: lib().dca_cube3_pdb_eval(s, n, ld, row_kind, m, *rest))
+
+
+# ------------------------------------------------------------------------------ exact LightsOut heuristic (lightsout7)
+LIGHTSOUT_EXACT_DIM = 7  # the one board size the library instantiates (its press matrix is invertible over GF(2))
+
+
+def lightsout_exact_matrix() -> np.ndarray:
+    """A^-1 over GF(2) as the kernels use it -> uint64 [49]: row a, bit i for cell i (include/dca.h).  No device needed."""
+    out = np.zeros(LIGHTSOUT_EXACT_DIM ** 2, np.uint64)
+    check(lib().dca_lightsout_exact_matrix(LIGHTSOUT_EXACT_DIM, out.ctypes.data_as(C.c_void_p)), "dca_lightsout_exact_matrix")
+    return out
+
+
+def _lightsout_exact(who: str, symbol: str, states: torch.Tensor, out: Optional[torch.Tensor], dtype: torch.dtype) -> torch.Tensor:
+    states, n, ld = _pdb_rows(states, LIGHTSOUT_EXACT_DIM ** 2, who)
+    if out is None:
+        out = torch.empty(n, dtype=dtype, device=states.device)
+    assert out.dtype == dtype and out.is_cuda and out.numel() >= n
+    check(getattr(lib(), symbol)(LIGHTSOUT_EXACT_DIM, _raw(states), n, ld, ptr(out), stream_ptr()), symbol)
+    return out
+
+
+def lightsout_exact_eval(states: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The exact distance popcount(A^-1 row) per row -> f32 [n].  states: uint8 device rows [n, >= 49] with unit byte stride (a
+    strided view is fine); a cell is bit 0 of its byte, so ANY bytes are in bounds (include/dca.h, the bit-0 rule)."""
+    return _lightsout_exact("lightsout_exact_eval", "dca_lightsout_exact_eval", states, out, torch.float32)
+
+
+def lightsout_exact_solve(states: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The optimal solution per row as a 64-bit mask -> int64 [n]: bit a set iff cell a is pressed.  states as for the eval."""
+    return _lightsout_exact("lightsout_exact_solve", "dca_lightsout_exact_solve", states, out, torch.int64)
 
 
 # ------------------------------------------------------------------------------ training step

@@ -117,7 +117,7 @@ __host__ __device__ inline int npuzzle_swap(int dim, int z, int a) {
 
 // LightsOut: does pressing cell `a` flip cell `i`?  (move matrix lights_out.py:33-44 / environments.cpp:133-154:
 // the cell itself, a + dim if its x = a / dim < dim - 1, a - dim if x > 0, a + 1 if its y = a % dim < dim - 1, a - 1 if y > 0)
-__host__ __device__ inline uint32_t lightsout_flip(int dim, int a, int i) {
+constexpr __host__ __device__ inline uint32_t lightsout_flip(int dim, int a, int i) {
     const int x = a / dim, y = a - x * dim;
     return (uint32_t)((i == a) | (x < dim - 1 && i == a + dim) | (x > 0 && i == a - dim) | (y < dim - 1 && i == a + 1) |
                       (y > 0 && i == a - 1));

@@ -49,6 +49,18 @@ def _is_pdb(args) -> bool:
     return str(getattr(args, "model_dir", "")).startswith("pdb:")
 
 
+def _is_exact(args) -> bool:
+    return str(getattr(args, "model_dir", "")).startswith("exact:")
+
+
+def _exact_heuristic(args):
+    """`--model_dir exact:gf2`, no network and no table: the GF(2) solve of lightsout7 (utils/lightsout_exact.py).  ValueError
+    for any other environment or any other name after `exact:`."""
+    from ..utils.lightsout_exact import LightsOutExact, parse_exact_spec
+    parse_exact_spec(args.env, str(args.model_dir).split(":", 1)[1])
+    return LightsOutExact(args.env)
+
+
 def _pattern_database(args):
     """`--model_dir pdb:SPEC`, no network: additive tables for the sliding puzzles (utils/pattern_db.py), corner / edge tables
     combined by max for cube3 (utils/cube3_pdb.py).  Not built yet; ValueError for a spec the environment cannot have."""
@@ -64,6 +76,7 @@ def _load_heuristic(args, env):
     """Device heuristic closure.  `--model_dir synthetic:SEED` builds the environment's network with
     deterministic synthetic weights (the reference checkpoints are not redistributable here)."""
     pdb = _pattern_database(args) if _is_pdb(args) else None  # the spec is checked here, before any device work
+    exact = _exact_heuristic(args) if _is_exact(args) else None  # likewise
     device, devices, on_gpu = nnet_utils.get_device()
     print("device: %s, devices: %s, on_gpu: %s" % (device, devices, on_gpu))
     if not on_gpu:
@@ -73,6 +86,9 @@ def _load_heuristic(args, env):
         pdb.build()
         print("pattern database %s: %d bytes, sweeps %s, built in %.2f s" % (pdb.spec, pdb.bytes, pdb.sweeps, time.time() - start))
         return pdb.heuristic_fn_dev(), 0  # the closure reads the packed uint8 rows of the dedup-first path (stride 0 = no one-hot rows)
+    if exact is not None:
+        print("exact heuristic %s for %s: popcount(A^-1 s) over GF(2), no table" % (exact.spec, exact.env_name))
+        return exact.heuristic_fn_dev(), 0  # as for pdb: the packed uint8 rows, no one-hot rows
     nnet = env.get_nnet_model()
     if str(args.model_dir).startswith("synthetic:"):
         from ..utils.synthetic_weights import load_synthetic_weights
@@ -130,11 +146,11 @@ def auto_instances(args, env, n_states: int, builtin) -> int:
     never more than the states this rank can draw, _AUTO_MAX_INSTANCES, or what `--max_nodes` leaves room for.
     Integer-valued built-ins (manhattan, zero) make every f-level ONE cost tie of up to millions of entries, which only a
     single-instance engine refines with its whole grid: those searches stay at K = 1, and so does a
-    `pdb:` model, whose values are integers too."""
+    `pdb:` or `exact:` model, whose values are integers too."""
     v = str(getattr(args, "instances_per_gpu", "auto")).lower()
     if v != "auto":
         return max(1, int(v))
-    if builtin in (_lib.HEUR_MANHATTAN, _lib.HEUR_ZERO) or _is_pdb(args):
+    if builtin in (_lib.HEUR_MANHATTAN, _lib.HEUR_ZERO) or _is_pdb(args) or _is_exact(args):
         return 1
     per = max(1, int(args.batch_size) * env.get_num_moves())
     want = _AUTO_CHILDREN_BUILTIN if builtin is not None else _MIN_NNET_ROWS
@@ -245,7 +261,11 @@ def build_parser() -> ArgumentParser:
                              "groups of tiles such as 1,2,3,4/5,6,7,8.  On cube3: corner / edge cubie tables combined by max, SPEC a "
                              "preset (corners, korf, korf7; no auto) or groups of cubies of one kind such as "
                              "c0,c1,c2,c3/e0,e1,e2,e3,e4,e5.  Admissible and consistent: with --weight 1 --semantics cpp "
-                             "the solutions are optimal")
+                             "the solutions are optimal.  On lightsout7: exact:gf2 — the exact distance popcount(A^-1 s) by a "
+                             "GF(2) solve, no table and nothing to build.  Use it with a weight below 1 (the reference's "
+                             "line: --weight 0.2 --batch_size 1000): the solutions are still optimal for any weight in (0, 1), while "
+                             "at --weight 1 all 2^h states made by pressing a subset of the solution's cells tie at one f and the "
+                             "search, though correct, can walk millions of them")
     parser.add_argument('--env', type=str, required=True, help="Environment: cube3, puzzle8, puzzle15, puzzle24, puzzle35, puzzle48, lightsout7 "
                                                                       "(puzzle8 has every layer-1 kernel puzzle15 has: no --nnet_dtype mode is on a fall-back there)")
     parser.add_argument('--batch_size', type=int, default=1, help="Batch size for BWAS")

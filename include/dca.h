@@ -306,7 +306,32 @@ int dca_cube3_pdb_eval(const uint8_t* states /*[n, ld]*/, int64_t n, int64_t ld,
                        const int* ks /*host [num_patterns]*/, const uint8_t* const* tables /*host [num_patterns] of device pointers*/,
                        float* out /*[n]*/, void* stream);
 
-/* state hash (a9).  The reference's hash VALUES are process-randomised SipHash (cube3.py:17-21)
+/* Exact LightsOut heuristic (csrc/dca_lightsout_exact.hip; `--env lightsout7 --model_dir exact:gf2`): the true distance of any
+ * state, by linear algebra over GF(2) instead of a table.
+ *   algebra      pressing cell a flips a fixed set of cells, presses commute, and pressing a cell twice is the identity.  A
+ *                state is therefore s = A x (mod 2), x = the cells pressed an odd number of times, A[i][a] = 1 where a press
+ *                of a flips cell i (the move matrix of lights_out.py:33-44; A is symmetric).  On the 7 x 7 board A has rank 49:
+ *                x = A^-1 s is the only press set that makes s, pressing its cells once each, in any order, is the shortest
+ *                solution, and the distance is popcount(A^-1 s).  A^-1 is derived at compile time from the move rule; a board
+ *                size whose matrix is singular (4 x 4, 5 x 5) does not compile.
+ *   bit-0 rule   cell i of a row contributes bit 0 of its byte, b & 1.  The engine pads closure input to a multiple of 1024
+ *                rows whose padding is stale or zero: no byte forms an address, so ANY bytes are in bounds, and a row's value is
+ *                that of the same row reduced to b & 1 (the any-bytes rule).
+ * dca_lightsout_exact_matrix (host only, no device call): rows[a] = row a of A^-1 as the kernels use it, bit i for cell i, bits
+ * 49..63 zero.
+ * dca_lightsout_exact_eval: out[i] = popcount(A^-1 row_i), an integer <= 49, exact in fp32.  dca_lightsout_exact_solve:
+ * presses[i] has bit a set iff cell a is in the optimal solution of row i; popcount(presses[i]) is eval's out[i].  states:
+ * device rows [n, ld], ld >= 49, any byte alignment (word loads when the base pointer and ld are both multiples of 4, byte loads
+ * otherwise).  Stream-ordered, nothing synchronises.
+ * DCA_E_BADARG before any HIP call, the message naming the argument: dim other than 7; a NULL rows; n < 0 or >= 2^31; ld < 49;
+ * a NULL states / out / presses when n > 0 (both may be NULL when n == 0, which launches nothing); out not 4-byte, presses not
+ * 8-byte aligned. */
+int dca_lightsout_exact_matrix(int dim, uint64_t* rows /*host [dim*dim]*/);
+int dca_lightsout_exact_eval(int dim, const uint8_t* states /*[n, ld]*/, int64_t n, int64_t ld, float* out /*[n]*/, void* stream);
+int dca_lightsout_exact_solve(int dim, const uint8_t* states /*[n, ld]*/, int64_t n, int64_t ld, uint64_t* presses /*[n]*/,
+                              void* stream);
+
+/* state hash (a9). The reference's hash VALUES are process-randomised SipHash (cube3.py:17-21)
  * or unpinned boost::hash_range (parallel_weighted_astar.cpp:104-111); what is pinned is key
  * equality.  This library defines, for a D-byte state split in little-endian 8-byte words
  * w_0..w_{ceil(D/8)-1} (last word zero-padded):
