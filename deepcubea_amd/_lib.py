@@ -73,6 +73,8 @@ _SIGNATURES = {
     "dca_lightsout_exact_matrix": "i ip",
     "dca_lightsout_exact_eval": "i ipllpp",
     "dca_lightsout_exact_solve": "i ipllpp",
+    "dca_idastar_npuzzle": "i ipippplpppipppipp",
+    "dca_idastar_cube3": "i pipppplpppipppipp",
     "dca_engine_create": "i piidilii",
     "dca_engine_create_multi": "i piidiliii",
     "dca_engine_num_instances": "i p",
@@ -146,6 +148,8 @@ _SIGNATURES = {
     "dca_engine_set_tiers": "i pll",
     "dca_engine_debug": "i ppp",
     "dca_debug_tune": "i ii",
+    "dca_idastar_host": "i iipipppplpppipppip",
+    "dca_idastar_set_prefix": "i i",
     "dca_debug_write_ceiling": "i pllp",
     "dca_f16x3_gemm_variant": "i i",
     "dca_gemm16_variant": "i i",
@@ -636,6 +640,108 @@ def lightsout_exact_eval(states: torch.Tensor, out: Optional[torch.Tensor] = Non
 def lightsout_exact_solve(states: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The optimal solution per row as a 64-bit mask -> int64 [n]: bit a set iff cell a is pressed.  states as for the eval."""
     return _lightsout_exact("lightsout_exact_solve", "dca_lightsout_exact_solve", states, out, torch.int64)
+
+
+# ------------------------------------------------------------------------------ IDA* on the pattern databases
+IDASTAR_SOLVED, IDASTAR_BUDGET, IDASTAR_UNSOLVABLE = 0, 1, 2
+IDASTAR_STATUS = {IDASTAR_SOLVED: "solved", IDASTAR_BUDGET: "budget exhausted", IDASTAR_UNSOLVABLE: "unsolvable"}
+IDASTAR_POLL_NODES, IDASTAR_MAX_LANES, IDASTAR_MAX_MOVES = 512, 1 << 19, 254  # include/dca.h
+IDASTAR_OVERSHOOT = IDASTAR_MAX_LANES * IDASTAR_POLL_NODES  # total_nodes <= max_nodes + this, whatever the launch
+IDASTAR_MAX_PREFIX = {ENV_NPUZZLE: 15, ENV_CUBE3: 6}  # moves a work item's prefix has at the most
+IDASTAR_MAX_PUZZLE_PATTERNS = 8
+
+
+def _idastar(symbol: str, call, root, width: int, max_nodes: int) -> dict:
+    """What the three searches share: the root's bytes, the output buffers, and the result as a dict shaped like the engine's
+    (solved, moves, path_cost, nodes_generated) plus status, thresholds and nodes_per_threshold.  call(root, max_nodes, *outputs)
+    makes the entry point's call."""
+    root = np.ascontiguousarray(root, dtype=np.uint8).reshape(-1)
+    if root.size != width:
+        raise ValueError("%s: a root of %d bytes, not %d" % (symbol, root.size, width))
+    cap = IDASTAR_MAX_MOVES + 2
+    status, length, count, total = C.c_int(-1), C.c_int(0), C.c_int(0), C.c_int64(0)
+    moves, thresholds, per = np.zeros(cap, np.uint8), np.zeros(cap, np.int32), np.zeros(cap, np.int64)
+
+    def as_p(a):
+        return a.ctypes.data_as(C.c_void_p)
+    check(call(as_p(root), int(max_nodes), C.byref(status), C.byref(length), as_p(moves), cap, C.byref(count), as_p(thresholds),
+               as_p(per), cap, C.byref(total)), symbol)
+    n = min(count.value, cap)
+    solved = status.value == IDASTAR_SOLVED
+    return {"solved": solved, "status": IDASTAR_STATUS[status.value], "moves": [int(m) for m in moves[:length.value]] if solved else [],
+            "path_cost": float(length.value) if solved else float("inf"), "nodes_generated": int(total.value),
+            "thresholds": [int(t) for t in thresholds[:n]], "nodes_per_threshold": [int(c) for c in per[:n]]}
+
+
+def _no_size(family: int, k: int) -> None:
+    return None
+
+
+def _idastar_set(groups, families, tables, host: bool):
+    """The pattern set's marshalled arrays (as the evals build them) and the HOST array of table pointers."""
+    pointers, _, keep = _pdb_set(tuple(tuple(g) for g in groups), tuple(families), _no_size)
+    if len(tables) != len(groups):
+        raise ValueError("%d tables for %d patterns" % (len(tables), len(groups)))
+    if host:
+        keep = (keep, [np.ascontiguousarray(t, dtype=np.uint8).reshape(-1) for t in tables])
+        addresses = [t.ctypes.data for t in keep[1]]
+    else:
+        addresses = [ptr(t) for t in tables]
+    return pointers, (C.c_void_p * max(len(tables), 1))(*addresses), keep
+
+
+def _table_sizes(who: str, sizes, tables, host: bool) -> None:
+    """The library sees a table as an address: a short one would be read past its end, and a host address handed to the kernel
+    (or a device address to the host search) is a fault.  So uint8 device tensors for the device searches, uint8 host arrays for
+    the host search, each of its pattern's size where that is defined (the library refuses the pattern otherwise)."""
+    for i, (size, t) in enumerate(zip(sizes, tables)):
+        if host:
+            if isinstance(t, torch.Tensor) or np.asarray(t).dtype != np.uint8:
+                raise ValueError("%s: table %d is not a uint8 host array" % (who, i))
+            n = int(np.asarray(t).size)
+        else:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
+                raise ValueError("%s: table %d is not a contiguous uint8 device tensor" % (who, i))
+            n = int(t.numel())
+        if size is not None and n != size:
+            raise ValueError("%s: a table of %d elements for a pattern that needs %d bytes" % (who, n, size))
+
+
+def idastar_npuzzle(dim: int, root, partition, tables, max_nodes: int) -> dict:
+    """Optimal solution of one sliding-puzzle root by IDA* on the device tables of `partition` (include/dca.h "IDA*") -> dict.
+    Synchronises once per threshold."""
+    _table_sizes("idastar_npuzzle", [_pdb_table_bytes(dim, len(g)) for g in partition], tables, False)
+    (_, ids, ks), ptrs, _keep = _idastar_set(partition, (dim,) * len(partition), tables, False)
+    return _idastar("dca_idastar_npuzzle", lambda r, n, *out: lib().dca_idastar_npuzzle(dim, r, len(partition), ids, ks, ptrs, n, *out,
+                                                                                        stream_ptr()), root, max(dim, 0) ** 2, max_nodes)
+
+
+def idastar_cube3(root, patterns, tables, max_nodes: int) -> dict:
+    """Optimal solution of one cube3 root (54 sticker ids) by IDA* on the device tables of `patterns` [(kind, cubies), ...]."""
+    _table_sizes("idastar_cube3", [_cube3_table_bytes(kind, len(g)) for kind, g in patterns], tables, False)
+    (kinds, ids, ks), ptrs, _keep = _idastar_set([g for _, g in patterns], [kind for kind, _ in patterns], tables, False)
+    return _idastar("dca_idastar_cube3", lambda r, n, *out: lib().dca_idastar_cube3(r, len(patterns), kinds, ids, ks, ptrs, n, *out,
+                                                                                    stream_ptr()), root, 54, max_nodes)
+
+
+def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int) -> dict:
+    """The same search run sequentially on the CPU from HOST tables (include/dca_debug.h): no device needed.  patterns: the
+    partition (puzzles) or [(kind, cubies), ...] (cube3); tables: one uint8 array per pattern."""
+    if env == ENV_CUBE3:
+        groups, families = [g for _, g in patterns], [kind for kind, _ in patterns]
+        sizes, width = [_cube3_table_bytes(kind, len(g)) for kind, g in patterns], 54
+    else:
+        groups, families = list(patterns), [dim] * len(patterns)
+        sizes, width = [_pdb_table_bytes(dim, len(g)) for g in patterns], max(dim, 0) ** 2
+    _table_sizes("idastar_host", sizes, tables, True)
+    (kinds, ids, ks), ptrs, _keep = _idastar_set(groups, families, tables, True)
+    return _idastar("dca_idastar_host", lambda r, n, *out: lib().dca_idastar_host(env, dim, r, len(groups), kinds, ids, ks, ptrs, n, *out),
+                    root, width, max_nodes)
+
+
+def idastar_set_prefix(depth: int) -> None:
+    """Test hook: the prefix depth of every work item (-1 = chosen from the previous iteration's node count)."""
+    check(lib().dca_idastar_set_prefix(depth), "dca_idastar_set_prefix")
 
 
 # ------------------------------------------------------------------------------ training step

@@ -1,0 +1,752 @@
+// dca_idastar.hip — iterative-deepening A* on the pattern databases (include/dca.h "IDA*"): optimal solutions with no OPEN, no
+// CLOSED and no node pool.  Memory is the tables plus a packed move stack per lane.
+//
+//   frame    ida_lane<D> is one depth-first search as a flat state machine over a domain D (the sliding puzzles of dim 3, 4, 5;
+//            cube3).  One loop iteration handles one node: the lane makes the next child of its current node, evaluates h, and
+//            either descends (f <= T), goes on to the next sibling, or — no sibling left — backtracks by undoing its last move
+//            (moves invert with a ^ 1: no stack of states, only the move stack, kept in LDS).  The state lives in registers: the
+//            puzzles' board packed 4 or 5 bits a position with the blank and one running table index per pattern, cube3's two
+//            words of cubie locations.  The same function, compiled for the host, is the sequential search of
+//            dca_idastar_host (include/dca_debug.h).
+//   work     item i of an iteration names a move prefix of P moves, the mixed-radix digits of i (first move = most significant
+//            digit; cube3: radix 12; puzzles: 4 for the first move, then 3 — a digit picks among the moves that do not undo
+//            the one before).  A lane replays the prefix from the root under the pruning rules and the f <= T test and drops the item
+//            where the prefix is pruned; below the prefix it searches depth first and never backtracks above it.  Items are
+//            handed out by one agent-scope counter; a lane whose item is finished takes the next one in the same loop, so a wave
+//            lives until the list is empty.  No lane waits for another: no barrier after the LDS staging, no spin.
+//   counts   every retained child whose h is evaluated counts once.  A prefix node that several items replay is counted by the
+//            item whose remaining digits are all 0, so a completed iteration's count does not depend on which lane ran what.
+//   ending   the first lane at the goal claims a word by compare-and-swap and writes its moves; a lane adds its count to the
+//            launch's counter every DCA_IDASTAR_POLL_NODES nodes (sooner under a tight budget: ida_poll), stops when that
+//            passes the budget and polls the stop word there.  Whoever stops the launch also sets the item counter's top bit,
+//            which ends every other lane's item fetch.
+//
+// Rates are in profiles/idastar_probe.txt.
+#include <mutex>
+#include <type_traits>
+
+#include "dca_pdb_cube3.h"
+#include "dca_pdb_puzzle.h"
+
+namespace dca {
+
+constexpr int kIdaThreads = 256;
+constexpr int kIdaMaxBlocks = DCA_IDASTAR_MAX_LANES / kIdaThreads;
+constexpr int kIdaBlocksPerCu = 8;
+constexpr int kIdaPuzzlePatterns = 8;  // running indices a lane keeps in registers
+constexpr uint32_t kIdaPoll = DCA_IDASTAR_POLL_NODES;
+constexpr uint32_t kIdaMaxT = DCA_IDASTAR_MAX_MOVES;  // thresholds above it: unsolvable
+constexpr uint32_t kIdaNoMove = 0xFEu;                // "no previous move": matches no rule (even, and its face is no face)
+constexpr uint32_t kIdaStopItems = 0x80000000u;       // the item counter's top bit: every later fetch is past the list's end
+constexpr uint32_t kIdaSolved = 1u, kIdaBudget = 2u;  // bits of IdaCtrl::stop
+
+// One launch's control block (device memory, or host memory for the host search); all zero in front of every launch.
+struct IdaCtrl {
+    unsigned long long nodes;  // counted nodes of this launch
+    uint32_t next_item;
+    uint32_t stop;
+    uint32_t claim;   // 0 -> 1 by the lane that writes the solution
+    uint32_t best;    // 0xFFFFFFFF - (the smallest f above T seen), 0 = none: a max, so that zero is "nothing yet"
+    uint32_t length;  // of the solution
+    uint32_t pad;
+    uint8_t moves[256];
+};
+
+#define DCA_IDA_INLINE __host__ __device__ inline __attribute__((always_inline))
+#define DCA_IDA_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+// ------------------------------------------------------------------------------------------------------ sliding puzzles
+struct PzMaps {  // tile -> (its weight N^(digit) in its pattern's index, its pattern; 0xFF: the tile is in no pattern)
+    uint64_t w[32];
+    uint32_t p[32];
+};
+
+template <int DIM>
+struct PzDomain {
+    static constexpr int N = DIM * DIM, NM = 4, RADIX = 3, MOVE_BITS = 2, MAX_PREFIX = 15, STACK_WORDS = 16;
+    static constexpr int BITS = N <= 16 ? 4 : 5;
+    using Board = std::conditional_t<(N * BITS <= 64), uint64_t, unsigned __int128>;
+    struct State {
+        Board board;                        // position i holds tile (board >> BITS * i) & MASK
+        uint32_t blank;                     // the blank's position
+        uint64_t idx[kIdaPuzzlePatterns];  // per pattern: its table index without the blank digit
+    };
+    struct Ctx {
+        const uint64_t* tile_w;
+        const uint32_t* tile_p;
+        const uint8_t* table[kIdaPuzzlePatterns];
+        int np;
+    };
+    static constexpr Board MASK = (1u << BITS) - 1u;
+    static constexpr Board goal_board() {
+        Board b = 0;
+        for (int i = 0; i < N; i++) b |= (Board)((i + 1) % N) << (BITS * i);
+        return b;
+    }
+
+    // A prefix digit's move: the first digit is the move itself, a later one counts the moves other than the undo of m.
+    static DCA_IDA_INLINE uint32_t digit_move(uint32_t d, uint32_t m) { return m == kIdaNoMove ? d : d + (d >= (m ^ 1u) ? 1u : 0u); }
+    // Is a prefix depth p (that many items) worth it after an iteration of `prev` nodes?  A board has about 2.13 children a
+    // node, so few of the items survive their replay and only a deep prefix feeds the chip; a dropped item costs a counter
+    // add and the nodes up to its first illegal or pruned move, all lanes busy, and this iteration is several times `prev`.
+    static bool worth(int64_t items, int, int64_t prev) { return items <= 8 * prev; }
+    // the rules: no no-op move, no undoing of the previous move
+    static DCA_IDA_INLINE bool legal(const State& s, uint32_t a, uint32_t m, uint32_t) {
+        return a != (m ^ 1u) && (uint32_t)npuzzle_swap(DIM, (int)s.blank, (int)a) != s.blank;
+    }
+    // the blank trades places with the tile t at nb: t's digit goes nb -> blank in its pattern's index, the blank digit is added
+    // at the gather.  (A no-op move — only ever asked for as a legal one — would leave the state as it is.)
+    static DCA_IDA_INLINE State apply(const State& s, uint32_t a, const Ctx& c) {
+        const uint32_t nb = (uint32_t)npuzzle_swap(DIM, (int)s.blank, (int)a);
+        const uint32_t t = (uint32_t)((s.board >> (BITS * nb)) & MASK);
+        State r;
+        r.board = (s.board & ~(MASK << (BITS * nb))) | ((Board)t << (BITS * s.blank));
+        r.blank = nb;
+        const uint64_t w = c.tile_w[t];  // t < 2^BITS <= 32
+        const uint32_t p = c.tile_p[t];
+        const uint64_t delta = w * (uint64_t)s.blank - w * (uint64_t)nb;  // modulo 2^64: the sum is the exact index
+#pragma unroll
+        for (int q = 0; q < kIdaPuzzlePatterns; q++) r.idx[q] = s.idx[q] + (p == (uint32_t)q ? delta : 0ull);
+        return r;
+    }
+    static DCA_IDA_INLINE uint32_t h(const State& s, const Ctx& c) {
+        uint32_t sum = 0;
+#pragma unroll
+        for (int q = 0; q < kIdaPuzzlePatterns; q++)
+            if (q < c.np) sum += c.table[q][s.idx[q] + s.blank];  // every digit < N: inside the table
+        return sum;
+    }
+    static DCA_IDA_INLINE bool goal(const State& s) { return s.board == goal_board(); }
+};
+
+// ---------------------------------------------------------------------------------------------------------------- cube3
+struct C3Domain {
+    static constexpr int NM = 12, RADIX = 12, MOVE_BITS = 4, MAX_PREFIX = 6, STACK_WORDS = 32;
+    struct State {
+        uint64_t corner, edge;  // c3_row_locs: 5 bits a cubie
+    };
+    struct Ctx {
+        const uint8_t* mv;  // [2][12][24]: kind, move, location -> location
+        const C3Set* set;
+    };
+    static constexpr uint64_t home(int n, int o) {
+        uint64_t w = 0;
+        for (int q = 0; q < n; q++) w |= (uint64_t)(q * o) << (5 * q);
+        return w;
+    }
+
+    static DCA_IDA_INLINE uint32_t digit_move(uint32_t d, uint32_t) { return d; }
+    // Is a prefix depth p worth it after an iteration of `prev` nodes?  Replaying every item's prefix (at most p nodes an
+    // item) then costs less than half of the previous, 13 times smaller, iteration.
+    static bool worth(int64_t items, int p, int64_t prev) { return items * p <= prev / 2; }
+    // a = 2 face + dir: no undo; a half turn with the even action only; no third turn of a kind; opposite faces ascending
+    static DCA_IDA_INLINE bool legal(const State&, uint32_t a, uint32_t m, uint32_t mp) {
+        const uint32_t fa = a >> 1, fm = m >> 1;
+        return !(a == (m ^ 1u) || (a == m && (a & 1u)) || (a == m && m == mp) || (fa == (fm ^ 1u) && fa < fm));
+    }
+    static DCA_IDA_INLINE State apply(const State& s, uint32_t a, const Ctx& c) {
+        State r{0ull, 0ull};
+        const uint8_t* mc = c.mv + a * kC3Locs;
+        const uint8_t* me = c.mv + (12 + a) * kC3Locs;
+#pragma unroll
+        for (int q = 0; q < 8; q++) r.corner |= (uint64_t)mc[(s.corner >> (5 * q)) & 31u] << (5 * q);  // locations stay < 24
+#pragma unroll
+        for (int q = 0; q < 12; q++) r.edge |= (uint64_t)me[(s.edge >> (5 * q)) & 31u] << (5 * q);
+        return r;
+    }
+    static DCA_IDA_INLINE uint32_t h(const State& s, const Ctx& c) {
+        const C3Set& set = *c.set;
+        uint32_t best = 0;
+        for (int p0 = 0; p0 < set.np; p0 += 4) {  // four independent gathers in flight
+            uint32_t v[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                v[q] = 0;
+                const int pi = p0 + q;
+                if (pi < set.np) {
+                    const uint64_t idx = set.kind[pi] == DCA_CUBE3_CORNERS ? c3_index<DCA_CUBE3_CORNERS>(s.corner, set.pat[pi], set.k[pi])
+                                                                           : c3_index<DCA_CUBE3_EDGES>(s.edge, set.pat[pi], set.k[pi]);
+                    v[q] = set.table[pi][idx];
+                }
+            }
+            const uint32_t x = v[0] > v[1] ? v[0] : v[1], y = v[2] > v[3] ? v[2] : v[3];
+            best = best > x ? best : x;
+            best = best > y ? best : y;
+        }
+        return best;
+    }
+    // every cubie at its home location (h = 0 is not the goal: a corners-only set is 0 on unsolved states)
+    static DCA_IDA_INLINE bool goal(const State& s) { return s.corner == home(8, 3) && s.edge == home(12, 2); }
+};
+
+// ------------------------------------------------------------------------------------------------------------ the frame
+// One lane's share of one iteration (threshold T, prefix depth P, n_items = NM * RADIX^(P-1) < 2^31 work items).  stk: the lane's move
+// stack, word w at stk[w * stride].  budget: the nodes this launch may still count; poll: the nodes between a lane's flushes.
+template <typename D>
+DCA_IDA_INLINE void ida_lane(const typename D::Ctx& c, const typename D::State& root, IdaCtrl* ctrl, uint32_t* stk, uint32_t stride,
+                             uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
+    constexpr uint32_t PER = 32u / D::MOVE_BITS, MM = (1u << D::MOVE_BITS) - 1u, NM = D::NM;
+    typename D::State s = root;
+    uint32_t g = 0, item = 0, cursor = 0, m1 = kIdaNoMove, m2 = kIdaNoMove, since = 0, best = 0;
+    bool have = false;
+    const auto stack_get = [&](uint32_t d) { return (stk[(d / PER) * stride] >> ((d % PER) * D::MOVE_BITS)) & MM; };
+    for (;;) {
+        if (!have) {  // the next item, from the root
+            item = __hip_atomic_fetch_add(&ctrl->next_item, 1u, DCA_IDA_RLX);
+            if (item >= n_items) break;
+            s = root;
+            g = 0;
+            cursor = 0;
+            m1 = m2 = kIdaNoMove;
+            have = true;
+        }
+        const bool replay = g < P;
+        uint32_t a, below = 1;  // below = RADIX^(digits after this one)
+        if (replay) {
+            for (uint32_t d = g + 1; d < P; d++) below *= (uint32_t)D::RADIX;
+            const uint32_t q = item / below;  // (the first digit's radix is NM: no digit above it)
+            a = D::digit_move(g == 0u ? q : q % (uint32_t)D::RADIX, m1);
+            if (!D::legal(s, a, m1, m2)) {
+                have = false;
+                continue;
+            }
+        } else {
+            while (cursor < NM && !D::legal(s, cursor, m1, m2)) cursor++;
+            if (cursor >= NM) {
+                if (g == P) {  // the item's subtree is exhausted
+                    have = false;
+                    continue;
+                }
+                s = D::apply(s, m1 ^ 1u, c);  // backtrack: undo the last move, go on with its next sibling
+                cursor = m1 + 1u;
+                g--;
+                m1 = m2;
+                m2 = g >= 2u ? stack_get(g - 2u) : kIdaNoMove;
+                continue;
+            }
+            a = cursor;
+        }
+        const typename D::State ch = D::apply(s, a, c);
+        const uint32_t f = g + 1u + D::h(ch, c);
+        since += (!replay || item % below == 0u) ? 1u : 0u;  // a replayed node: counted by the item whose later digits are 0
+        if (f <= T) {
+            uint32_t* word = stk + (g / PER) * stride;
+            const uint32_t sh = (g % PER) * D::MOVE_BITS;
+            *word = (*word & ~(MM << sh)) | (a << sh);
+            if (D::goal(ch)) {
+                uint32_t free_word = 0u;  // the first claim writes; the host reads after the launch
+                if (__hip_atomic_compare_exchange_strong(&ctrl->claim, &free_word, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                         __HIP_MEMORY_SCOPE_AGENT)) {
+                    for (uint32_t d = 0; d <= g; d++) ctrl->moves[d] = (uint8_t)stack_get(d);
+                    ctrl->length = g + 1u;
+                }
+                __hip_atomic_fetch_or(&ctrl->stop, kIdaSolved, DCA_IDA_RLX);
+                __hip_atomic_fetch_or(&ctrl->next_item, kIdaStopItems, DCA_IDA_RLX);
+                break;
+            }
+            s = ch;
+            m2 = m1;
+            m1 = a;
+            g++;
+            cursor = 0;
+        } else {
+            const uint32_t inv = 0xFFFFFFFFu - f;
+            best = best > inv ? best : inv;
+            if (replay)
+                have = false;
+            else
+                cursor = a + 1u;
+        }
+        if (since >= poll) {
+            const unsigned long long before = __hip_atomic_fetch_add(&ctrl->nodes, (unsigned long long)since, DCA_IDA_RLX);
+            const bool over = before + since > budget;
+            since = 0;
+            if (over) {
+                __hip_atomic_fetch_or(&ctrl->stop, kIdaBudget, DCA_IDA_RLX);
+                __hip_atomic_fetch_or(&ctrl->next_item, kIdaStopItems, DCA_IDA_RLX);
+                break;
+            }
+            if (__hip_atomic_load(&ctrl->stop, DCA_IDA_RLX) != 0u) break;
+        }
+    }
+    if (since != 0u) __hip_atomic_fetch_add(&ctrl->nodes, (unsigned long long)since, DCA_IDA_RLX);
+    if (best != 0u) __hip_atomic_fetch_max(&ctrl->best, best, DCA_IDA_RLX);
+}
+
+// -------------------------------------------------------------------------------------------------------------- kernels
+template <int DIM>
+struct PzArgs {
+    typename PzDomain<DIM>::State root;
+    const uint8_t* table[kIdaPuzzlePatterns];
+    int np;
+};
+
+template <int DIM>
+__global__ __launch_bounds__(kIdaThreads) void ida_puzzle_kernel(PzArgs<DIM> args, PzMaps maps, IdaCtrl* ctrl, uint32_t T, uint32_t P,
+                                                                 uint32_t n_items, unsigned long long budget, uint32_t poll) {
+    using D = PzDomain<DIM>;
+    __shared__ uint64_t tile_w[32];
+    __shared__ uint32_t tile_p[32];
+    __shared__ uint32_t stk[D::STACK_WORDS * kIdaThreads];
+    if (threadIdx.x == 0) {  // (constant indices into the kernel argument: scalar loads, no private copy of the struct)
+#pragma unroll
+        for (int t = 0; t < 32; t++) {
+            tile_w[t] = maps.w[t];
+            tile_p[t] = maps.p[t];
+        }
+    }
+    __syncthreads();
+    typename D::Ctx c;
+    c.tile_w = tile_w;
+    c.tile_p = tile_p;
+#pragma unroll
+    for (int q = 0; q < kIdaPuzzlePatterns; q++) c.table[q] = args.table[q];
+    c.np = args.np;
+    ida_lane<D>(c, args.root, ctrl, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
+}
+
+struct C3IdaMoves {
+    uint32_t w[2 * 12 * kC3Locs / 4];  // both kinds' location-move tables as words
+};
+
+__global__ __launch_bounds__(kIdaThreads) void ida_cube3_kernel(C3Domain::State root, C3Set set, C3IdaMoves mt, IdaCtrl* ctrl, uint32_t T,
+                                                                uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
+    __shared__ uint32_t mvw[2 * 12 * kC3Locs / 4];
+    __shared__ uint32_t stk[C3Domain::STACK_WORDS * kIdaThreads];
+    if (threadIdx.x == 0) {  // (constant indices into the kernel argument: scalar loads, no private copy of the struct)
+#pragma unroll
+        for (int q = 0; q < 2 * 12 * kC3Locs / 4; q++) mvw[q] = mt.w[q];
+    }
+    __syncthreads();
+    C3Domain::Ctx c;
+    c.mv = (const uint8_t*)mvw;
+    c.set = &set;
+    ida_lane<C3Domain>(c, root, ctrl, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
+}
+
+// ----------------------------------------------------------------------------------------------------------- host side
+struct IdaOut {
+    int* status;
+    int* length;
+    uint8_t* moves;
+    int moves_cap;
+    int* num_thresholds;
+    int* thresholds;
+    int64_t* nodes_per_threshold;
+    int thresholds_cap;
+    int64_t* total_nodes;
+};
+
+static int g_ida_forced_prefix = -1;  // dca_idastar_set_prefix
+
+template <typename D>
+static uint32_t ida_items(uint32_t P) {
+    uint32_t n = P == 0u ? 1u : (uint32_t)D::NM;
+    for (uint32_t d = 1; d < P; d++) n *= (uint32_t)D::RADIX;
+    return n;
+}
+
+// The prefix depth of an iteration from the node count of the one before: the deepest P the family finds worth its items
+// (D::worth); 0 — one item, one lane — for the first iterations.
+template <typename D>
+static uint32_t ida_prefix(int64_t prev_nodes) {
+    if (g_ida_forced_prefix >= 0) return (uint32_t)(g_ida_forced_prefix < D::MAX_PREFIX ? g_ida_forced_prefix : D::MAX_PREFIX);
+    uint32_t p = 0;
+    while (p < (uint32_t)D::MAX_PREFIX && D::worth((int64_t)ida_items<D>(p + 1u), (int)p + 1, prev_nodes)) p++;
+    return p;
+}
+
+// The nodes between a lane's flushes: DCA_IDASTAR_POLL_NODES, or less where the budget left is small against the lanes in
+// flight — budget / (2 lanes), so that what the lanes hold unflushed stays under half of the budget (or one node a lane).
+static uint32_t ida_poll(unsigned long long budget, int lanes) {
+    const unsigned long long p = budget / (2ull * (unsigned long long)lanes);
+    return (uint32_t)(p < 1 ? 1 : p < kIdaPoll ? p : kIdaPoll);
+}
+
+// The threshold loop both searches share.  run(T, P, n_items, budget, ctrl) runs one iteration and fills `ctrl` (host copy).
+template <typename D, typename Run>
+static int ida_drive(uint32_t h_root, bool root_dead, bool root_goal, int64_t max_nodes, const IdaOut& out, Run run) {
+    *out.status = DCA_IDASTAR_UNSOLVABLE;
+    *out.length = 0;
+    *out.num_thresholds = 0;
+    *out.total_nodes = 0;
+    if (root_dead) return 0;  // a table says the goal cannot be reached from the root
+    if (root_goal) {
+        *out.status = DCA_IDASTAR_SOLVED;
+        return 0;
+    }
+    int64_t total = 0, prev = 0;
+    uint32_t T = h_root;
+    for (int it = 0; T <= kIdaMaxT; it++) {
+        const uint32_t P = ida_prefix<D>(prev);
+        const uint32_t n_items = ida_items<D>(P);
+        IdaCtrl ctrl{};
+        if (int rc = run(T, P, n_items, (unsigned long long)(max_nodes - total), ctrl)) return rc;
+        prev = (int64_t)ctrl.nodes;
+        total += prev;
+        if (it < out.thresholds_cap) {
+            out.thresholds[it] = (int)T;
+            out.nodes_per_threshold[it] = prev;
+        }
+        *out.num_thresholds = it + 1;
+        *out.total_nodes = total;
+        if (ctrl.stop & kIdaSolved) {
+            *out.status = DCA_IDASTAR_SOLVED;
+            *out.length = (int)ctrl.length;
+            for (int d = 0; d < (int)ctrl.length && d < out.moves_cap; d++) out.moves[d] = ctrl.moves[d];
+            return 0;
+        }
+        if ((ctrl.stop & kIdaBudget) || total >= max_nodes) {
+            *out.status = DCA_IDASTAR_BUDGET;
+            return 0;
+        }
+        if (ctrl.best == 0u) return 0;  // no child above the threshold: the whole space was searched
+        T = 0xFFFFFFFFu - ctrl.best;
+    }
+    return 0;
+}
+
+static int ida_check_out(const char* who, int64_t max_nodes, const IdaOut& o) {
+    if (max_nodes <= 0) {
+        set_error("bad argument: %s: max_nodes = %lld is not positive", who, (long long)max_nodes);
+        return DCA_E_BADARG;
+    }
+    if (!o.status || !o.length || !o.num_thresholds || !o.total_nodes) {
+        set_error("bad argument: %s: status, length, num_thresholds and total_nodes must not be NULL", who);
+        return DCA_E_BADARG;
+    }
+    if (o.moves_cap < 0 || (o.moves_cap > 0 && !o.moves)) {
+        set_error("bad argument: %s: moves: NULL with moves_cap = %d", who, o.moves_cap);
+        return DCA_E_BADARG;
+    }
+    if (o.thresholds_cap < 0 || (o.thresholds_cap > 0 && (!o.thresholds || !o.nodes_per_threshold))) {
+        set_error("bad argument: %s: thresholds / nodes_per_threshold: NULL with thresholds_cap = %d", who, o.thresholds_cap);
+        return DCA_E_BADARG;
+    }
+    return 0;
+}
+
+// the root's bytes: a permutation of 0..N-1 of the goal's parity, or a refusal
+static int ida_check_puzzle_root(const char* who, int dim, const uint8_t* root) {
+    const int N = dim * dim;
+    uint64_t seen = 0;
+    int blank = 0;
+    for (int i = 0; i < N; i++) {
+        const int t = root[i];
+        if (t >= N) {
+            set_error("bad argument: %s: root: byte %d at position %d is not a tile of a %d x %d board", who, t, i, dim, dim);
+            return DCA_E_BADARG;
+        }
+        if ((seen >> t) & 1) {
+            set_error("bad argument: %s: root: tile %d appears twice", who, t);
+            return DCA_E_BADARG;
+        }
+        seen |= 1ull << t;
+        if (t == 0) blank = i;
+    }
+    int inv = 0;
+    for (int i = 0; i < N; i++)
+        for (int j = i + 1; j < N; j++) inv += root[i] != 0 && root[j] != 0 && root[i] > root[j];
+    // a horizontal blank move keeps the tiles' order; a vertical one carries a tile past dim - 1 others
+    const int parity = (inv + (dim % 2 == 0 ? dim - 1 - blank / dim : 0)) & 1;
+    if (parity) {
+        set_error("bad argument: %s: root: the permutation has the wrong parity, the goal cannot be reached from it", who);
+        return DCA_E_BADARG;
+    }
+    return 0;
+}
+
+static int ida_check_cube3_root(const char* who, const uint8_t* root) {
+    uint64_t seen = 0;
+    for (int i = 0; i < 54; i++) {
+        const int t = root[i];
+        if (t >= 54 || ((seen >> t) & 1)) {
+            set_error("bad argument: %s: root: byte %d at position %d: the 54 bytes are not the sticker ids 0..53 once each", who, t, i);
+            return DCA_E_BADARG;
+        }
+        seen |= 1ull << t;
+    }
+    return 0;
+}
+
+static int ida_blocks(uint32_t n_items) {
+    static int cap = 0;  // (the same value whoever writes it)
+    if (cap == 0) {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+            cus = 1;
+        cap = cus * kIdaBlocksPerCu < kIdaMaxBlocks ? cus * kIdaBlocksPerCu : kIdaMaxBlocks;
+    }
+    const uint32_t b = (n_items + kIdaThreads - 1) / kIdaThreads;
+    return (int)(b < (uint32_t)cap ? b : (uint32_t)cap);
+}
+
+// The root's table bytes, v[p] = table[p][idx[p]]: device memory (the copies queued, then one synchronise) or host memory.
+static int ida_root_bytes(bool on_device, int np, const uint8_t* const* table, const uint64_t* idx, hipStream_t st, uint8_t* v) {
+    if (!on_device) {
+        for (int p = 0; p < np; p++) v[p] = table[p][idx[p]];
+        return 0;
+    }
+    hipError_t e = hipSuccess;
+    for (int p = 0; p < np && e == hipSuccess; p++) e = hipMemcpyAsync(v + p, table[p] + idx[p], 1, hipMemcpyDeviceToHost, st);
+    const hipError_t sync = hipStreamSynchronize(st);  // also after a failure: no copy into v is left pending
+    if (e == hipSuccess) e = sync;
+    return e == hipSuccess ? 0 : hip_fail(e, "IDA*: the root's table bytes");
+}
+
+// A search's control block.  hipFree synchronises the device, so a search that ends well leaves its block in a one-entry slot
+// and the next search on that device takes it from there.  A search holds its block alone: two searches at once (two host
+// threads) find the slot empty for one of them, which allocates its own and frees it where the slot is full again.  A search
+// that ends on an error frees its block (a launch may still be writing it; the free waits for it).
+static std::mutex g_ida_slot_mutex;
+static IdaCtrl* g_ida_slot = nullptr;
+static int g_ida_slot_device = -1;
+
+static int ida_block_take(IdaCtrl*& block, int& device) {
+    DCA_HIP(hipGetDevice(&device));
+    {
+        std::lock_guard<std::mutex> lock(g_ida_slot_mutex);
+        if (g_ida_slot != nullptr && g_ida_slot_device == device) {
+            block = g_ida_slot;
+            g_ida_slot = nullptr;
+            return 0;
+        }
+    }
+    DCA_HIP(hipMalloc((void**)&block, sizeof(IdaCtrl)));
+    return 0;
+}
+
+static void ida_block_give(IdaCtrl* block, int device, bool idle) {
+    if (block == nullptr) return;
+    if (idle) {
+        std::lock_guard<std::mutex> lock(g_ida_slot_mutex);
+        if (g_ida_slot == nullptr) {
+            g_ida_slot = block;
+            g_ida_slot_device = device;
+            return;
+        }
+    }
+    (void)hipFree(block);
+}
+
+// One iteration on the device: zero the block, launch, read the block back (this synchronises the stream).
+template <typename Launch>
+static int ida_device_iteration(IdaCtrl* dev, IdaCtrl& ctrl, hipStream_t st, const char* name, Launch launch) {
+    DCA_HIP(hipMemsetAsync(dev, 0, sizeof(IdaCtrl), st));
+    launch();
+    if (int rc = launch_check(name)) return rc;
+    DCA_HIP(hipMemcpyAsync(&ctrl, dev, sizeof(IdaCtrl), hipMemcpyDeviceToHost, st));
+    DCA_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+template <int DIM>
+static int ida_puzzle(const uint8_t* root, const PdbSet& set, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
+    using D = PzDomain<DIM>;
+    constexpr int N = D::N;
+    PzMaps maps{};
+    for (int t = 0; t < 32; t++) maps.p[t] = 0xFFu;
+    PzArgs<DIM> args{};
+    args.np = set.np;
+    int pos[N];
+    for (int i = 0; i < N; i++) {
+        pos[root[i]] = i;
+        args.root.board |= (typename D::Board)root[i] << (D::BITS * i);
+    }
+    args.root.blank = (uint32_t)pos[0];
+    uint64_t root_idx[kIdaPuzzlePatterns] = {};
+    for (int p = 0; p < set.np; p++) {
+        uint64_t w = N;  // the blank is digit 0, tiles[j] digit j + 1
+        for (int j = 0; j < set.k[p]; j++, w *= N) {
+            const int t = set.pat[p].id[j];
+            maps.w[t] = w;
+            maps.p[t] = (uint32_t)p;
+            args.root.idx[p] += w * (uint64_t)pos[t];
+        }
+        args.table[p] = set.table[p];
+        root_idx[p] = args.root.idx[p] + args.root.blank;
+    }
+    uint8_t v[kIdaPuzzlePatterns] = {};
+    if (int rc = ida_root_bytes(on_device, set.np, set.table, root_idx, st, v)) return rc;
+    uint32_t h_root = 0;
+    bool dead = false;
+    for (int p = 0; p < set.np; p++) {
+        dead = dead || v[p] >= kPdbInf;
+        h_root += v[p];
+    }
+    IdaCtrl* dev = nullptr;
+    int device = -1;
+    if (on_device && !dead && !D::goal(args.root))
+        if (int rc = ida_block_take(dev, device)) return rc;
+    const int rc = ida_drive<D>(h_root, dead, D::goal(args.root), max_nodes, out,
+                                [&](uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, IdaCtrl& ctrl) {
+        if (on_device)
+            return ida_device_iteration(dev, ctrl, st, "ida_puzzle_kernel", [&] {
+                hipLaunchKernelGGL(ida_puzzle_kernel<DIM>, dim3(ida_blocks(n_items)), dim3(kIdaThreads), 0, st, args, maps, dev, T, P, n_items, budget,
+                                   ida_poll(budget, ida_blocks(n_items) * kIdaThreads));
+            });
+        typename D::Ctx c;
+        c.tile_w = maps.w;
+        c.tile_p = maps.p;
+        for (int q = 0; q < kIdaPuzzlePatterns; q++) c.table[q] = args.table[q];
+        c.np = args.np;
+        uint32_t stk[D::STACK_WORDS] = {};
+        ida_lane<D>(c, args.root, &ctrl, stk, 1u, T, P, n_items, budget, ida_poll(budget, 1));
+        return 0;
+    });
+    ida_block_give(dev, device, rc == 0);
+    return rc;
+}
+
+static int ida_cube3(const uint8_t* root, const C3Set& set, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
+    uint32_t w[14];
+    pdb_load_row<54, 1>(root, w);
+    C3Domain::State s0;
+    s0.corner = c3_row_locs<DCA_CUBE3_CORNERS, DCA_ROWS_STATE>(w);
+    s0.edge = c3_row_locs<DCA_CUBE3_EDGES, DCA_ROWS_STATE>(w);
+    uint64_t root_idx[kPdbMaxPatterns] = {};
+    for (int p = 0; p < set.np; p++)
+        root_idx[p] = set.kind[p] == DCA_CUBE3_CORNERS ? c3_index<DCA_CUBE3_CORNERS>(s0.corner, set.pat[p], set.k[p])
+                                                      : c3_index<DCA_CUBE3_EDGES>(s0.edge, set.pat[p], set.k[p]);
+    uint8_t v[kPdbMaxPatterns] = {};
+    if (int rc = ida_root_bytes(on_device, set.np, set.table, root_idx, st, v)) return rc;
+    uint32_t h_root = 0;
+    bool dead = false;
+    for (int p = 0; p < set.np; p++) {
+        dead = dead || v[p] >= kPdbInf;
+        h_root = h_root > v[p] ? h_root : v[p];
+    }
+    C3IdaMoves mt{};
+    for (int kind = 0; kind < 2; kind++)
+        for (int a = 0; a < 12; a++)
+            for (int l = 0; l < kC3Locs; l++)
+                mt.w[((kind * 12 + a) * kC3Locs + l) >> 2] |= (uint32_t)kC3.move[kind][a][l] << (8 * (l & 3));
+    IdaCtrl* dev = nullptr;
+    int device = -1;
+    if (on_device && !dead && !C3Domain::goal(s0))
+        if (int rc = ida_block_take(dev, device)) return rc;
+    const int rc = ida_drive<C3Domain>(h_root, dead, C3Domain::goal(s0), max_nodes, out,
+                                       [&](uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, IdaCtrl& ctrl) {
+        if (on_device)
+            return ida_device_iteration(dev, ctrl, st, "ida_cube3_kernel", [&] {
+                hipLaunchKernelGGL(ida_cube3_kernel, dim3(ida_blocks(n_items)), dim3(kIdaThreads), 0, st, s0, set, mt, dev, T, P, n_items, budget,
+                                   ida_poll(budget, ida_blocks(n_items) * kIdaThreads));
+            });
+        C3Domain::Ctx c;
+        c.mv = (const uint8_t*)mt.w;  // little-endian words: byte l of a row is location l
+        c.set = &set;
+        uint32_t stk[C3Domain::STACK_WORDS] = {};
+        ida_lane<C3Domain>(c, s0, &ctrl, stk, 1u, T, P, n_items, budget, ida_poll(budget, 1));
+        return 0;
+    });
+    ida_block_give(dev, device, rc == 0);
+    return rc;
+}
+
+// every refusal of a puzzle search, then the search: before any HIP call
+static int ida_npuzzle_entry(const char* who, int dim, const uint8_t* root, int num_patterns, const uint8_t* tiles, const int* ks,
+                             const uint8_t* const* tables, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
+    if (dim < 3 || dim > 7) {
+        set_error("bad argument: %s: dim: unsupported puzzle dim %d (3..5)", who, dim);
+        return DCA_E_BADARG;
+    }
+    if (dim > 5) {
+        set_error("bad argument: %s: dim: IDA* is built for dim 3..5; an optimal solution of a %d x %d board is out of reach", who, dim, dim);
+        return DCA_E_BADARG;
+    }
+    if (root == nullptr || tiles == nullptr || ks == nullptr || tables == nullptr) {
+        set_error("bad argument: %s: root, tiles, ks and tables must not be NULL", who);
+        return DCA_E_BADARG;
+    }
+    if (num_patterns < 1 || num_patterns > kIdaPuzzlePatterns) {
+        set_error("bad argument: %s: num_patterns = %d is not in 1..%d (a lane keeps one running index per pattern)", who, num_patterns,
+                  kIdaPuzzlePatterns);
+        return DCA_E_BADARG;
+    }
+    if (int rc = ida_check_out(who, max_nodes, out)) return rc;
+    const int N = dim * dim;
+    PdbSet set{};
+    uint64_t seen = 0;
+    if (int rc = pdb_fill_set(
+            who, set, num_patterns, tiles, ks, tables, [&](int p) { return pdb_bytes_checked(who, dim, ks[p]); },
+            [&](int p, const uint8_t* t) {
+                if (ks[p] > kPdbMaxK) {
+                    set_error("bad argument: %s: ks: pattern %d has %d tiles, over %d", who, p, ks[p], kPdbMaxK);
+                    return DCA_E_BADARG;
+                }
+                return pdb_check_tiles(who, N, t, ks[p], seen);
+            }))
+        return rc;
+    if (int rc = ida_check_puzzle_root(who, dim, root)) return rc;
+    switch (dim) {
+        case 3: return ida_puzzle<3>(root, set, max_nodes, out, on_device, st);
+        case 4: return ida_puzzle<4>(root, set, max_nodes, out, on_device, st);
+        default: return ida_puzzle<5>(root, set, max_nodes, out, on_device, st);
+    }
+}
+
+static int ida_cube3_entry(const char* who, const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
+                           const uint8_t* const* tables, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
+    if (root == nullptr || kinds == nullptr || cubies == nullptr || ks == nullptr || tables == nullptr) {
+        set_error("bad argument: %s: root, kinds, cubies, ks and tables must not be NULL", who);
+        return DCA_E_BADARG;
+    }
+    if (num_patterns < 1 || num_patterns > kPdbMaxPatterns) {
+        set_error("bad argument: %s: num_patterns = %d is not in 1..%d", who, num_patterns, kPdbMaxPatterns);
+        return DCA_E_BADARG;
+    }
+    if (int rc = ida_check_out(who, max_nodes, out)) return rc;
+    C3Set set{};
+    if (int rc = pdb_fill_set(
+            who, set, num_patterns, cubies, ks, tables, [&](int p) { return c3_bytes_checked(who, kinds[p], ks[p]); },
+            [&](int p, const uint8_t* c) { return c3_check_cubies(who, kinds[p], c, ks[p]); }))
+        return rc;
+    for (int p = 0; p < num_patterns; p++) {
+        set.kind[p] = (uint8_t)kinds[p];
+        set.kinds_used |= 1 << kinds[p];
+    }
+    if (int rc = ida_check_cube3_root(who, root)) return rc;
+    return ida_cube3(root, set, max_nodes, out, on_device, st);
+}
+
+}  // namespace dca
+
+using namespace dca;
+
+extern "C" {
+
+int dca_idastar_npuzzle(int dim, const uint8_t* root, int num_patterns, const uint8_t* tiles, const int* ks, const uint8_t* const* tables,
+                        int64_t max_nodes, int* status, int* length, uint8_t* moves, int moves_cap, int* num_thresholds, int* thresholds,
+                        int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes, void* stream) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    return ida_npuzzle_entry(__func__, dim, root, num_patterns, tiles, ks, tables, max_nodes, out, true, (hipStream_t)stream);
+}
+
+int dca_idastar_cube3(const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
+                      const uint8_t* const* tables, int64_t max_nodes, int* status, int* length, uint8_t* moves, int moves_cap,
+                      int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes,
+                      void* stream) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    return ida_cube3_entry(__func__, root, num_patterns, kinds, cubies, ks, tables, max_nodes, out, true, (hipStream_t)stream);
+}
+
+int dca_idastar_host(int env, int dim, const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* ids, const int* ks,
+                     const uint8_t* const* tables, int64_t max_nodes, int* status, int* length, uint8_t* moves, int moves_cap,
+                     int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    if (env == DCA_ENV_NPUZZLE) return ida_npuzzle_entry(__func__, dim, root, num_patterns, ids, ks, tables, max_nodes, out, false, nullptr);
+    if (env == DCA_ENV_CUBE3) return ida_cube3_entry(__func__, root, num_patterns, kinds, ids, ks, tables, max_nodes, out, false, nullptr);
+    set_error("bad argument: %s: env = %d is neither cube3 nor a sliding puzzle", __func__, env);
+    return DCA_E_BADARG;
+}
+
+int dca_idastar_set_prefix(int depth) {
+    if (depth < -1 || depth > PzDomain<3>::MAX_PREFIX) {
+        set_error("bad argument: %s: depth = %d is not in -1..%d", __func__, depth, (int)PzDomain<3>::MAX_PREFIX);
+        return DCA_E_BADARG;
+    }
+    g_ida_forced_prefix = depth;
+    return 0;
+}
+
+}  // extern "C"

@@ -331,6 +331,63 @@ int dca_lightsout_exact_eval(int dim, const uint8_t* states /*[n, ld]*/, int64_t
 int dca_lightsout_exact_solve(int dim, const uint8_t* states /*[n, ld]*/, int64_t n, int64_t ld, uint64_t* presses /*[n]*/,
                               void* stream);
 
+/* IDA* on the pattern databases (csrc/dca_idastar.hip; `python -m deepcubea_amd.search_methods.idastar`): iterative-deepening A*
+ * (Korf 1985 / 1997), the search the tables were invented for.  No OPEN, no CLOSED, no node pool: memory is the caller's tables
+ * plus a packed move stack per lane, so a search runs as long as its node budget lets it.  With an admissible table set the
+ * solution it returns is optimal.  dim 3..5 for the puzzles (6 and 7 are refused: their optimal solutions are out of reach).
+ *   inputs       root: HOST bytes, the N tiles of a board or the 54 sticker ids of a cube.  The pattern set exactly as
+ *                dca_pdb_eval / dca_cube3_pdb_eval take it (host ids, ks, kinds; a HOST array of device table pointers); the
+ *                puzzles take at most 8 patterns (a lane keeps one running index per pattern in registers), cube3 up to 24.
+ *   thresholds   T_0 = h(root); the next T is the smallest f = g + h above T among the children generated.  One launch per
+ *                threshold; the call SYNCHRONISES the stream after each to read the counters back.
+ *   pruning      a child is generated unless its move a, after the previous move m (and m_prev before that), is:
+ *                puzzles — a no-op (the blank at the board's edge), or a == m ^ 1;
+ *                cube3, a = 2 face + dir, faces U D L R B F, f ^ 1 the opposite face — a == m ^ 1; a == m with a odd (a half
+ *                turn is written with the even action only); a == m == m_prev; face(a) == face(m) ^ 1 with face(a) < face(m)
+ *                (opposite faces commute: ascending order only).
+ *   node count   every generated child (one that passes the pruning rules and whose h is evaluated) counts once.  A completed
+ *                iteration's count is the same on every run; the last iteration ends early when a lane reaches the goal, so
+ *                its count varies.  nodes_per_threshold[i] goes with thresholds[i]; *total_nodes is their sum.
+ *   status       DCA_IDASTAR_SOLVED: *length moves, the first min(*length, moves_cap) of them in moves[] (a move is the
+ *                environment's action number); applying them to the root gives the goal — for cube3 every cubie at home, not
+ *                merely h = 0.  DCA_IDASTAR_BUDGET: the count passed max_nodes.  A lane adds its nodes to the launch's counter
+ *                and polls the stop word every `interval` nodes, and a lane without an item counts nothing, so a launch counts at
+ *                most (what was left of max_nodes) + min(items, lanes) * interval, and *total_nodes <= max_nodes + that product
+ *                for the last launch.  `items` and `lanes` are those of "work items" below; interval =
+ *                DCA_IDASTAR_POLL_NODES, or (what was left of max_nodes) / (2 lanes), at least 1, where that is smaller.  Whatever
+ *                the launch: *total_nodes <= max_nodes + DCA_IDASTAR_MAX_LANES * DCA_IDASTAR_POLL_NODES and <= max_nodes +
+ *                max(max_nodes / 2, DCA_IDASTAR_MAX_LANES).  A budget that ends inside the iteration that reaches the goal may still end
+ *                solved, within these bounds.  DCA_IDASTAR_UNSOLVABLE: a table byte at the root is 0xFE or
+ *                0xFF, the threshold passed DCA_IDASTAR_MAX_MOVES, or no child was left above the threshold.  All three return 0.
+ *   work items   an iteration is split into items = NM * RADIX^(P - 1) move prefixes of depth P (one item, P = 0, in the first
+ *                iterations), P the deepest the family finds worth it after a previous iteration of `prev` nodes (0 before the
+ *                first): cube3 — NM = RADIX = 12, P <= 6, 12^P * P <= prev / 2; puzzles — NM = 4, RADIX = 3, P <= 15,
+ *                4 * 3^(P - 1) <= 8 prev.  The launch has lanes = 256 * min(ceil(items / 256), 8 * compute units,
+ *                DCA_IDASTAR_MAX_LANES / 256).  Results and completed iterations' counts do not depend on the split.
+ *   capacities   *num_thresholds = the thresholds run; the first min(that, thresholds_cap) entries of thresholds[] and
+ *                nodes_per_threshold[] are written.  A root that is the goal: solved, length 0, no threshold run.
+ * DCA_E_BADARG before any HIP call, the message naming the argument: dim outside 3..5; a NULL root / ids / ks / kinds / tables /
+ * table / status / length / num_thresholds / total_nodes, or a NULL buffer with a positive capacity; a negative capacity;
+ * max_nodes <= 0; num_patterns outside 1..8 (puzzles) or 1..24 (cube3); what dca_pdb_eval / dca_cube3_pdb_eval refuse in a
+ * pattern set; a puzzle root with a byte >= N, a tile twice, or the wrong parity (the goal cannot be reached from it); a cube3
+ * root that is not the ids 0..53 once each. */
+#define DCA_IDASTAR_SOLVED 0
+#define DCA_IDASTAR_BUDGET 1
+#define DCA_IDASTAR_UNSOLVABLE 2
+#define DCA_IDASTAR_POLL_NODES 512
+#define DCA_IDASTAR_MAX_LANES (1 << 19)
+#define DCA_IDASTAR_MAX_MOVES 254
+int dca_idastar_npuzzle(int dim, const uint8_t* root /*host [N]*/, int num_patterns, const uint8_t* tiles /*host*/,
+                        const int* ks /*host [num_patterns]*/, const uint8_t* const* tables /*host [num_patterns] of device pointers*/,
+                        int64_t max_nodes, int* status, int* length, uint8_t* moves /*host [moves_cap]*/, int moves_cap,
+                        int* num_thresholds, int* thresholds /*host [thresholds_cap]*/,
+                        int64_t* nodes_per_threshold /*host [thresholds_cap]*/, int thresholds_cap, int64_t* total_nodes, void* stream);
+int dca_idastar_cube3(const uint8_t* root /*host [54]*/, int num_patterns, const int* kinds /*host [num_patterns]*/,
+                      const uint8_t* cubies /*host*/, const int* ks /*host [num_patterns]*/,
+                      const uint8_t* const* tables /*host [num_patterns] of device pointers*/, int64_t max_nodes, int* status, int* length,
+                      uint8_t* moves /*host [moves_cap]*/, int moves_cap, int* num_thresholds, int* thresholds /*host [thresholds_cap]*/,
+                      int64_t* nodes_per_threshold /*host [thresholds_cap]*/, int thresholds_cap, int64_t* total_nodes, void* stream);
+
 /* state hash (a9). The reference's hash VALUES are process-randomised SipHash (cube3.py:17-21)
  * or unpinned boost::hash_range (parallel_weighted_astar.cpp:104-111); what is pinned is key
  * equality.  This library defines, for a D-byte state split in little-endian 8-byte words

@@ -54,6 +54,22 @@ int dca_engine_debug(dca_engine* e, double* out /*host [16]*/, void* stream);
  * Any other knob is refused with DCA_E_BADARG (the error text names it) before any HIP call.                             */
 int dca_debug_tune(int knob, int value);
 
+/* ---- IDA* --------------------------------------------------------------------------------------------------------- */
+/* Host-only (no device needed): the search of dca_idastar_npuzzle — env DCA_ENV_NPUZZLE, dim 3..5; kinds ignored, may be NULL —
+ * or of dca_idastar_cube3 — env DCA_ENV_CUBE3; dim ignored — run sequentially on the CPU from tables in HOST memory, through the
+ * same move, index-update, pruning and work-item code the kernel compiles.  Same refusals, same outputs; the completed
+ * iterations' thresholds and node counts equal the device's.  For tests on a machine without a GPU. */
+int dca_idastar_host(int env, int dim, const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* ids, const int* ks,
+                     const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int64_t max_nodes, int* status, int* length,
+                     uint8_t* moves, int moves_cap, int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold,
+                     int thresholds_cap, int64_t* total_nodes);
+/* test hook, process-wide: every iteration of the three searches above splits its work into items of `depth` prefix moves (a
+ * family's own limit where depth is above it: 15 for the puzzles, 6 for cube3); -1 (the default) = chosen from the previous
+ * iteration's node count.  Results never depend on it.  DCA_E_BADARG outside -1..15.
+ * NOT thread-safe: one plain global that the production entry points read at every iteration.  Never call it while a search
+ * runs in another thread, and put -1 back before anything but a test searches. */
+int dca_idastar_set_prefix(int depth);
+
 /* ---- environment kernels ------------------------------------------------------------------------------------------- */
 /* Store-only yardstick of the gather kernel's roofline (bench.py times it in the same process, right after the kernel itself):
  * fills buf[0, bytes) with plain 16-byte stores, one contiguous region of bytes_per_block per workgroup (1 MiB: the pattern

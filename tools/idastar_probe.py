@@ -1,0 +1,175 @@
+"""IDA* on the pattern databases on the MI355X, measured once -> profiles/idastar_probe.txt.
+
+    python tools/idastar_probe.py [--out profiles/idastar_probe.txt] [--legs resources,puzzle15,puzzle24,cube3] [--seconds 150]
+
+One GPU visit.  Every leg runs in a fresh child process under its own `timeout`, one after another, and the visit ends at the
+first leg that does not exit 0 (nothing is started on a device after a leg has failed on it).  Legs:
+  resources  the kernels' registers, LDS, scratch bytes and occupancy, from a compile of csrc/dca_idastar.hip with
+             -Rpass-analysis=kernel-resource-usage (no device needed).  A kernel with scratch fails the leg.
+  puzzle15   all 500 shipped test states with 5-5-5 and with 6-6-3: solved, length == the shipped optimal length, nodes, seconds.
+  puzzle24   the shipped test states in ascending optimal length with 6-6-6-6, until --seconds of search have passed.
+  cube3      the shipped test states in ascending optimal length with korf and with korf7, --seconds of search each.
+A state's node budget is what the rate measured so far gets through in --state_seconds; a state that runs out of it is listed.
+The rate of a family is nodes over seconds summed over its searches of at least 0.05 s (shorter ones time the launches, not the
+kernel).  No threshold is set on any time or rate: the numbers are recorded, not met."""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+LEG_TIMEOUT_S = {"resources": 120, "puzzle15": 500, "puzzle24": 500, "cube3": 700}
+FIRST_BUDGET = 1 << 31  # nodes, until a rate is known
+
+
+def resources_leg():
+    src = os.path.join(ROOT, "deepcubea_amd", "csrc", "dca_idastar.hip")
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only",
+           "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull]
+    text = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, check=True, universal_newlines=True).stdout
+    rows, cur = [], {}
+    for key, value in re.findall(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+)", text):
+        if key == "Function Name":
+            cur = {"name": value}
+            rows.append(cur)
+        elif cur:
+            cur[key.strip()] = value
+    assert rows, "no resource remarks in the compiler's output"
+    print("kernel resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):")
+    for r in rows:
+        name = subprocess.run(["c++filt", r["name"]], stdout=subprocess.PIPE, universal_newlines=True).stdout.strip().split("(")[0]
+        print("  %-38s VGPRs %3s  SGPRs %3s  LDS %6s B/block  scratch %s B/lane  occupancy %s waves/SIMD"
+              % (name, r.get("VGPRs"), r.get("TotalSGPRs"), r.get("LDS Size"), r.get("ScratchSize"), r.get("Occupancy")))
+        assert r.get("ScratchSize") == "0", "a kernel with scratch is not finished"
+
+
+class Rate:
+    def __init__(self):
+        self.nodes, self.seconds = 0, 0.0
+
+    def add(self, nodes, seconds):
+        if seconds >= 0.05:
+            self.nodes += nodes
+            self.seconds += seconds
+
+    @property
+    def value(self):
+        return self.nodes / self.seconds if self.seconds > 0 else None
+
+
+def run_states(search, label, roots, lens, ids, seconds, state_seconds, verbose):
+    """Searches the roots in order until `seconds` of search have passed -> prints a summary, returns the rate."""
+    import torch
+    rate = Rate()
+    spent, ran, optimal, missed, nodes_all, times = 0.0, 0, 0, [], [], []
+    for root, want, i in zip(roots, lens, ids):
+        if spent >= seconds:
+            break
+        budget = int(rate.value * state_seconds) if rate.value else FIRST_BUDGET
+        torch.cuda.synchronize()
+        t0 = time.time()
+        res = search.solve(root, budget)
+        dt = time.time() - t0
+        spent += dt
+        ran += 1
+        rate.add(res["nodes_generated"], dt)
+        nodes_all.append(res["nodes_generated"])
+        times.append(dt)
+        if res["solved"]:
+            assert len(res["moves"]) == want, "state %d: length %d, shipped optimal %d" % (i, len(res["moves"]), want)
+            optimal += 1
+        else:
+            missed.append((i, want, res["status"], res["nodes_generated"], res["thresholds"][-1:]))
+        if verbose:
+            print("    state %4d  optimal %3d  %-16s nodes %14d  %8.3f s  thresholds %s"
+                  % (i, want, res["status"], res["nodes_generated"], dt, res["thresholds"]), flush=True)
+    print("  %-18s ran %d of %d states (optimal length %d .. %d) in %.1f s of search: solved at the shipped optimal length %d / %d"
+          % (label, ran, len(roots), min(lens[:ran]), max(lens[:ran]), spent, optimal, ran))
+    print("  %-18s nodes per state: median %.3g, mean %.3g, max %.3g; seconds per state: median %.4f, mean %.4f, max %.3f"
+          % ("", np.median(nodes_all), np.mean(nodes_all), np.max(nodes_all), np.median(times), np.mean(times), np.max(times)))
+    print("  %-18s rate over the searches of >= 0.05 s: %s nodes/s" % ("", "%.3g" % rate.value if rate.value else "none that long"))
+    for i, want, status, nodes, last in missed:
+        print("  %-18s OUT OF BUDGET: state %d (optimal %d): %s after %d nodes, last threshold %s" % ("", i, want, status, nodes, last))
+    sys.stdout.flush()
+    return rate.value
+
+
+def golden():
+    return np.load(os.path.join(ROOT, "tests", "golden", "golden.npz"))
+
+
+def puzzle_leg(env_name, specs, seconds, state_seconds, verbose, in_order):
+    from deepcubea_amd.search_methods.idastar import IDAStar
+    from deepcubea_amd.utils.pattern_db import PatternDatabase
+    z = golden()
+    states, lens = z["%s_test_states" % env_name], z["%s_test_opt_len" % env_name].astype(int)
+    ids = np.argsort(lens, kind="stable") if in_order else np.arange(len(lens))
+    for spec in specs:
+        t0 = time.time()
+        pdb = PatternDatabase(env_name, spec).build()
+        print("%s pdb:%s: %d bytes built in %.2f s" % (env_name, spec, pdb.bytes, time.time() - t0), flush=True)
+        run_states(IDAStar(env_name, pdb), "%s %s" % (env_name, spec), states[ids], lens[ids], ids, seconds, state_seconds, verbose)
+        del pdb
+
+
+def cube3_leg(seconds, state_seconds, verbose):
+    from deepcubea_amd.search_methods.idastar import IDAStar
+    from deepcubea_amd.utils.cube3_pdb import Cube3PatternDatabase
+    z = golden()
+    states, lens = z["cube3_test_states"], z["cube3_test_opt_len"].astype(int)
+    ids = np.argsort(lens, kind="stable")
+    for spec in ("korf", "korf7"):
+        t0 = time.time()
+        pdb = Cube3PatternDatabase(spec).build()
+        print("cube3 pdb:%s: %d bytes built in %.2f s" % (spec, pdb.bytes, time.time() - t0), flush=True)
+        run_states(IDAStar("cube3", pdb), "cube3 %s" % spec, states[ids], lens[ids], ids, seconds, state_seconds, verbose)
+        del pdb
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "idastar_probe.txt"))
+    ap.add_argument("--legs", default="resources,puzzle15,puzzle24,cube3")
+    ap.add_argument("--seconds", type=float, default=150.0, help="seconds of search per pattern set")
+    ap.add_argument("--state_seconds", type=float, default=40.0, help="a state's node budget, in seconds at the measured rate")
+    ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--leg", default=None, help="(internal) run one leg in this process")
+    args = ap.parse_args()
+    if args.leg:
+        if args.leg == "resources":
+            resources_leg()
+        elif args.leg == "puzzle15":
+            puzzle_leg("puzzle15", ("5-5-5", "6-6-3"), 1e9, args.state_seconds, args.verbose, False)
+        elif args.leg == "puzzle24":
+            puzzle_leg("puzzle24", ("6-6-6-6",), args.seconds, args.state_seconds, args.verbose, True)
+        elif args.leg == "cube3":
+            cube3_leg(args.seconds, args.state_seconds, args.verbose)
+        else:
+            raise ValueError("unknown leg %r" % args.leg)
+        return
+    lines = ["IDA* on the pattern databases (tools/idastar_probe.py), one MI355X; --seconds %g --state_seconds %g" % (args.seconds, args.state_seconds),
+             "For comparison, the batched A* engine on the same tables (DESIGN 4.6): puzzle15 5-5-5 solves 460 of 500 and 6-6-3 492 of 500",
+             "inside its 2^24-id pool; no puzzle24 search with 6-6-6-6; cube3 korf roots up to 13 moves from the goal.", ""]
+    for leg in args.legs.split(","):
+        cmd = ["timeout", "-k", "10", str(LEG_TIMEOUT_S[leg]), sys.executable, os.path.abspath(__file__), "--leg", leg, "--seconds", str(args.seconds),
+               "--state_seconds", str(args.state_seconds)] + (["--verbose"] if args.verbose else [])
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
+        lines += ["---- leg %s (exit %d)" % (leg, p.returncode)] + p.stdout.rstrip().split("\n") + [""]
+        print("\n".join(lines[-(len(p.stdout.rstrip().split("\n")) + 2):]), flush=True)
+        if p.returncode != 0:
+            lines.append("leg %s failed: the visit ends here" % leg)
+            break
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    sys.exit(0 if lines[-1] == "" else 1)
+
+
+if __name__ == "__main__":
+    main()
