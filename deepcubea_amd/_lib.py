@@ -65,6 +65,7 @@ _SIGNATURES = {
     "dca_pdb_bytes": "l ii",
     "dca_pdb_build": "i ipippp",
     "dca_pdb_eval": "i ipllippppp",
+    "dca_pdb_eval_reflected": "i ipllippppp",
     "dca_cube3_pdb_bytes": "l ii",
     "dca_cube3_pdb_cubies": "i ip",
     "dca_cube3_pdb_index": "i ipipip",
@@ -74,6 +75,7 @@ _SIGNATURES = {
     "dca_lightsout_exact_eval": "i ipllpp",
     "dca_lightsout_exact_solve": "i ipllpp",
     "dca_idastar_npuzzle": "i ipippplpppipppipp",
+    "dca_idastar_npuzzle_reflected": "i ipippplpppipppipp",
     "dca_idastar_cube3": "i pipppplpppipppipp",
     "dca_engine_create": "i piidilii",
     "dca_engine_create_multi": "i piidiliii",
@@ -149,6 +151,8 @@ _SIGNATURES = {
     "dca_engine_debug": "i ppp",
     "dca_debug_tune": "i ii",
     "dca_idastar_host": "i iipipppplpppipppip",
+    "dca_idastar_host_reflected": "i ipippplpppipppip",
+    "dca_pdb_eval_host": "i ipllipppip",
     "dca_idastar_set_prefix": "i i",
     "dca_debug_write_ceiling": "i pllp",
     "dca_f16x3_gemm_variant": "i i",
@@ -548,11 +552,28 @@ def pdb_build(dim: int, tiles, table: Optional[torch.Tensor] = None):
     return _pdb_build("dca_pdb_build", pdb_bytes, dim, tiles, table)
 
 
-def pdb_eval(dim: int, states: torch.Tensor, partition, tables, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def pdb_eval(dim: int, states: torch.Tensor, partition, tables, out: Optional[torch.Tensor] = None, reflect: bool = False) -> torch.Tensor:
     """Sum of the patterns' table bytes per row -> f32 [n].  states: uint8 device rows [n, >= dim * dim] with unit byte stride
-    (a strided view is fine); ANY bytes are in bounds (include/dca.h, the any-bytes rule)."""
-    return _pdb_eval("pdb_eval", "dca_pdb_eval", states, dim * dim, partition, (dim,) * len(partition), _pdb_table_bytes, tables, out,
-                     lambda s, n, ld, m, dims, *rest: lib().dca_pdb_eval(dim, s, n, ld, m, *rest))
+    (a strided view is fine); ANY bytes are in bounds (include/dca.h, the any-bytes rule).  reflect: the larger of that sum and
+    the sum at the row's mirror image (include/dca.h, "Reflected look-up")."""
+    symbol = "dca_pdb_eval_reflected" if reflect else "dca_pdb_eval"
+    return _pdb_eval("pdb_eval", symbol, states, dim * dim, partition, (dim,) * len(partition), _pdb_table_bytes, tables, out,
+                     lambda s, n, ld, m, dims, *rest: getattr(lib(), symbol)(dim, s, n, ld, m, *rest))
+
+
+def pdb_eval_host(dim: int, rows, partition, tables, reflect: bool = False) -> np.ndarray:
+    """pdb_eval on the CPU (include/dca_debug.h: the kernels' own row value in a plain loop) -> float32 [n].  rows: a uint8 host
+    array [n, >= dim * dim]; tables: one uint8 host array per pattern.  No device needed."""
+    rows = np.asarray(rows)
+    if rows.dtype != np.uint8 or rows.ndim != 2:
+        raise ValueError("pdb_eval_host: rows must be a uint8 host array [n, >= %d]" % (dim * dim))
+    rows = np.ascontiguousarray(rows)
+    _table_sizes("pdb_eval_host", [_pdb_table_bytes(dim, len(g)) for g in partition], tables, True)
+    (_, ids, ks), ptrs, _keep = _idastar_set(partition, (dim,) * len(partition), tables, True)
+    out = np.zeros(len(rows), np.float32)
+    check(lib().dca_pdb_eval_host(dim, rows.ctypes.data_as(C.c_void_p), len(rows), rows.shape[1], len(partition), ids, ks, ptrs,
+                                  int(bool(reflect)), out.ctypes.data_as(C.c_void_p)), "dca_pdb_eval_host")
+    return out
 
 
 # ------------------------------------------------------------------------------ pattern databases (cube3)
@@ -649,6 +670,7 @@ IDASTAR_POLL_NODES, IDASTAR_MAX_LANES, IDASTAR_MAX_MOVES = 512, 1 << 19, 254  # 
 IDASTAR_OVERSHOOT = IDASTAR_MAX_LANES * IDASTAR_POLL_NODES  # total_nodes <= max_nodes + this, whatever the launch
 IDASTAR_MAX_PREFIX = {ENV_NPUZZLE: 15, ENV_CUBE3: 6}  # moves a work item's prefix has at the most
 IDASTAR_MAX_PUZZLE_PATTERNS = 8
+IDASTAR_MAX_REFLECT_PATTERNS = 4  # a running index and a reflected one per pattern share the 8 a lane keeps
 
 
 def _idastar(symbol: str, call, root, width: int, max_nodes: int) -> dict:
@@ -707,13 +729,14 @@ def _table_sizes(who: str, sizes, tables, host: bool) -> None:
             raise ValueError("%s: a table of %d elements for a pattern that needs %d bytes" % (who, n, size))
 
 
-def idastar_npuzzle(dim: int, root, partition, tables, max_nodes: int) -> dict:
+def idastar_npuzzle(dim: int, root, partition, tables, max_nodes: int, reflect: bool = False) -> dict:
     """Optimal solution of one sliding-puzzle root by IDA* on the device tables of `partition` (include/dca.h "IDA*") -> dict.
-    Synchronises once per threshold."""
+    Synchronises once per threshold.  reflect: h is the reflected value; at most IDASTAR_MAX_REFLECT_PATTERNS patterns."""
     _table_sizes("idastar_npuzzle", [_pdb_table_bytes(dim, len(g)) for g in partition], tables, False)
     (_, ids, ks), ptrs, _keep = _idastar_set(partition, (dim,) * len(partition), tables, False)
-    return _idastar("dca_idastar_npuzzle", lambda r, n, *out: lib().dca_idastar_npuzzle(dim, r, len(partition), ids, ks, ptrs, n, *out,
-                                                                                        stream_ptr()), root, max(dim, 0) ** 2, max_nodes)
+    symbol = "dca_idastar_npuzzle_reflected" if reflect else "dca_idastar_npuzzle"
+    return _idastar(symbol, lambda r, n, *out: getattr(lib(), symbol)(dim, r, len(partition), ids, ks, ptrs, n, *out, stream_ptr()),
+                    root, max(dim, 0) ** 2, max_nodes)
 
 
 def idastar_cube3(root, patterns, tables, max_nodes: int) -> dict:
@@ -724,9 +747,12 @@ def idastar_cube3(root, patterns, tables, max_nodes: int) -> dict:
                                                                                     stream_ptr()), root, 54, max_nodes)
 
 
-def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int) -> dict:
+def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int, reflect: bool = False) -> dict:
     """The same search run sequentially on the CPU from HOST tables (include/dca_debug.h): no device needed.  patterns: the
-    partition (puzzles) or [(kind, cubies), ...] (cube3); tables: one uint8 array per pattern."""
+    partition (puzzles) or [(kind, cubies), ...] (cube3); tables: one uint8 array per pattern.  reflect: the reflected search,
+    sliding puzzles only."""
+    if reflect and env != ENV_NPUZZLE:
+        raise ValueError("idastar_host: the reflected look-up is defined for the sliding puzzles only")
     if env == ENV_CUBE3:
         groups, families = [g for _, g in patterns], [kind for kind, _ in patterns]
         sizes, width = [_cube3_table_bytes(kind, len(g)) for kind, g in patterns], 54
@@ -735,6 +761,9 @@ def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int) -> 
         sizes, width = [_pdb_table_bytes(dim, len(g)) for g in patterns], max(dim, 0) ** 2
     _table_sizes("idastar_host", sizes, tables, True)
     (kinds, ids, ks), ptrs, _keep = _idastar_set(groups, families, tables, True)
+    if reflect:
+        return _idastar("dca_idastar_host_reflected", lambda r, n, *out: lib().dca_idastar_host_reflected(dim, r, len(groups), ids, ks, ptrs,
+                                                                                                          n, *out), root, width, max_nodes)
     return _idastar("dca_idastar_host", lambda r, n, *out: lib().dca_idastar_host(env, dim, r, len(groups), kinds, ids, ks, ptrs, n, *out),
                     root, width, max_nodes)
 

@@ -8,6 +8,8 @@
 //            puzzles' board packed 4 or 5 bits a position with the blank and one running table index per pattern, cube3's two
 //            words of cubie locations.  The same function, compiled for the host, is the sequential search of
 //            dca_idastar_host (include/dca_debug.h).
+//   reflect  PzDomain<DIM, true>: the puzzles' search on the reflected look-up (include/dca.h) — a second running index per
+//            pattern, that of the state's mirror image, in the other half of the lane's eight, and h the larger of the two sums.
 //   work     item i of an iteration names a move prefix of P moves, the mixed-radix digits of i (first move = most significant
 //            digit; cube3: radix 12; puzzles: 4 for the first move, then 3 — a digit picks among the moves that do not undo
 //            the one before).  A lane replays the prefix from the root under the pruning rules and the f <= T test and drops the item
@@ -21,7 +23,7 @@
 //            passes the budget and polls the stop word there.  Whoever stops the launch also sets the item counter's top bit,
 //            which ends every other lane's item fetch.
 //
-// Rates are in profiles/idastar_probe.txt.
+// Rates are in profiles/idastar_probe.txt; the reflected search against the plain one in profiles/idastar_reflect_probe.txt.
 #include <mutex>
 #include <type_traits>
 
@@ -60,8 +62,14 @@ struct PzMaps {  // tile -> (its weight N^(digit) in its pattern's index, its pa
     uint64_t w[32];
     uint32_t p[32];
 };
+struct PzMapsReflect : PzMaps {  // and tile t -> the same of phi(t), the pattern as its slot np + p(phi(t)) of State::idx
+    uint64_t rw[32];
+    uint32_t rp[32];
+};
 
-template <int DIM>
+// REFLECT: the reflected look-up (include/dca.h): slots np .. 2 np - 1 of State::idx are the running indices of the state's
+// mirror image in the main diagonal, and h is the larger of the two sums.  Without it nothing below differs from the plain search.
+template <int DIM, bool REFLECT = false>
 struct PzDomain {
     static constexpr int N = DIM * DIM, NM = 4, RADIX = 3, MOVE_BITS = 2, MAX_PREFIX = 15, STACK_WORDS = 16;
     static constexpr int BITS = N <= 16 ? 4 : 5;
@@ -76,6 +84,8 @@ struct PzDomain {
         const uint32_t* tile_p;
         const uint8_t* table[kIdaPuzzlePatterns];
         int np;
+        const uint64_t* rtile_w;  // REFLECT only
+        const uint32_t* rtile_p;
     };
     static constexpr Board MASK = (1u << BITS) - 1u;
     static constexpr Board goal_board() {
@@ -105,11 +115,39 @@ struct PzDomain {
         const uint64_t w = c.tile_w[t];  // t < 2^BITS <= 32
         const uint32_t p = c.tile_p[t];
         const uint64_t delta = w * (uint64_t)s.blank - w * (uint64_t)nb;  // modulo 2^64: the sum is the exact index
+        if constexpr (REFLECT) {
+            // in the mirror image tile phi(t) goes refl(nb) -> refl(blank); p < np <= rp, so a slot takes one of the two deltas
+            const uint64_t rw = c.rtile_w[t];
+            const uint32_t rp = c.rtile_p[t];
+            const uint64_t rdelta = rw * (uint64_t)pdb_refl<DIM>(s.blank) - rw * (uint64_t)pdb_refl<DIM>(nb);
+#pragma unroll
+            for (int q = 0; q < kIdaPuzzlePatterns; q++)
+                r.idx[q] = s.idx[q] + (p == (uint32_t)q ? delta : 0ull) + (rp == (uint32_t)q ? rdelta : 0ull);
+            return r;
+        }
 #pragma unroll
         for (int q = 0; q < kIdaPuzzlePatterns; q++) r.idx[q] = s.idx[q] + (p == (uint32_t)q ? delta : 0ull);
         return r;
     }
     static DCA_IDA_INLINE uint32_t h(const State& s, const Ctx& c) {
+        if constexpr (REFLECT) {
+            // slot np + q reads table q again (c.table[np + q] = c.table[q]): every slot is a constant register, and the 2 np
+            // gathers are independent, all in flight before the first is summed
+            const uint32_t rblank = pdb_refl<DIM>(s.blank);
+            uint32_t v[kIdaPuzzlePatterns];
+#pragma unroll
+            for (int q = 0; q < kIdaPuzzlePatterns; q++) {
+                v[q] = 0;
+                if (q < 2 * c.np) v[q] = c.table[q][s.idx[q] + (q < c.np ? s.blank : rblank)];
+            }
+            uint32_t sum = 0, rsum = 0;
+#pragma unroll
+            for (int q = 0; q < kIdaPuzzlePatterns; q++) {
+                sum += q < c.np ? v[q] : 0u;
+                rsum += q < c.np ? 0u : v[q];
+            }
+            return sum > rsum ? sum : rsum;
+        }
         uint32_t sum = 0;
 #pragma unroll
         for (int q = 0; q < kIdaPuzzlePatterns; q++)
@@ -274,17 +312,20 @@ DCA_IDA_INLINE void ida_lane(const typename D::Ctx& c, const typename D::State& 
 }
 
 // -------------------------------------------------------------------------------------------------------------- kernels
-template <int DIM>
+template <int DIM, bool REFLECT = false>
 struct PzArgs {
-    typename PzDomain<DIM>::State root;
+    typename PzDomain<DIM, REFLECT>::State root;
     const uint8_t* table[kIdaPuzzlePatterns];
     int np;
 };
 
-template <int DIM>
-__global__ __launch_bounds__(kIdaThreads) void ida_puzzle_kernel(PzArgs<DIM> args, PzMaps maps, IdaCtrl* ctrl, uint32_t T, uint32_t P,
-                                                                 uint32_t n_items, unsigned long long budget, uint32_t poll) {
-    using D = PzDomain<DIM>;
+template <bool REFLECT>
+using PzMapsOf = std::conditional_t<REFLECT, PzMapsReflect, PzMaps>;
+
+template <int DIM, bool REFLECT = false>
+__global__ __launch_bounds__(kIdaThreads) void ida_puzzle_kernel(PzArgs<DIM, REFLECT> args, PzMapsOf<REFLECT> maps, IdaCtrl* ctrl, uint32_t T,
+                                                                 uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
+    using D = PzDomain<DIM, REFLECT>;
     __shared__ uint64_t tile_w[32];
     __shared__ uint32_t tile_p[32];
     __shared__ uint32_t stk[D::STACK_WORDS * kIdaThreads];
@@ -295,8 +336,21 @@ __global__ __launch_bounds__(kIdaThreads) void ida_puzzle_kernel(PzArgs<DIM> arg
             tile_p[t] = maps.p[t];
         }
     }
-    __syncthreads();
     typename D::Ctx c;
+    if constexpr (REFLECT) {  // the second pair of tile maps, staged like the first
+        __shared__ uint64_t rtile_w[32];
+        __shared__ uint32_t rtile_p[32];
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int t = 0; t < 32; t++) {
+                rtile_w[t] = maps.rw[t];
+                rtile_p[t] = maps.rp[t];
+            }
+        }
+        c.rtile_w = rtile_w;
+        c.rtile_p = rtile_p;
+    }
+    __syncthreads();
     c.tile_w = tile_w;
     c.tile_p = tile_p;
 #pragma unroll
@@ -540,13 +594,15 @@ static int ida_device_iteration(IdaCtrl* dev, IdaCtrl& ctrl, hipStream_t st, con
     return 0;
 }
 
-template <int DIM>
+template <int DIM, bool REFLECT>
 static int ida_puzzle(const uint8_t* root, const PdbSet& set, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
-    using D = PzDomain<DIM>;
+    using D = PzDomain<DIM, REFLECT>;
     constexpr int N = D::N;
-    PzMaps maps{};
+    PzMapsOf<REFLECT> maps{};
     for (int t = 0; t < 32; t++) maps.p[t] = 0xFFu;
-    PzArgs<DIM> args{};
+    if constexpr (REFLECT)
+        for (int t = 0; t < 32; t++) maps.rp[t] = 0xFFu;
+    PzArgs<DIM, REFLECT> args{};
     args.np = set.np;
     int pos[N];
     for (int i = 0; i < N; i++) {
@@ -562,18 +618,30 @@ static int ida_puzzle(const uint8_t* root, const PdbSet& set, int64_t max_nodes,
             maps.w[t] = w;
             maps.p[t] = (uint32_t)p;
             args.root.idx[p] += w * (uint64_t)pos[t];
+            if constexpr (REFLECT) {  // slot np + p: tile t's digit in the mirror image is refl(pos(phi(t))); phi(t) moves it
+                const int u = (int)pdb_phi<DIM>((uint32_t)t);
+                maps.rw[u] = w;
+                maps.rp[u] = (uint32_t)(set.np + p);
+                args.root.idx[set.np + p] += w * (uint64_t)pdb_refl<DIM>((uint32_t)pos[u]);
+            }
         }
         args.table[p] = set.table[p];
         root_idx[p] = args.root.idx[p] + args.root.blank;
+        if constexpr (REFLECT) {
+            args.table[set.np + p] = set.table[p];
+            root_idx[set.np + p] = args.root.idx[set.np + p] + pdb_refl<DIM>(args.root.blank);
+        }
     }
+    const int slots = REFLECT ? 2 * set.np : set.np;
     uint8_t v[kIdaPuzzlePatterns] = {};
-    if (int rc = ida_root_bytes(on_device, set.np, set.table, root_idx, st, v)) return rc;
-    uint32_t h_root = 0;
+    if (int rc = ida_root_bytes(on_device, slots, args.table, root_idx, st, v)) return rc;
+    uint32_t h_root = 0, h_mirror = 0;
     bool dead = false;
-    for (int p = 0; p < set.np; p++) {
+    for (int p = 0; p < slots; p++) {
         dead = dead || v[p] >= kPdbInf;
-        h_root += v[p];
+        (p < set.np ? h_root : h_mirror) += v[p];
     }
+    h_root = h_root > h_mirror ? h_root : h_mirror;
     IdaCtrl* dev = nullptr;
     int device = -1;
     if (on_device && !dead && !D::goal(args.root))
@@ -582,12 +650,16 @@ static int ida_puzzle(const uint8_t* root, const PdbSet& set, int64_t max_nodes,
                                 [&](uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, IdaCtrl& ctrl) {
         if (on_device)
             return ida_device_iteration(dev, ctrl, st, "ida_puzzle_kernel", [&] {
-                hipLaunchKernelGGL(ida_puzzle_kernel<DIM>, dim3(ida_blocks(n_items)), dim3(kIdaThreads), 0, st, args, maps, dev, T, P, n_items, budget,
+                hipLaunchKernelGGL((ida_puzzle_kernel<DIM, REFLECT>), dim3(ida_blocks(n_items)), dim3(kIdaThreads), 0, st, args, maps, dev, T, P, n_items, budget,
                                    ida_poll(budget, ida_blocks(n_items) * kIdaThreads));
             });
         typename D::Ctx c;
         c.tile_w = maps.w;
         c.tile_p = maps.p;
+        if constexpr (REFLECT) {
+            c.rtile_w = maps.rw;
+            c.rtile_p = maps.rp;
+        }
         for (int q = 0; q < kIdaPuzzlePatterns; q++) c.table[q] = args.table[q];
         c.np = args.np;
         uint32_t stk[D::STACK_WORDS] = {};
@@ -645,7 +717,8 @@ static int ida_cube3(const uint8_t* root, const C3Set& set, int64_t max_nodes, c
 
 // every refusal of a puzzle search, then the search: before any HIP call
 static int ida_npuzzle_entry(const char* who, int dim, const uint8_t* root, int num_patterns, const uint8_t* tiles, const int* ks,
-                             const uint8_t* const* tables, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
+                             const uint8_t* const* tables, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st,
+                             bool reflect = false) {
     if (dim < 3 || dim > 7) {
         set_error("bad argument: %s: dim: unsupported puzzle dim %d (3..5)", who, dim);
         return DCA_E_BADARG;
@@ -663,6 +736,11 @@ static int ida_npuzzle_entry(const char* who, int dim, const uint8_t* root, int 
                   kIdaPuzzlePatterns);
         return DCA_E_BADARG;
     }
+    if (reflect && num_patterns > kIdaPuzzlePatterns / 2) {
+        set_error("bad argument: %s: num_patterns = %d is not in 1..%d (a lane keeps a running index and a reflected one per pattern, %d in all)",
+                  who, num_patterns, kIdaPuzzlePatterns / 2, kIdaPuzzlePatterns);
+        return DCA_E_BADARG;
+    }
     if (int rc = ida_check_out(who, max_nodes, out)) return rc;
     const int N = dim * dim;
     PdbSet set{};
@@ -678,10 +756,16 @@ static int ida_npuzzle_entry(const char* who, int dim, const uint8_t* root, int 
             }))
         return rc;
     if (int rc = ida_check_puzzle_root(who, dim, root)) return rc;
+    if (reflect)
+        switch (dim) {
+            case 3: return ida_puzzle<3, true>(root, set, max_nodes, out, on_device, st);
+            case 4: return ida_puzzle<4, true>(root, set, max_nodes, out, on_device, st);
+            default: return ida_puzzle<5, true>(root, set, max_nodes, out, on_device, st);
+        }
     switch (dim) {
-        case 3: return ida_puzzle<3>(root, set, max_nodes, out, on_device, st);
-        case 4: return ida_puzzle<4>(root, set, max_nodes, out, on_device, st);
-        default: return ida_puzzle<5>(root, set, max_nodes, out, on_device, st);
+        case 3: return ida_puzzle<3, false>(root, set, max_nodes, out, on_device, st);
+        case 4: return ida_puzzle<4, false>(root, set, max_nodes, out, on_device, st);
+        default: return ida_puzzle<5, false>(root, set, max_nodes, out, on_device, st);
     }
 }
 
@@ -722,6 +806,14 @@ int dca_idastar_npuzzle(int dim, const uint8_t* root, int num_patterns, const ui
     return ida_npuzzle_entry(__func__, dim, root, num_patterns, tiles, ks, tables, max_nodes, out, true, (hipStream_t)stream);
 }
 
+int dca_idastar_npuzzle_reflected(int dim, const uint8_t* root, int num_patterns, const uint8_t* tiles, const int* ks,
+                                  const uint8_t* const* tables, int64_t max_nodes, int* status, int* length, uint8_t* moves, int moves_cap,
+                                  int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap,
+                                  int64_t* total_nodes, void* stream) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    return ida_npuzzle_entry(__func__, dim, root, num_patterns, tiles, ks, tables, max_nodes, out, true, (hipStream_t)stream, true);
+}
+
 int dca_idastar_cube3(const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
                       const uint8_t* const* tables, int64_t max_nodes, int* status, int* length, uint8_t* moves, int moves_cap,
                       int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes,
@@ -738,6 +830,13 @@ int dca_idastar_host(int env, int dim, const uint8_t* root, int num_patterns, co
     if (env == DCA_ENV_CUBE3) return ida_cube3_entry(__func__, root, num_patterns, kinds, ids, ks, tables, max_nodes, out, false, nullptr);
     set_error("bad argument: %s: env = %d is neither cube3 nor a sliding puzzle", __func__, env);
     return DCA_E_BADARG;
+}
+
+int dca_idastar_host_reflected(int dim, const uint8_t* root, int num_patterns, const uint8_t* tiles, const int* ks,
+                               const uint8_t* const* tables, int64_t max_nodes, int* status, int* length, uint8_t* moves, int moves_cap,
+                               int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    return ida_npuzzle_entry(__func__, dim, root, num_patterns, tiles, ks, tables, max_nodes, out, false, nullptr, true);
 }
 
 int dca_idastar_set_prefix(int depth) {

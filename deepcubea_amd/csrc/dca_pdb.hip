@@ -13,8 +13,10 @@
 //           row[p] == t (0 if none; bytes >= N match no tile) by a compare sweep over the N positions — no array indexed by a
 //           row byte, so nothing a row holds can form an address: every digit is < N and every index < N^(k+1) for ANY bytes.
 //           One byte gather per pattern (up to four in flight), summed, written as fp32.
+//           The reflected family (PdbEvalReflect, dca_pdb_eval_reflected) reads the same tables at the row and at its mirror
+//           image in the main diagonal and writes the larger sum; it derives every tile's position once, in one pass over the row.
 //
-// What bounds either kernel has not been measured (profiles/pdb_probe.txt holds only wall-clock rates).
+// What bounds either kernel has not been measured (profiles/pdb_probe.txt and profiles/pdb_reflect_probe.txt hold only wall-clock rates).
 #include "dca_pdb_puzzle.h"
 
 namespace dca {
@@ -123,6 +125,68 @@ static int pdb_build_launch(uint8_t* table, uint64_t total, int k, const PdbPatt
     return rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- eval
+// the eval frame's loop on the CPU: the kernels' own row load and row_value, one row after another (dca_pdb_eval_host)
+template <typename F>
+static void pdb_eval_rows_host(const uint8_t* states, int64_t n, int64_t ld, const PdbSet& set, float* out) {
+    for (int64_t i = 0; i < n; i++) {
+        uint32_t w[(F::N + 3) / 4];
+        pdb_load_row<F::N, 1>(states + i * ld, w);
+        out[i] = (float)F::row_value(w, set);
+    }
+}
+
+template <int DIM>
+static int pdb_eval_run(const uint8_t* states, int64_t n, int64_t ld, const PdbSet& set, float* out, bool reflect, bool host, hipStream_t st) {
+    if (host) {
+        if (reflect)
+            pdb_eval_rows_host<PdbEvalReflect<DIM>>(states, n, ld, set, out);
+        else
+            pdb_eval_rows_host<PdbEval<DIM>>(states, n, ld, set, out);
+        return 0;
+    }
+    return reflect ? pdb_eval_launch<PdbEvalReflect<DIM>>(states, n, ld, set, out, st) : pdb_eval_launch<PdbEval<DIM>>(states, n, ld, set, out, st);
+}
+
+#define DCA_PDB_ARG(cond)                                      \
+    do {                                                       \
+        if (!(cond)) {                                         \
+            set_error("bad argument: %s: %s", who, #cond);     \
+            return DCA_E_BADARG;                               \
+        }                                                      \
+    } while (0)
+
+// what the three eval entry points share: every refusal, before any HIP call, then the family's kernels or the host loop
+static int pdb_eval_entry(const char* who, int dim, const uint8_t* states, int64_t n, int64_t ld, int num_patterns, const uint8_t* tiles,
+                          const int* ks, const uint8_t* const* tables, float* out, bool reflect, bool host, hipStream_t st) {
+    if (dim < 3 || dim > 7) {
+        set_error("bad argument: %s: dim: unsupported puzzle dim %d (3..7)", who, dim);
+        return DCA_E_BADARG;
+    }
+    const int N = dim * dim;
+    DCA_PDB_ARG(n >= 0 && n < ((int64_t)1 << 31));
+    DCA_PDB_ARG(ld >= N);
+    DCA_PDB_ARG(num_patterns >= 1 && num_patterns <= 24);
+    DCA_PDB_ARG(tiles != nullptr && ks != nullptr && tables != nullptr);
+    PdbSet set{};
+    uint64_t seen = 0;  // across the whole set: the patterns are disjoint
+    if (int rc = pdb_fill_set(
+            who, set, num_patterns, tiles, ks, tables, [&](int p) { return pdb_bytes_checked(who, dim, ks[p]); },
+            [&](int p, const uint8_t* t) { return pdb_check_tiles(who, N, t, ks[p], seen); }))
+        return rc;
+    if (n == 0) return 0;
+    DCA_PDB_ARG(states != nullptr && out != nullptr);
+    DCA_PDB_ARG(((uintptr_t)out & 3) == 0);
+    switch (dim) {
+        case 3: return pdb_eval_run<3>(states, n, ld, set, out, reflect, host, st);
+        case 4: return pdb_eval_run<4>(states, n, ld, set, out, reflect, host, st);
+        case 5: return pdb_eval_run<5>(states, n, ld, set, out, reflect, host, st);
+        case 6: return pdb_eval_run<6>(states, n, ld, set, out, reflect, host, st);
+        default: return pdb_eval_run<7>(states, n, ld, set, out, reflect, host, st);
+    }
+}
+#undef DCA_PDB_ARG
+
 }  // namespace dca
 
 using namespace dca;
@@ -152,33 +216,17 @@ int dca_pdb_build(int dim, const uint8_t* tiles, int k, uint8_t* table, int* swe
 
 int dca_pdb_eval(int dim, const uint8_t* states, int64_t n, int64_t ld, int num_patterns, const uint8_t* tiles, const int* ks,
                  const uint8_t* const* tables, float* out, void* stream) {
-    if (dim < 3 || dim > 7) {
-        set_error("bad argument: %s: dim: unsupported puzzle dim %d (3..7)", __func__, dim);
-        return DCA_E_BADARG;
-    }
-    const int N = dim * dim;
-    DCA_ARG(n >= 0 && n < ((int64_t)1 << 31));
-    DCA_ARG(ld >= N);
-    DCA_ARG(num_patterns >= 1 && num_patterns <= 24);
-    DCA_ARG(tiles != nullptr && ks != nullptr && tables != nullptr);
-    PdbSet set{};
-    uint64_t seen = 0;  // across the whole set: the patterns are disjoint
-    const char* who = __func__;
-    if (int rc = pdb_fill_set(
-            who, set, num_patterns, tiles, ks, tables, [&](int p) { return pdb_bytes_checked(who, dim, ks[p]); },
-            [&](int p, const uint8_t* t) { return pdb_check_tiles(who, N, t, ks[p], seen); }))
-        return rc;
-    if (n == 0) return 0;
-    DCA_ARG(states != nullptr && out != nullptr);
-    DCA_ARG(((uintptr_t)out & 3) == 0);
-    hipStream_t st = (hipStream_t)stream;
-    switch (dim) {
-        case 3: return pdb_eval_launch<PdbEval<3>>(states, n, ld, set, out, st);
-        case 4: return pdb_eval_launch<PdbEval<4>>(states, n, ld, set, out, st);
-        case 5: return pdb_eval_launch<PdbEval<5>>(states, n, ld, set, out, st);
-        case 6: return pdb_eval_launch<PdbEval<6>>(states, n, ld, set, out, st);
-        default: return pdb_eval_launch<PdbEval<7>>(states, n, ld, set, out, st);
-    }
+    return pdb_eval_entry(__func__, dim, states, n, ld, num_patterns, tiles, ks, tables, out, false, false, (hipStream_t)stream);
+}
+
+int dca_pdb_eval_reflected(int dim, const uint8_t* states, int64_t n, int64_t ld, int num_patterns, const uint8_t* tiles, const int* ks,
+                           const uint8_t* const* tables, float* out, void* stream) {
+    return pdb_eval_entry(__func__, dim, states, n, ld, num_patterns, tiles, ks, tables, out, true, false, (hipStream_t)stream);
+}
+
+int dca_pdb_eval_host(int dim, const uint8_t* states, int64_t n, int64_t ld, int num_patterns, const uint8_t* tiles, const int* ks,
+                      const uint8_t* const* tables, int reflect, float* out) {
+    return pdb_eval_entry(__func__, dim, states, n, ld, num_patterns, tiles, ks, tables, out, reflect != 0, true, nullptr);
 }
 
 }  // extern "C"

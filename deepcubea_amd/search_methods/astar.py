@@ -258,7 +258,9 @@ def build_parser() -> ArgumentParser:
                         help="Directory of nnet model, or synthetic:SEED, or builtin:manhattan / builtin:zero, or pdb:SPEC — "
                              "additive pattern databases on the sliding puzzles, built on the GPU at start-up: SPEC is a preset "
                              "(puzzle8 4-4; puzzle15 5-5-5, 6-6-3; puzzle24 6-6-6-6; auto = the first of these) or explicit "
-                             "groups of tiles such as 1,2,3,4/5,6,7,8.  On cube3: corner / edge cubie tables combined by max, SPEC a "
+                             "groups of tiles such as 1,2,3,4/5,6,7,8; SPEC+reflect reads the same tables at the state and at its "
+                             "mirror image in the main diagonal and takes the larger value.  "
+                             "On cube3: corner / edge cubie tables combined by max, SPEC a "
                              "preset (corners, korf, korf7; no auto) or groups of cubies of one kind such as "
                              "c0,c1,c2,c3/e0,e1,e2,e3,e4,e5.  Admissible and consistent: with --weight 1 --semantics cpp "
                              "the solutions are optimal.  On lightsout7: exact:gf2 — the exact distance popcount(A^-1 s) by a "

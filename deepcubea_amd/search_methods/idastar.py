@@ -47,11 +47,14 @@ def pattern_database(args):
     spec = model.split(":", 1)[1]
     if env_name == "cube3":
         from ..utils.cube3_pdb import Cube3PatternDatabase
-        return Cube3PatternDatabase(spec)
+        return Cube3PatternDatabase(spec)  # (refuses a +reflect suffix)
     from ..utils.pattern_db import PatternDatabase
     pdb = PatternDatabase(env_name, spec)
     if len(pdb.partition) > _lib.IDASTAR_MAX_PUZZLE_PATTERNS:
         raise ValueError("IDA* takes at most %d patterns on a sliding puzzle, not %d" % (_lib.IDASTAR_MAX_PUZZLE_PATTERNS, len(pdb.partition)))
+    if pdb.reflect and len(pdb.partition) > _lib.IDASTAR_MAX_REFLECT_PATTERNS:
+        raise ValueError("IDA* with +reflect takes at most %d patterns (a lane keeps two running indices per pattern), not %d"
+                         % (_lib.IDASTAR_MAX_REFLECT_PATTERNS, len(pdb.partition)))
     return pdb
 
 
@@ -74,7 +77,7 @@ class IDAStar:
             max_nodes = default_max_nodes(self.env_name)
         if self.env == _lib.ENV_CUBE3:
             return _lib.idastar_cube3(root, self.pdb.patterns, self.pdb.tables, max_nodes)
-        return _lib.idastar_npuzzle(self.dim, root, self.pdb.partition, self.pdb.tables, max_nodes)
+        return _lib.idastar_npuzzle(self.dim, root, self.pdb.partition, self.pdb.tables, max_nodes, reflect=self.pdb.reflect)
 
 
 def refused_root(err: Exception) -> Dict[str, Any]:
@@ -89,7 +92,8 @@ def build_parser() -> ArgumentParser:
     parser.add_argument('--env', type=str, required=True, help="Environment: %s" % ", ".join(ENVS))
     parser.add_argument('--model_dir', type=str, required=True,
                         help="pdb:SPEC, as for astar.py: a preset (puzzle8 4-4; puzzle15 5-5-5, 6-6-3; puzzle24 6-6-6-6; auto; cube3 "
-                             "corners, korf, korf7) or explicit groups.  Built on the GPU at start-up")
+                             "corners, korf, korf7) or explicit groups.  On a sliding puzzle SPEC+reflect searches on the reflected "
+                             "look-up (at most 4 patterns).  Built on the GPU at start-up")
     parser.add_argument('--results_dir', type=str, required=True, help="Directory to save results")
     parser.add_argument('--start_idx', type=int, default=0, help="")
     parser.add_argument('--max_nodes', type=int, default=None,

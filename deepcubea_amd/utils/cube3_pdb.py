@@ -66,6 +66,8 @@ def parse_cube3_pdb_spec(spec: str) -> PatternSet:
     with no device needed, for: an unknown name (cube3 has no "auto"), bare numbers, corners and edges in one group, a cubie
     twice in one group, more than 8 cubies in a group, a table over the size cap, more than 24 groups."""
     spec = str(spec).strip()
+    if "+" in spec:
+        raise ValueError("cube3 pattern database %r: a suffix such as +reflect is defined for the sliding puzzles only" % spec)
     if spec.lower() in PRESETS:
         return PRESETS[spec.lower()]
     if not re.fullmatch(r"[ce\d,/\s]+", spec) or not re.search(r"\d", spec):

@@ -1,6 +1,7 @@
 """Additive disjoint pattern databases for the sliding puzzles (include/dca.h "pattern databases", csrc/dca_pdb.hip): an exact
 admissible, consistent heuristic — the baseline the DeepCubeA paper measures its learned heuristic against.  With
-`--model_dir pdb:<spec> --weight 1 --semantics cpp` the engine is an optimal solver.
+`--model_dir pdb:<spec> --weight 1 --semantics cpp` the engine is an optimal solver.  `<spec>+reflect` reads the same tables at
+the state and at its mirror image in the main diagonal and takes the larger value (Korf & Felner's reflected look-up).
 
 A partition is a tuple of patterns, a pattern a tuple of tiles; `parse_pdb_spec` turns a preset name or explicit groups
 ("1,2,3,4/5,6,7,8") into one and refuses what cannot be built, before any device work."""
@@ -25,6 +26,18 @@ PRESETS: Dict[str, Dict[str, Partition]] = {
 }
 AUTO = {"puzzle8": "4-4", "puzzle15": "5-5-5", "puzzle24": "6-6-6-6"}  # puzzle35 / puzzle48: explicit groups only
 MAX_TABLE_BYTES = 1 << 34  # one pattern's table (the library's own limit)
+REFLECT_SUFFIX = "+reflect"  # a spec that ends in it asks for the reflected look-up (include/dca.h); the tables are the same
+
+
+def split_reflect(spec: str) -> Tuple[str, bool]:
+    """A spec string -> (the spec parse_pdb_spec takes, whether it ended in "+reflect").  ValueError for any other use of '+'."""
+    spec = str(spec).strip()
+    base, plus, suffix = spec.partition("+")
+    if not plus:
+        return spec, False
+    if "+" + suffix.strip().lower() != REFLECT_SUFFIX:
+        raise ValueError("pattern database %r: the only suffix is %s, once" % (spec, REFLECT_SUFFIX))
+    return base.strip(), True
 
 
 def puzzle_dim(env_name: str) -> int:
@@ -172,15 +185,21 @@ class PatternDatabase(_TableSet):
 
     _engine_rows = "state"
 
-    def __init__(self, env_name: str, partition):
+    def __init__(self, env_name: str, partition, reflect: bool = False):
         super().__init__()
         self.env_name = str(env_name).lower()
         self.dim = puzzle_dim(env_name)
-        self.partition = parse_pdb_spec(env_name, partition) if isinstance(partition, str) else check_partition(self.dim, partition)
+        if isinstance(partition, str):
+            partition, suffix = split_reflect(partition)
+            self.partition = parse_pdb_spec(env_name, partition)
+            reflect = bool(reflect) or suffix
+        else:
+            self.partition = check_partition(self.dim, partition)
+        self.reflect = bool(reflect)
 
     @property
     def spec(self) -> str:
-        return "/".join(",".join(str(t) for t in g) for g in self.partition)
+        return "/".join(",".join(str(t) for t in g) for g in self.partition) + (REFLECT_SUFFIX if self.reflect else "")
 
     def _table_bytes(self) -> List[int]:
         return table_bytes(self.dim, self.partition)
@@ -190,7 +209,7 @@ class PatternDatabase(_TableSet):
 
     def heuristic(self, states: torch.Tensor) -> torch.Tensor:
         self._ready("build() or load() first")
-        return _lib.pdb_eval(self.dim, states, self.partition, self.tables)
+        return _lib.pdb_eval(self.dim, states, self.partition, self.tables, reflect=self.reflect)
 
     _engine_heuristic = heuristic  # the engine hands the closure the state rows [m, D]
 

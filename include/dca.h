@@ -247,6 +247,24 @@ int dca_pdb_eval(int dim, const uint8_t* states /*[n, ld]*/, int64_t n, int64_t 
                  const int* ks /*host [num_patterns]*/, const uint8_t* const* tables /*host [num_patterns] of device pointers*/,
                  float* out /*[n]*/, void* stream);
 
+/* Reflected look-up (Korf & Felner 2002): the goal — tile t at position t - 1, the blank at N - 1 — is its own mirror image in the
+ * board's main diagonal, so mirroring a state keeps its distance, and the same tables read at the mirrored state give a second
+ * admissible, consistent value at no table bytes.  For a dim x dim board, N = dim * dim:
+ *   refl(p) = (p mod dim) * dim + p div dim      on positions
+ *   phi(0) = 0, phi(t) = refl(t - 1) + 1         on tiles; both are involutions.
+ * The mirror image of a state holds phi(t) at refl(pos(t)), so the REFLECTED INDEX of a pattern (t_1 ... t_k) on a row is
+ *   refl(pos(0)) + N * (refl(pos(phi(t_1))) + N * (refl(pos(phi(t_2))) + ...))
+ * with pos exactly the any-bytes rule above (the last position < N holding the byte, 0 if none): every digit is < N, so a
+ * reflected look-up is in bounds for ANY bytes, like a plain one.  The reflected value of a row is
+ *   max(sum_p table_p[index_p], sum_p table_p[reflected index_p]),
+ * each sum over the whole set, 0xFE / 0xFF terms included: the larger of two admissible, consistent values, which is again
+ * both.  A partition whose every pattern is its own mirror image (phi maps its tiles onto themselves) gains nothing:
+ * the mirror is then an automorphism of each pattern's abstract graph, and the two look-ups read equal distances.
+ * dca_pdb_eval_reflected: dca_pdb_eval with that value; the same parameters, the same refusals. */
+int dca_pdb_eval_reflected(int dim, const uint8_t* states /*[n, ld]*/, int64_t n, int64_t ld, int num_patterns,
+                           const uint8_t* tiles /*host*/, const int* ks /*host [num_patterns]*/,
+                           const uint8_t* const* tables /*host [num_patterns] of device pointers*/, float* out /*[n]*/, void* stream);
+
 /* Pattern databases for cube3 (csrc/dca_pdb_cube3.hip; `--env cube3 --model_dir pdb:<spec>`): Korf's distance tables over
  * corner cubies and over subsets of the edge cubies, combined by MAX (a face turn moves cubies of several patterns at once, so
  * the tables do not add).  Every table is admissible and consistent on its own, and so is their max.
@@ -382,6 +400,18 @@ int dca_idastar_npuzzle(int dim, const uint8_t* root /*host [N]*/, int num_patte
                         int64_t max_nodes, int* status, int* length, uint8_t* moves /*host [moves_cap]*/, int moves_cap,
                         int* num_thresholds, int* thresholds /*host [thresholds_cap]*/,
                         int64_t* nodes_per_threshold /*host [thresholds_cap]*/, int thresholds_cap, int64_t* total_nodes, void* stream);
+/* dca_idastar_npuzzle with h = the reflected value ("Reflected look-up" above).  A lane keeps a second running index per
+ * pattern, that of the state's mirror image: a move of tile t from position nb to the blank's position b adds
+ * w(t) * (b - nb) to the index of t's pattern, as in the plain search, and w(phi(t)) * (refl(b) - refl(nb)) to the reflected
+ * index of phi(t)'s pattern (nothing where phi(t) is in no pattern); the blank digits b and refl(b) are added at the gather.
+ * The root is unsolvable if any of the 2 * num_patterns root bytes is 0xFE or 0xFF.  Same parameters, outputs and refusals,
+ * except that num_patterns must be in 1..4: the two indices per pattern share the 8 a lane keeps in registers. */
+int dca_idastar_npuzzle_reflected(int dim, const uint8_t* root /*host [N]*/, int num_patterns, const uint8_t* tiles /*host*/,
+                                  const int* ks /*host [num_patterns]*/,
+                                  const uint8_t* const* tables /*host [num_patterns] of device pointers*/, int64_t max_nodes, int* status,
+                                  int* length, uint8_t* moves /*host [moves_cap]*/, int moves_cap, int* num_thresholds,
+                                  int* thresholds /*host [thresholds_cap]*/, int64_t* nodes_per_threshold /*host [thresholds_cap]*/,
+                                  int thresholds_cap, int64_t* total_nodes, void* stream);
 int dca_idastar_cube3(const uint8_t* root /*host [54]*/, int num_patterns, const int* kinds /*host [num_patterns]*/,
                       const uint8_t* cubies /*host*/, const int* ks /*host [num_patterns]*/,
                       const uint8_t* const* tables /*host [num_patterns] of device pointers*/, int64_t max_nodes, int* status, int* length,

@@ -63,7 +63,19 @@ int dca_idastar_host(int env, int dim, const uint8_t* root, int num_patterns, co
                      const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int64_t max_nodes, int* status, int* length,
                      uint8_t* moves, int moves_cap, int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold,
                      int thresholds_cap, int64_t* total_nodes);
-/* test hook, process-wide: every iteration of the three searches above splits its work into items of `depth` prefix moves (a
+/* Host-only: the search of dca_idastar_npuzzle_reflected on the CPU from HOST tables, as dca_idastar_host is that of
+ * dca_idastar_npuzzle.  Same refusals (num_patterns in 1..4), same outputs. */
+int dca_idastar_host_reflected(int dim, const uint8_t* root, int num_patterns, const uint8_t* tiles, const int* ks,
+                               const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int64_t max_nodes, int* status,
+                               int* length, uint8_t* moves, int moves_cap, int* num_thresholds, int* thresholds,
+                               int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes);
+/* Host-only: what dca_pdb_eval computes where reflect == 0, what dca_pdb_eval_reflected computes otherwise, in a plain loop on
+ * the CPU, through the row load and the row value the kernels compile.  states, tables and out are HOST memory; the refusals are those of dca_pdb_eval.
+ * So that the any-bytes rule and the reflected index have a test on a machine without a GPU. */
+int dca_pdb_eval_host(int dim, const uint8_t* states /*host [n, ld]*/, int64_t n, int64_t ld, int num_patterns,
+                      const uint8_t* tiles /*host*/, const int* ks /*host [num_patterns]*/,
+                      const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int reflect, float* out /*host [n]*/);
+/* test hook, process-wide: every iteration of the searches above splits its work into items of `depth` prefix moves (a
  * family's own limit where depth is above it: 15 for the puzzles, 6 for cube3); -1 (the default) = chosen from the previous
  * iteration's node count.  Results never depend on it.  DCA_E_BADARG outside -1..15.
  * NOT thread-safe: one plain global that the production entry points read at every iteration.  Never call it while a search

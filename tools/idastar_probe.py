@@ -9,6 +9,10 @@ first leg that does not exit 0 (nothing is started on a device after a leg has f
   puzzle15   all 500 shipped test states with 5-5-5 and with 6-6-3: solved, length == the shipped optimal length, nodes, seconds.
   puzzle24   the shipped test states in ascending optimal length with 6-6-6-6, until --seconds of search have passed.
   cube3      the shipped test states in ascending optimal length with korf and with korf7, --seconds of search each.
+  puzzle15_reflect, puzzle24_reflect
+             the same states and settings with and without the reflected look-up (`+reflect`), on the same built tables in one
+             process: a plain run, then a reflected one, then both restricted to the states both ran and solved.  Written to
+             profiles/idastar_reflect_probe.txt with `--legs resources,puzzle15_reflect,puzzle24_reflect --out ...`.
 A state's node budget is what the rate measured so far gets through in --state_seconds; a state that runs out of it is listed.
 The rate of a family is nodes over seconds summed over its searches of at least 0.05 s (shorter ones time the launches, not the
 kernel).  No threshold is set on any time or rate: the numbers are recorded, not met."""
@@ -24,7 +28,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-LEG_TIMEOUT_S = {"resources": 120, "puzzle15": 500, "puzzle24": 500, "cube3": 700}
+LEG_TIMEOUT_S = {"resources": 120, "puzzle15": 500, "puzzle24": 500, "cube3": 700, "puzzle15_reflect": 500, "puzzle24_reflect": 700}
 FIRST_BUDGET = 1 << 31  # nodes, until a rate is known
 
 
@@ -64,10 +68,11 @@ class Rate:
 
 
 def run_states(search, label, roots, lens, ids, seconds, state_seconds, verbose):
-    """Searches the roots in order until `seconds` of search have passed -> prints a summary, returns the rate."""
+    """Searches the roots in order until `seconds` of search have passed -> prints a summary, returns the rate and, per state
+    run, {id: (solved, nodes, seconds)}."""
     import torch
     rate = Rate()
-    spent, ran, optimal, missed, nodes_all, times = 0.0, 0, 0, [], [], []
+    spent, ran, optimal, missed, nodes_all, times, records = 0.0, 0, 0, [], [], [], {}
     for root, want, i in zip(roots, lens, ids):
         if spent >= seconds:
             break
@@ -81,6 +86,7 @@ def run_states(search, label, roots, lens, ids, seconds, state_seconds, verbose)
         rate.add(res["nodes_generated"], dt)
         nodes_all.append(res["nodes_generated"])
         times.append(dt)
+        records[int(i)] = (res["solved"], res["nodes_generated"], dt)
         if res["solved"]:
             assert len(res["moves"]) == want, "state %d: length %d, shipped optimal %d" % (i, len(res["moves"]), want)
             optimal += 1
@@ -97,7 +103,7 @@ def run_states(search, label, roots, lens, ids, seconds, state_seconds, verbose)
     for i, want, status, nodes, last in missed:
         print("  %-18s OUT OF BUDGET: state %d (optimal %d): %s after %d nodes, last threshold %s" % ("", i, want, status, nodes, last))
     sys.stdout.flush()
-    return rate.value
+    return rate.value, records
 
 
 def golden():
@@ -115,6 +121,35 @@ def puzzle_leg(env_name, specs, seconds, state_seconds, verbose, in_order):
         pdb = PatternDatabase(env_name, spec).build()
         print("%s pdb:%s: %d bytes built in %.2f s" % (env_name, spec, pdb.bytes, time.time() - t0), flush=True)
         run_states(IDAStar(env_name, pdb), "%s %s" % (env_name, spec), states[ids], lens[ids], ids, seconds, state_seconds, verbose)
+        del pdb
+
+
+def reflect_leg(env_name, specs, seconds, state_seconds, verbose, in_order):
+    """Per spec: the tables built once, a plain run and a reflected run over the same states in the same order, and the two
+    compared on the states both solved."""
+    from deepcubea_amd.search_methods.idastar import IDAStar
+    from deepcubea_amd.utils.pattern_db import PatternDatabase
+    z = golden()
+    states, lens = z["%s_test_states" % env_name], z["%s_test_opt_len" % env_name].astype(int)
+    ids = np.argsort(lens, kind="stable") if in_order else np.arange(len(lens))
+    for spec in specs:
+        t0 = time.time()
+        pdb = PatternDatabase(env_name, spec).build()
+        print("%s pdb:%s: %d bytes built in %.2f s" % (env_name, spec, pdb.bytes, time.time() - t0), flush=True)
+        runs = {}
+        for reflect in (False, True):
+            pdb.reflect = reflect  # the same tables: the suffix changes the look-up, not the bytes
+            runs[reflect] = run_states(IDAStar(env_name, pdb), "%s %s" % (env_name, pdb.spec if reflect else spec), states[ids], lens[ids], ids,
+                                       seconds, state_seconds, verbose)[1]
+        both = [i for i in runs[False] if i in runs[True] and runs[False][i][0] and runs[True][i][0]]
+        nodes = [sum(runs[r][i][1] for i in both) for r in (False, True)]
+        secs = [sum(runs[r][i][2] for i in both) for r in (False, True)]
+        fewer = sum(1 for i in both if runs[True][i][1] < runs[False][i][1])
+        faster = sum(1 for i in both if runs[True][i][2] < runs[False][i][2])
+        print("  %s %s, the %d states both runs solved: nodes plain %.4g, reflected %.4g (x %.3f); seconds plain %.2f, reflected %.2f (x %.3f)"
+              % (env_name, spec, len(both), nodes[0], nodes[1], nodes[1] / nodes[0], secs[0], secs[1], secs[1] / secs[0]))
+        print("  %-18s reflected has fewer nodes on %d and less time on %d of them; nodes/s plain %.3g, reflected %.3g"
+              % ("", fewer, faster, nodes[0] / secs[0], nodes[1] / secs[1]), flush=True)
         del pdb
 
 
@@ -148,6 +183,10 @@ def main():
             puzzle_leg("puzzle15", ("5-5-5", "6-6-3"), 1e9, args.state_seconds, args.verbose, False)
         elif args.leg == "puzzle24":
             puzzle_leg("puzzle24", ("6-6-6-6",), args.seconds, args.state_seconds, args.verbose, True)
+        elif args.leg == "puzzle15_reflect":
+            reflect_leg("puzzle15", ("5-5-5", "6-6-3"), 1e9, args.state_seconds, args.verbose, False)
+        elif args.leg == "puzzle24_reflect":
+            reflect_leg("puzzle24", ("6-6-6-6",), args.seconds, args.state_seconds, args.verbose, True)
         elif args.leg == "cube3":
             cube3_leg(args.seconds, args.state_seconds, args.verbose)
         else:

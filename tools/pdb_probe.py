@@ -1,13 +1,14 @@
 """Pattern databases on the MI355X, measured once -> profiles/pdb_probe.txt.
 
-    python tools/pdb_probe.py [--states 500] [--cap 16777216] [--budget_s 150] [--puzzle24 | --only_puzzle24]
+    python tools/pdb_probe.py [--states 500] [--cap 16777216] [--budget_s 150] [--puzzle24 | --only_puzzle24 | --reflect_eval]
 
 Legs: (1) build time and sweep count of every preset (puzzle24 6-6-6-6 — four tables of 6.1 GB — only with --puzzle24);
 (2) dca_pdb_eval rows/s at 131 072 rows; (3) on the shipped puzzle15 test states (tests/golden/golden.npz, with their optimal
 lengths): BWAS at weight 1, cpp semantics, batch 10 000 under a node cap (`--cap` ids per search) with pdb:5-5-5, pdb:6-6-3
 and builtin:manhattan — how many states each solves at the optimal length inside the cap, and the nodes generated per state.
 Each heuristic gets `--budget_s` seconds of wall time and walks the states in file order; the comparison is made on the prefix
-every heuristic reached."""
+every heuristic reached.  `--reflect_eval` runs one leg alone: rows/s of the plain and of the reflected eval (`+reflect`) on
+1 048 576 rows of puzzle15 (5-5-5, 6-6-3) and puzzle24 (6-6-6-6), the two timed alternately after a warm-up, with the spread."""
 import argparse
 import os
 import sys
@@ -54,6 +55,29 @@ def eval_leg(env, name, pdb, rows=131072, reps=20):
           % (env, name, rows, med * 1e6, min(times) * 1e6, rows / med, reps), flush=True)
 
 
+def reflect_eval_leg(env, name, pdb, rows=1 << 20, reps=20):
+    D = pdb.dim * pdb.dim
+    rng = np.random.default_rng(0)
+    X = torch.from_numpy(rng.permuted(np.tile(np.arange(D, dtype=np.uint8), (rows, 1)), axis=1)).cuda()
+    out = torch.empty(rows, dtype=torch.float32, device="cuda")
+    times = {False: [], True: []}
+    for rep in range(3 + reps):  # three warm-up rounds, then plain and reflected alternately
+        for reflect in (False, True):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            _lib.pdb_eval(pdb.dim, X, pdb.partition, pdb.tables, out=out, reflect=reflect)
+            b.record()
+            b.synchronize()
+            if rep >= 3:
+                times[reflect].append(a.elapsed_time(b) * 1e-3)
+    med = {r: float(np.median(t)) for r, t in times.items()}
+    for reflect in (False, True):
+        t = times[reflect]
+        print("eval   %-9s %-16s %d rows (uniform random permutations)  median %.1f us  min %.1f us  max %.1f us  %.3g rows/s (median of %d)"
+              % (env, name + ("+reflect" if reflect else ""), rows, med[reflect] * 1e6, min(t) * 1e6, max(t) * 1e6, rows / med[reflect], reps), flush=True)
+    print("eval   %-9s %-16s reflected / plain time: %.2f" % (env, name, med[True] / med[False]), flush=True)
+
+
 def search_leg(label, states, opt, cap, budget_s, pdb=None):
     eng = BwasEngine("puzzle15", 1.0, 10000, max_nodes=cap, semantics=_lib.SEM_CPP, packed=pdb is not None)
     fn = pdb.heuristic_fn_dev() if pdb is not None else None
@@ -81,10 +105,18 @@ def main():
     ap.add_argument("--budget_s", type=float, default=150.0)
     ap.add_argument("--puzzle24", action="store_true")
     ap.add_argument("--only_puzzle24", action="store_true", help="the puzzle24 6-6-6-6 build and eval legs alone")
+    ap.add_argument("--reflect_eval", action="store_true", help="the plain against the reflected eval on 2^20 rows, alone")
     args = ap.parse_args()
     _lib.require_gpu()
     print("pdb_probe: %s, states %d, node cap %d per search, %.0f s per heuristic" % (torch.cuda.get_device_name(0), args.states, args.cap,
                                                                                      args.budget_s), flush=True)
+    if args.reflect_eval:
+        for env, name in (("puzzle15", "5-5-5"), ("puzzle15", "6-6-3"), ("puzzle24", "6-6-6-6")):
+            pdb = build_leg(env, name)
+            reflect_eval_leg(env, name, pdb)
+            del pdb
+            torch.cuda.empty_cache()
+        return
     built = {}
     for env in ("puzzle8", "puzzle15"):
         for name in sorted(PRESETS[env]) if not args.only_puzzle24 else ():
