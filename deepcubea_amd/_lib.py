@@ -71,12 +71,14 @@ _SIGNATURES = {
     "dca_cube3_pdb_index": "i ipipip",
     "dca_cube3_pdb_build": "i ipippp",
     "dca_cube3_pdb_eval": "i plliipppppp",
+    "dca_cube3_pdb_eval_sym": "i plliippppipp",
     "dca_lightsout_exact_matrix": "i ip",
     "dca_lightsout_exact_eval": "i ipllpp",
     "dca_lightsout_exact_solve": "i ipllpp",
     "dca_idastar_npuzzle": "i ipippplpppipppipp",
     "dca_idastar_npuzzle_reflected": "i ipippplpppipppipp",
     "dca_idastar_cube3": "i pipppplpppipppipp",
+    "dca_idastar_cube3_sym": "i pippppilpppipppipp",
     "dca_engine_create": "i piidilii",
     "dca_engine_create_multi": "i piidiliii",
     "dca_engine_num_instances": "i p",
@@ -153,6 +155,10 @@ _SIGNATURES = {
     "dca_idastar_host": "i iipipppplpppipppip",
     "dca_idastar_host_reflected": "i ipippplpppipppip",
     "dca_pdb_eval_host": "i ipllipppip",
+    "dca_idastar_host_sym": "i pippppilpppipppip",
+    "dca_cube3_pdb_eval_sym_host": "i plliippppip",
+    "dca_cube3_sym_tables": "i pp",
+    "dca_cube3_sym_images": "i ipiipppp",
     "dca_idastar_set_prefix": "i i",
     "dca_debug_write_ceiling": "i pllp",
     "dca_f16x3_gemm_variant": "i i",
@@ -624,12 +630,54 @@ def cube3_pdb_build(kind: int, cubies, table: Optional[torch.Tensor] = None):
     return _pdb_build("dca_cube3_pdb_build", cube3_pdb_bytes, kind, cubies, table)
 
 
-def cube3_pdb_eval(states: torch.Tensor, row_kind: int, patterns, tables, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def cube3_pdb_eval(states: torch.Tensor, row_kind: int, patterns, tables, out: Optional[torch.Tensor] = None, sym: int = 0) -> torch.Tensor:
     """Max of the patterns' table bytes per row -> f32 [n].  patterns: [(kind, cubies), ...]; states: uint8 device rows
-    [n, >= 54] with unit byte stride (a strided view is fine); ANY bytes are in bounds (include/dca.h, the any-bytes rule)."""
-    return _pdb_eval("cube3_pdb_eval", "dca_cube3_pdb_eval", states, 54, [g for _, g in patterns], [kind for kind, _ in patterns],
-                     _cube3_table_bytes, tables, out,
-                     lambda s, n, ld, m, *rest: lib().dca_cube3_pdb_eval(s, n, ld, row_kind, m, *rest))
+    [n, >= 54] with unit byte stride (a strided view is fine); ANY bytes are in bounds (include/dca.h, the any-bytes rule).
+    sym = N in 1..48: the max over the first N images of every pattern as well (include/dca.h, "Symmetric look-ups"); 0: plain."""
+    groups, kinds = [g for _, g in patterns], [kind for kind, _ in patterns]
+    if not sym:
+        return _pdb_eval("cube3_pdb_eval", "dca_cube3_pdb_eval", states, 54, groups, kinds, _cube3_table_bytes, tables, out,
+                         lambda s, n, ld, m, *rest: lib().dca_cube3_pdb_eval(s, n, ld, row_kind, m, *rest))
+    return _pdb_eval("cube3_pdb_eval", "dca_cube3_pdb_eval_sym", states, 54, groups, kinds, _cube3_table_bytes, tables, out,
+                     lambda s, n, ld, m, k, c, ks, t, *rest: lib().dca_cube3_pdb_eval_sym(s, n, ld, row_kind, m, k, c, ks, t, int(sym), *rest))
+
+
+CUBE3_SYMS, CUBE3_SYM_MAX_LOOKUPS = 48, 64  # include/dca.h
+
+
+def cube3_pdb_eval_host(rows, row_kind: int, patterns, tables, sym: int = 1) -> np.ndarray:
+    """cube3_pdb_eval(sym=...) on the CPU (include/dca_debug.h: the kernel's own row value in a plain loop) -> float32 [n].
+    rows: a uint8 host array [n, >= 54]; tables: one uint8 host array per pattern.  sym = 1 is the plain value.  No device needed."""
+    rows = np.asarray(rows)
+    if rows.dtype != np.uint8 or rows.ndim != 2:
+        raise ValueError("cube3_pdb_eval_host: rows must be a uint8 host array [n, >= 54]")
+    rows = np.ascontiguousarray(rows)
+    _table_sizes("cube3_pdb_eval_host", [_cube3_table_bytes(kind, len(g)) for kind, g in patterns], tables, True)
+    (kinds, ids, ks), ptrs, _keep = _idastar_set([g for _, g in patterns], [kind for kind, _ in patterns], tables, True)
+    out = np.zeros(len(rows), np.float32)
+    check(lib().dca_cube3_pdb_eval_sym_host(rows.ctypes.data_as(C.c_void_p), len(rows), rows.shape[1], row_kind, len(patterns), kinds, ids,
+                                            ks, ptrs, int(sym), out.ctypes.data_as(C.c_void_p)), "dca_cube3_pdb_eval_sym_host")
+    return out
+
+
+def cube3_sym_tables():
+    """The 48 symmetries as the library derives them, in include/dca.h's order -> (sticker permutations uint8 [48, 54], position
+    -> position; move maps uint8 [48, 12]).  No device needed."""
+    sticker, move = np.zeros((CUBE3_SYMS, 54), np.uint8), np.zeros((CUBE3_SYMS, 12), np.uint8)
+    check(lib().dca_cube3_sym_tables(sticker.ctypes.data_as(C.c_void_p), move.ctypes.data_as(C.c_void_p)), "dca_cube3_sym_tables")
+    return sticker, move
+
+
+def cube3_sym_images(kind: int, cubies, max_images: int = CUBE3_SYMS):
+    """The first min(max_images, distinct) images of one pattern -> (the symmetry standing for each uint8 [m], their source cubies
+    uint8 [m, k], their location maps uint8 [m, k, 24]).  No device needed."""
+    cubies = _byte_list(cubies)
+    k, count = len(cubies), C.c_int(0)
+    syms, src, maps = np.zeros(CUBE3_SYMS, np.uint8), np.zeros((CUBE3_SYMS, 8), np.uint8), np.zeros((CUBE3_SYMS, 8, 24), np.uint8)
+    check(lib().dca_cube3_sym_images(kind, cubies.ctypes.data_as(C.c_void_p), k, int(max_images), C.byref(count),
+                                     *(a.ctypes.data_as(C.c_void_p) for a in (syms, src, maps))), "dca_cube3_sym_images")
+    m = count.value
+    return syms[:m].copy(), src[:m, :k].copy(), maps[:m, :k].copy()
 
 
 # ------------------------------------------------------------------------------ exact LightsOut heuristic (lightsout7)
@@ -739,20 +787,26 @@ def idastar_npuzzle(dim: int, root, partition, tables, max_nodes: int, reflect: 
                     root, max(dim, 0) ** 2, max_nodes)
 
 
-def idastar_cube3(root, patterns, tables, max_nodes: int) -> dict:
-    """Optimal solution of one cube3 root (54 sticker ids) by IDA* on the device tables of `patterns` [(kind, cubies), ...]."""
+def idastar_cube3(root, patterns, tables, max_nodes: int, sym: int = 0) -> dict:
+    """Optimal solution of one cube3 root (54 sticker ids) by IDA* on the device tables of `patterns` [(kind, cubies), ...].
+    sym = N in 1..48: h is the max over the first N images of every pattern (include/dca.h, "Symmetric look-ups"); 0: plain."""
     _table_sizes("idastar_cube3", [_cube3_table_bytes(kind, len(g)) for kind, g in patterns], tables, False)
     (kinds, ids, ks), ptrs, _keep = _idastar_set([g for _, g in patterns], [kind for kind, _ in patterns], tables, False)
+    if sym:
+        return _idastar("dca_idastar_cube3_sym", lambda r, n, *out: lib().dca_idastar_cube3_sym(r, len(patterns), kinds, ids, ks, ptrs, int(sym),
+                                                                                                n, *out, stream_ptr()), root, 54, max_nodes)
     return _idastar("dca_idastar_cube3", lambda r, n, *out: lib().dca_idastar_cube3(r, len(patterns), kinds, ids, ks, ptrs, n, *out,
                                                                                     stream_ptr()), root, 54, max_nodes)
 
 
-def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int, reflect: bool = False) -> dict:
+def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int, reflect: bool = False, sym: int = 0) -> dict:
     """The same search run sequentially on the CPU from HOST tables (include/dca_debug.h): no device needed.  patterns: the
     partition (puzzles) or [(kind, cubies), ...] (cube3); tables: one uint8 array per pattern.  reflect: the reflected search,
-    sliding puzzles only."""
+    sliding puzzles only.  sym = N: the search on the symmetric look-ups, cube3 only."""
     if reflect and env != ENV_NPUZZLE:
         raise ValueError("idastar_host: the reflected look-up is defined for the sliding puzzles only")
+    if sym and env != ENV_CUBE3:
+        raise ValueError("idastar_host: the symmetric look-ups are defined for cube3 only")
     if env == ENV_CUBE3:
         groups, families = [g for _, g in patterns], [kind for kind, _ in patterns]
         sizes, width = [_cube3_table_bytes(kind, len(g)) for kind, g in patterns], 54
@@ -761,6 +815,9 @@ def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int, ref
         sizes, width = [_pdb_table_bytes(dim, len(g)) for g in patterns], max(dim, 0) ** 2
     _table_sizes("idastar_host", sizes, tables, True)
     (kinds, ids, ks), ptrs, _keep = _idastar_set(groups, families, tables, True)
+    if sym:
+        return _idastar("dca_idastar_host_sym", lambda r, n, *out: lib().dca_idastar_host_sym(r, len(groups), kinds, ids, ks, ptrs, int(sym),
+                                                                                              n, *out), root, width, max_nodes)
     if reflect:
         return _idastar("dca_idastar_host_reflected", lambda r, n, *out: lib().dca_idastar_host_reflected(dim, r, len(groups), ids, ks, ptrs,
                                                                                                           n, *out), root, width, max_nodes)

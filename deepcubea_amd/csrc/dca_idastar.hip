@@ -10,6 +10,8 @@
 //            dca_idastar_host (include/dca_debug.h).
 //   reflect  PzDomain<DIM, true>: the puzzles' search on the reflected look-up (include/dca.h) — a second running index per
 //            pattern, that of the state's mirror image, in the other half of the lane's eight, and h the larger of the two sums.
+//   sym      C3SymDomain: cube3's search on the symmetric look-ups (include/dca.h) — the same state and moves, h the largest byte
+//            over a look-up list in global memory, left at the first value that already prunes the child (BOUNDED).
 //   work     item i of an iteration names a move prefix of P moves, the mixed-radix digits of i (first move = most significant
 //            digit; cube3: radix 12; puzzles: 4 for the first move, then 3 — a digit picks among the moves that do not undo
 //            the one before).  A lane replays the prefix from the root under the pruning rules and the f <= T test and drops the item
@@ -23,7 +25,8 @@
 //            passes the budget and polls the stop word there.  Whoever stops the launch also sets the item counter's top bit,
 //            which ends every other lane's item fetch.
 //
-// Rates are in profiles/idastar_probe.txt; the reflected search against the plain one in profiles/idastar_reflect_probe.txt.
+// Rates are in profiles/idastar_probe.txt; the reflected search against the plain one in profiles/idastar_reflect_probe.txt,
+// the symmetric one in profiles/idastar_sym_probe.txt.
 #include <mutex>
 #include <type_traits>
 
@@ -73,6 +76,7 @@ template <int DIM, bool REFLECT = false>
 struct PzDomain {
     static constexpr int N = DIM * DIM, NM = 4, RADIX = 3, MOVE_BITS = 2, MAX_PREFIX = 15, STACK_WORDS = 16;
     static constexpr int BITS = N <= 16 ? 4 : 5;
+    static constexpr bool BOUNDED = false;  // h(s, c): the whole value, whatever the threshold
     using Board = std::conditional_t<(N * BITS <= 64), uint64_t, unsigned __int128>;
     struct State {
         Board board;                        // position i holds tile (board >> BITS * i) & MASK
@@ -160,6 +164,7 @@ struct PzDomain {
 // ---------------------------------------------------------------------------------------------------------------- cube3
 struct C3Domain {
     static constexpr int NM = 12, RADIX = 12, MOVE_BITS = 4, MAX_PREFIX = 6, STACK_WORDS = 32;
+    static constexpr bool BOUNDED = false;
     struct State {
         uint64_t corner, edge;  // c3_row_locs: 5 bits a cubie
     };
@@ -217,6 +222,31 @@ struct C3Domain {
     static DCA_IDA_INLINE bool goal(const State& s) { return s.corner == home(8, 3) && s.edge == home(12, 2); }
 };
 
+// cube3 on the symmetric look-ups (include/dca.h "Symmetric look-ups"): the same state, moves, rules and goal; h is the largest
+// byte over the look-up list.  The list and its location maps stay in global memory: LDS — what bounds this kernel's occupancy —
+// holds what the plain kernel's does.  A trip of four look-ups reads its four heads by scalar loads (the trip's number is
+// wave-uniform), issues its 32 per-lane map reads together, ranks, and issues its four gathers together (c3_sym_gather4;
+// checked in the generated code, profiles/cube3_sym_isa.txt).
+struct C3SymDomain : C3Domain {
+    static constexpr bool BOUNDED = true;  // h(s, c, slack) may stop at the first value above slack
+    struct Ctx : C3Domain::Ctx {
+        const C3SymList* list;
+        int n;
+    };
+    // The largest byte over the list, or — the early exit — over its first look-ups once that is above `slack` = T - g - 1:
+    // f > T either way, so the same children are pruned as under the full maximum; only the f a pruned child records for the
+    // next threshold may be smaller than its exact f (include/dca.h: the thresholds of the exact search still all occur).
+    static DCA_IDA_INLINE uint32_t h(const State& s, const Ctx& c, uint32_t slack) {
+        uint32_t best = 0;
+        for (int p0 = 0; p0 < c.n; p0 += 4) {  // four independent gathers in flight
+            const uint32_t v = c3_sym_gather4(c.list, p0, s.corner, s.edge);
+            best = best > v ? best : v;
+            if (best > slack) break;
+        }
+        return best;
+    }
+};
+
 // ------------------------------------------------------------------------------------------------------------ the frame
 // One lane's share of one iteration (threshold T, prefix depth P, n_items = NM * RADIX^(P-1) < 2^31 work items).  stk: the lane's move
 // stack, word w at stk[w * stride].  budget: the nodes this launch may still count; poll: the nodes between a lane's flushes.
@@ -265,7 +295,11 @@ DCA_IDA_INLINE void ida_lane(const typename D::Ctx& c, const typename D::State& 
             a = cursor;
         }
         const typename D::State ch = D::apply(s, a, c);
-        const uint32_t f = g + 1u + D::h(ch, c);
+        uint32_t f;
+        if constexpr (D::BOUNDED)  // a bounded family is told how much room is left below T
+            f = g + 1u + D::h(ch, c, T > g ? T - g - 1u : 0u);
+        else
+            f = g + 1u + D::h(ch, c);
         since += (!replay || item % below == 0u) ? 1u : 0u;  // a replayed node: counted by the item whose later digits are 0
         if (f <= T) {
             uint32_t* word = stk + (g / PER) * stride;
@@ -376,6 +410,23 @@ __global__ __launch_bounds__(kIdaThreads) void ida_cube3_kernel(C3Domain::State 
     c.mv = (const uint8_t*)mvw;
     c.set = &set;
     ida_lane<C3Domain>(c, root, ctrl, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
+}
+
+__global__ __launch_bounds__(kIdaThreads) void ida_cube3_sym_kernel(C3Domain::State root, C3SymSet set, C3IdaMoves mt, IdaCtrl* ctrl, uint32_t T,
+                                                                    uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
+    __shared__ uint32_t mvw[2 * 12 * kC3Locs / 4];
+    __shared__ uint32_t stk[C3Domain::STACK_WORDS * kIdaThreads];
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < 2 * 12 * kC3Locs / 4; q++) mvw[q] = mt.w[q];
+    }
+    __syncthreads();
+    C3SymDomain::Ctx c;
+    c.mv = (const uint8_t*)mvw;
+    c.set = nullptr;
+    c.list = set.list;
+    c.n = set.n;
+    ida_lane<C3SymDomain>(c, root, ctrl, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
 }
 
 // ----------------------------------------------------------------------------------------------------------- host side
@@ -670,6 +721,67 @@ static int ida_puzzle(const uint8_t* root, const PdbSet& set, int64_t max_nodes,
     return rc;
 }
 
+static C3IdaMoves c3_ida_moves() {
+    C3IdaMoves mt{};
+    for (int kind = 0; kind < 2; kind++)
+        for (int a = 0; a < 12; a++)
+            for (int l = 0; l < kC3Locs; l++)
+                mt.w[((kind * 12 + a) * kC3Locs + l) >> 2] |= (uint32_t)kC3.move[kind][a][l] << (8 * (l & 3));
+    return mt;
+}
+
+// The search on the symmetric look-ups: ida_cube3 with the list in place of the set.  The list's tables are device memory
+// (on_device) or host memory; the root's h is the full maximum, and the root is dead where ANY look-up's byte is >= 0xFE.
+static int ida_cube3_sym(const uint8_t* root, const C3SymList& list, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
+    uint32_t w[14];
+    pdb_load_row<54, 1>(root, w);
+    C3Domain::State s0;
+    s0.corner = c3_row_locs<DCA_CUBE3_CORNERS, DCA_ROWS_STATE>(w);
+    s0.edge = c3_row_locs<DCA_CUBE3_EDGES, DCA_ROWS_STATE>(w);
+    uint64_t root_idx[kC3SymMaxLookups] = {};
+    const uint8_t* tables[kC3SymMaxLookups] = {};
+    for (int p = 0; p < list.n; p++) {
+        const C3Lookup& lk = list.lk[p];
+        root_idx[p] = c3_sym_index(&lk, c3_lookup_head(&lk), s0.corner, s0.edge);
+        tables[p] = lk.table;
+    }
+    uint8_t v[kC3SymMaxLookups] = {};
+    if (int rc = ida_root_bytes(on_device, list.n, tables, root_idx, st, v)) return rc;
+    uint32_t h_root = 0;
+    bool dead = false;
+    for (int p = 0; p < list.n; p++) {
+        dead = dead || v[p] >= kPdbInf;
+        h_root = h_root > v[p] ? h_root : v[p];
+    }
+    const C3IdaMoves mt = c3_ida_moves();
+    const bool search = !dead && !C3Domain::goal(s0);
+    C3SymSet arg{&list, list.n, list.kinds_used};
+    IdaCtrl* dev = nullptr;
+    int device = -1;
+    if (on_device && search) {
+        if (int rc = c3_sym_device_list(list, arg.list)) return rc;
+        if (int rc = ida_block_take(dev, device)) return rc;
+    }
+    const int rc = ida_drive<C3SymDomain>(h_root, dead, C3Domain::goal(s0), max_nodes, out,
+                                          [&](uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, IdaCtrl& ctrl) {
+        if (on_device)
+            return ida_device_iteration(dev, ctrl, st, "ida_cube3_sym_kernel", [&] {
+                hipLaunchKernelGGL(ida_cube3_sym_kernel, dim3(ida_blocks(n_items)), dim3(kIdaThreads), 0, st, s0, arg, mt, dev, T, P, n_items, budget,
+                                   ida_poll(budget, ida_blocks(n_items) * kIdaThreads));
+            });
+        C3SymDomain::Ctx c;
+        c.mv = (const uint8_t*)mt.w;
+        c.set = nullptr;
+        c.list = &list;
+        c.n = list.n;
+        uint32_t stk[C3Domain::STACK_WORDS] = {};
+        ida_lane<C3SymDomain>(c, s0, &ctrl, stk, 1u, T, P, n_items, budget, ida_poll(budget, 1));
+        return 0;
+    });
+    ida_block_give(dev, device, rc == 0);
+    return rc;
+}
+
 static int ida_cube3(const uint8_t* root, const C3Set& set, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
     uint32_t w[14];
     pdb_load_row<54, 1>(root, w);
@@ -688,11 +800,7 @@ static int ida_cube3(const uint8_t* root, const C3Set& set, int64_t max_nodes, c
         dead = dead || v[p] >= kPdbInf;
         h_root = h_root > v[p] ? h_root : v[p];
     }
-    C3IdaMoves mt{};
-    for (int kind = 0; kind < 2; kind++)
-        for (int a = 0; a < 12; a++)
-            for (int l = 0; l < kC3Locs; l++)
-                mt.w[((kind * 12 + a) * kC3Locs + l) >> 2] |= (uint32_t)kC3.move[kind][a][l] << (8 * (l & 3));
+    const C3IdaMoves mt = c3_ida_moves();
     IdaCtrl* dev = nullptr;
     int device = -1;
     if (on_device && !dead && !C3Domain::goal(s0))
@@ -793,6 +901,22 @@ static int ida_cube3_entry(const char* who, const uint8_t* root, int num_pattern
     return ida_cube3(root, set, max_nodes, out, on_device, st);
 }
 
+// every refusal of a symmetric cube3 search, then the search: before any HIP call
+static int ida_cube3_sym_entry(const char* who, const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
+                               const uint8_t* const* tables, int max_images, int64_t max_nodes, const IdaOut& out, bool on_device,
+                               hipStream_t st) {
+    if (root == nullptr) {
+        set_error("bad argument: %s: root must not be NULL", who);
+        return DCA_E_BADARG;
+    }
+    if (int rc = ida_check_out(who, max_nodes, out)) return rc;
+    C3Set set{};
+    C3SymList list;
+    if (int rc = c3_fill_sym_entry(who, num_patterns, kinds, cubies, ks, tables, max_images, set, list)) return rc;
+    if (int rc = ida_check_cube3_root(who, root)) return rc;
+    return ida_cube3_sym(root, list, max_nodes, out, on_device, st);
+}
+
 }  // namespace dca
 
 using namespace dca;
@@ -822,6 +946,14 @@ int dca_idastar_cube3(const uint8_t* root, int num_patterns, const int* kinds, c
     return ida_cube3_entry(__func__, root, num_patterns, kinds, cubies, ks, tables, max_nodes, out, true, (hipStream_t)stream);
 }
 
+int dca_idastar_cube3_sym(const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
+                          const uint8_t* const* tables, int max_images, int64_t max_nodes, int* status, int* length, uint8_t* moves,
+                          int moves_cap, int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap,
+                          int64_t* total_nodes, void* stream) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    return ida_cube3_sym_entry(__func__, root, num_patterns, kinds, cubies, ks, tables, max_images, max_nodes, out, true, (hipStream_t)stream);
+}
+
 int dca_idastar_host(int env, int dim, const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* ids, const int* ks,
                      const uint8_t* const* tables, int64_t max_nodes, int* status, int* length, uint8_t* moves, int moves_cap,
                      int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes) {
@@ -837,6 +969,14 @@ int dca_idastar_host_reflected(int dim, const uint8_t* root, int num_patterns, c
                                int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes) {
     const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
     return ida_npuzzle_entry(__func__, dim, root, num_patterns, tiles, ks, tables, max_nodes, out, false, nullptr, true);
+}
+
+int dca_idastar_host_sym(const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
+                         const uint8_t* const* tables, int max_images, int64_t max_nodes, int* status, int* length, uint8_t* moves,
+                         int moves_cap, int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap,
+                         int64_t* total_nodes) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    return ida_cube3_sym_entry(__func__, root, num_patterns, kinds, cubies, ks, tables, max_images, max_nodes, out, false, nullptr);
 }
 
 int dca_idastar_set_prefix(int depth) {

@@ -15,6 +15,10 @@
 //           picks its cubies (wave-uniform shifts).  Every rank digit is clamped below its radix, so any 54 bytes give an
 //           index inside the table.  One byte gather per pattern, four in flight, max, written as fp32.
 //
+//   eval_sym  the same frame on the symmetric look-ups (dca_pdb_cube3.h "symmetries", include/dca.h): the locations once per
+//           row, then trips of four look-ups — their heads by scalar loads, their 32 map reads issued together, four ranks,
+//           four gathers issued together.  The list is global memory.  Cost per row: profiles/idastar_sym_probe.txt.
+//
 // What bounds either kernel has not been measured (profiles/cube3_pdb_probe.txt holds only wall-clock times).
 #include "dca_pdb_cube3.h"
 
@@ -161,6 +165,89 @@ int dca_cube3_pdb_eval(const uint8_t* states, int64_t n, int64_t ld, int row_kin
     hipStream_t st = (hipStream_t)stream;
     return row_kind == DCA_ROWS_STATE ? pdb_eval_launch<C3Eval<DCA_ROWS_STATE>>(states, n, ld, set, out, st)
                                       : pdb_eval_launch<C3Eval<DCA_ROWS_NNET>>(states, n, ld, set, out, st);
+}
+
+int dca_cube3_pdb_eval_sym(const uint8_t* states, int64_t n, int64_t ld, int row_kind, int num_patterns, const int* kinds,
+                           const uint8_t* cubies, const int* ks, const uint8_t* const* tables, int max_images, float* out,
+                           void* stream) {
+    DCA_ARG(n >= 0 && n < ((int64_t)1 << 31));
+    DCA_ARG(ld >= 54);
+    DCA_ARG(row_kind == DCA_ROWS_STATE || row_kind == DCA_ROWS_NNET);
+    C3Set set{};
+    C3SymList list;
+    if (int rc = c3_fill_sym_entry(__func__, num_patterns, kinds, cubies, ks, tables, max_images, set, list)) return rc;
+    if (n == 0) return 0;
+    DCA_ARG(states != nullptr && out != nullptr);
+    DCA_ARG(((uintptr_t)out & 3) == 0);
+    C3SymSet arg{nullptr, list.n, list.kinds_used};
+    if (int rc = c3_sym_device_list(list, arg.list)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return row_kind == DCA_ROWS_STATE ? pdb_eval_launch<C3EvalSym<DCA_ROWS_STATE>>(states, n, ld, arg, out, st)
+                                      : pdb_eval_launch<C3EvalSym<DCA_ROWS_NNET>>(states, n, ld, arg, out, st);
+}
+
+int dca_cube3_pdb_eval_sym_host(const uint8_t* states, int64_t n, int64_t ld, int row_kind, int num_patterns, const int* kinds,
+                                const uint8_t* cubies, const int* ks, const uint8_t* const* tables, int max_images, float* out) {
+    DCA_ARG(n >= 0 && n < ((int64_t)1 << 31));
+    DCA_ARG(ld >= 54);
+    DCA_ARG(row_kind == DCA_ROWS_STATE || row_kind == DCA_ROWS_NNET);
+    C3Set set{};
+    C3SymList list;
+    if (int rc = c3_fill_sym_entry(__func__, num_patterns, kinds, cubies, ks, tables, max_images, set, list)) return rc;
+    if (n == 0) return 0;
+    DCA_ARG(states != nullptr && out != nullptr);
+    const C3SymSet arg{&list, list.n, list.kinds_used};
+    for (int64_t i = 0; i < n; i++) {  // the kernel's row load and row value, one row after another
+        uint32_t w[14];
+        pdb_load_row<54, 1>(states + i * ld, w);
+        out[i] = (float)(row_kind == DCA_ROWS_STATE ? C3EvalSym<DCA_ROWS_STATE>::row_value(w, arg)
+                                                    : C3EvalSym<DCA_ROWS_NNET>::row_value(w, arg));
+    }
+    return 0;
+}
+
+int dca_cube3_sym_tables(uint8_t* sticker_perms, uint8_t* move_maps) {
+    DCA_ARG(sticker_perms != nullptr && move_maps != nullptr);
+    const Cube3Syms& t = c3_syms();
+    if (t.broken != nullptr) {
+        set_error("%s: the cube's symmetries could not be derived from the move table: %s", __func__, t.broken);
+        return DCA_E_STATE;
+    }
+    for (int s = 0; s < kC3Syms; s++) {
+        for (int p = 0; p < 54; p++) sticker_perms[s * 54 + p] = t.sticker[s][p];
+        for (int a = 0; a < 12; a++) move_maps[s * 12 + a] = t.move[s][a];
+    }
+    return 0;
+}
+
+int dca_cube3_sym_images(int kind, const uint8_t* cubies, int k, int max_images, int* num_images, uint8_t* syms, uint8_t* sources,
+                         uint8_t* maps) {
+    const int64_t total = c3_bytes_checked(__func__, kind, k);
+    if (total < 0) return (int)total;
+    DCA_ARG(cubies != nullptr);
+    DCA_ARG(num_images != nullptr);
+    if (int rc = c3_check_cubies(__func__, kind, cubies, k)) return rc;
+    C3Set set{};
+    set.np = 1;
+    set.kind[0] = (uint8_t)kind;
+    set.k[0] = (uint8_t)k;
+    set.pat[0] = pdb_pattern(cubies, k);
+    set.kinds_used = 1 << kind;
+    C3SymList list;
+    if (int rc = c3_fill_sym_list(__func__, set, max_images, list)) return rc;
+    *num_images = list.n;
+    const int o = kind == DCA_CUBE3_CORNERS ? 3 : 2;
+    for (int i = 0; i < list.n; i++) {
+        if (syms) syms[i] = (uint8_t)(list.lk[i].meta >> 16);
+        for (int j = 0; j < k; j++) {
+            if (sources) sources[i * kPdbMaxK + j] = (uint8_t)(list.lk[i].shift[j] / 5);
+            for (int l = 0; l < kC3Locs; l++) {  // the location, from the list's slot | r << 4
+                const int to = list.lk[i].map[j][l];
+                if (maps) maps[(i * kPdbMaxK + j) * kC3Locs + l] = (uint8_t)((to & 15) * o + (to >> 4));
+            }
+        }
+    }
+    return 0;
 }
 
 }  // extern "C"

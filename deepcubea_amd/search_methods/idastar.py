@@ -47,7 +47,11 @@ def pattern_database(args):
     spec = model.split(":", 1)[1]
     if env_name == "cube3":
         from ..utils.cube3_pdb import Cube3PatternDatabase
-        return Cube3PatternDatabase(spec)  # (refuses a +reflect suffix)
+        return Cube3PatternDatabase(spec)  # (takes +sym / +sym:N, refuses a +reflect suffix)
+    from ..utils.cube3_pdb import SYM_SUFFIX
+    if spec.partition("+")[2].strip().lower().startswith(SYM_SUFFIX[1:]):
+        raise ValueError("pattern database %r: %s reads a table at the images of a state under the cube's 48 symmetries, and is "
+                         "defined for cube3 only; a sliding puzzle's one symmetry is +reflect" % (spec, SYM_SUFFIX))
     from ..utils.pattern_db import PatternDatabase
     pdb = PatternDatabase(env_name, spec)
     if len(pdb.partition) > _lib.IDASTAR_MAX_PUZZLE_PATTERNS:
@@ -76,7 +80,7 @@ class IDAStar:
         if max_nodes is None:
             max_nodes = default_max_nodes(self.env_name)
         if self.env == _lib.ENV_CUBE3:
-            return _lib.idastar_cube3(root, self.pdb.patterns, self.pdb.tables, max_nodes)
+            return _lib.idastar_cube3(root, self.pdb.patterns, self.pdb.tables, max_nodes, sym=self.pdb.sym)
         return _lib.idastar_npuzzle(self.dim, root, self.pdb.partition, self.pdb.tables, max_nodes, reflect=self.pdb.reflect)
 
 
@@ -93,7 +97,9 @@ def build_parser() -> ArgumentParser:
     parser.add_argument('--model_dir', type=str, required=True,
                         help="pdb:SPEC, as for astar.py: a preset (puzzle8 4-4; puzzle15 5-5-5, 6-6-3; puzzle24 6-6-6-6; auto; cube3 "
                              "corners, korf, korf7) or explicit groups.  On a sliding puzzle SPEC+reflect searches on the reflected "
-                             "look-up (at most 4 patterns).  Built on the GPU at start-up")
+                             "look-up (at most 4 patterns); on cube3 SPEC+sym searches on the symmetric look-ups, every table read again at "
+                             "the state's images under the cube's 48 symmetries (SPEC+sym:N: the first N images of each pattern).  "
+                             "Built on the GPU at start-up")
     parser.add_argument('--results_dir', type=str, required=True, help="Directory to save results")
     parser.add_argument('--start_idx', type=int, default=0, help="")
     parser.add_argument('--max_nodes', type=int, default=None,

@@ -4,7 +4,11 @@ over corner cubies and over subsets of the edge cubies, combined by max — an e
 
 A set is a tuple of patterns, a pattern a (kind, cubies) pair; `parse_cube3_pdb_spec` turns a preset name or explicit groups
 ("c0,c1,c2/e0,e1,e2,e3") into one and refuses what cannot be built, before any device work.  Patterns may share cubies: the
-max of admissible tables is admissible."""
+max of admissible tables is admissible.
+
+`<spec>+sym` reads every table again at the state's conjugates under the cube's 48 symmetries, each pattern at all of its distinct
+images, and takes the largest value (include/dca.h "Symmetric look-ups"): no table bytes, the same tables.  `<spec>+sym:N` takes
+the first N images of each pattern; `+sym:1` is the plain heuristic."""
 from __future__ import annotations
 
 import re
@@ -28,6 +32,50 @@ PRESETS: Dict[str, PatternSet] = {
 }
 MAX_K = 8
 MAX_TABLE_BYTES = 1 << 34  # one pattern's table (the library's own limit)
+SYM_SUFFIX = "+sym"  # a spec that ends in it, or in +sym:N, asks for the symmetric look-ups; the tables are the same
+SYM_ALL = _lib.CUBE3_SYMS
+
+
+def split_sym(spec: str) -> Tuple[str, int]:
+    """A spec string -> (the spec parse_cube3_pdb_spec takes, N): N = 0 without a suffix, 48 for "+sym", N for "+sym:N" with N in
+    1..48.  ValueError for any other use of '+' (a +reflect suffix among them: the parser words that refusal)."""
+    spec = str(spec).strip()
+    base, plus, suffix = spec.partition("+")
+    if not plus:
+        return spec, 0
+    m = re.fullmatch(r"sym(?::\s*(-?\d+))?", suffix.strip().lower())
+    if not m:
+        if suffix.strip().lower().startswith("sym"):
+            raise ValueError("cube3 pattern database %r: the suffix is %s or %s:N with N in 1..%d, once" % (spec, SYM_SUFFIX, SYM_SUFFIX, SYM_ALL))
+        parse_cube3_pdb_spec(spec)  # raises, in the parser's words: cube3 has no other suffix
+        raise ValueError("cube3 pattern database %r: the only suffix is %s or %s:N" % (spec, SYM_SUFFIX, SYM_SUFFIX))
+    sym = SYM_ALL if m.group(1) is None else int(m.group(1))
+    if sym == 0:
+        raise ValueError("cube3 pattern database %r: +sym:N takes N in 1..%d images of each pattern, not 0" % (spec, SYM_ALL))
+    return base.strip(), check_sym(sym)
+
+
+def check_sym(sym) -> int:
+    sym = int(sym or 0)
+    if not 0 <= sym <= SYM_ALL:
+        raise ValueError("+sym:N takes N in 1..%d images of each pattern, not %d" % (SYM_ALL, sym))
+    return sym
+
+
+def sym_suffix(sym: int) -> str:
+    return "" if not sym else SYM_SUFFIX if sym == SYM_ALL else "%s:%d" % (SYM_SUFFIX, sym)
+
+
+def sym_lookups(patterns: PatternSet, sym: int) -> int:
+    """Look-ups of a pattern set under +sym:N: per pattern min(N, its distinct images), as the library counts them (no device)."""
+    return sum(len(_lib.cube3_sym_images(kind, g, sym)[0]) for kind, g in patterns)
+
+
+def check_sym_lookups(patterns: PatternSet, sym: int) -> None:
+    n = sym_lookups(patterns, sym) if sym else 0
+    if n > _lib.CUBE3_SYM_MAX_LOOKUPS:
+        raise ValueError("cube3 pattern database %s%s: %d look-ups, over the cap of %d: take fewer images of each pattern with %s:N"
+                         % (spec_of(patterns), sym_suffix(sym), n, _lib.CUBE3_SYM_MAX_LOOKUPS, SYM_SUFFIX))
 
 
 def pattern_bytes(kind: int, k: int) -> int:
@@ -94,13 +142,21 @@ class Cube3PatternDatabase(_TableSet):
     env_name = "cube3"
     _engine_rows = "network-input"
 
-    def __init__(self, patterns):
+    def __init__(self, patterns, sym: int = 0):
         super().__init__()
-        self.patterns = parse_cube3_pdb_spec(patterns) if isinstance(patterns, str) else check_patterns(patterns)
+        sym = check_sym(sym)
+        if isinstance(patterns, str):
+            patterns, suffix = split_sym(patterns)
+            self.patterns = parse_cube3_pdb_spec(patterns)
+            sym = suffix or sym
+        else:
+            self.patterns = check_patterns(patterns)
+        self.sym = sym  # 0: plain; N: the first N images of each pattern (48: all)
+        check_sym_lookups(self.patterns, self.sym)
 
     @property
     def spec(self) -> str:
-        return spec_of(self.patterns)
+        return spec_of(self.patterns) + sym_suffix(self.sym)
 
     def _table_bytes(self) -> List[int]:
         return table_bytes(self.patterns)
@@ -110,7 +166,7 @@ class Cube3PatternDatabase(_TableSet):
 
     def heuristic(self, states: torch.Tensor, row_kind: int = _lib.ROWS_STATE) -> torch.Tensor:
         self._ready("build() or load() first")
-        return _lib.cube3_pdb_eval(states, row_kind, self.patterns, self.tables)
+        return _lib.cube3_pdb_eval(states, row_kind, self.patterns, self.tables, sym=self.sym)
 
     def _engine_heuristic(self, states: torch.Tensor) -> torch.Tensor:
         return self.heuristic(states, _lib.ROWS_NNET)  # BwasEngine.step / solve hand a cube3 closure the rows sticker // 9

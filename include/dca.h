@@ -324,6 +324,47 @@ int dca_cube3_pdb_eval(const uint8_t* states /*[n, ld]*/, int64_t n, int64_t ld,
                        const int* ks /*host [num_patterns]*/, const uint8_t* const* tables /*host [num_patterns] of device pointers*/,
                        float* out /*[n]*/, void* stream);
 
+/* Symmetric look-ups (`pdb:<spec>+sym`, `pdb:<spec>+sym:N`; cube3 only): every rotation and reflection sigma of the cube is an
+ * automorphism of the move graph that fixes the goal, so d(s) = d(sigma s sigma^-1), and table_Q read at the conjugate of s is an
+ * admissible bound on d(s) for every sigma — consistent too, because one move of s is one move of the conjugate.  The same
+ * tables, read up to 48 times, no table bytes.  Everything below is derived from the move table, once, at first use; a
+ * derivation that fails its own checks (every conjugated move is a move; the 48 move maps are distinct; no location map
+ * contradicts itself) makes every symmetric entry point return DCA_E_STATE.
+ *   symmetries   two faces (colours, position / 9) are opposite exactly when no cubie carries both: 0/1, 2/3, 4/5.  A symmetry is
+ *                a face map phi, a permutation of the 6 faces with phi(opposite(f)) = opposite(phi(f)); there are 3! * 2^3 =
+ *                DCA_CUBE3_SYMS = 48.  ORDER: ascending lexicographic order of (phi(0), phi(1), ..., phi(5)); symmetry 0 is the
+ *                identity.  sigma, its sticker permutation, sends the position on face f of the cubie with colour set F to the
+ *                position on face phi(f) of the cubie with colour set phi(F) (a centre: F = {f}).  pi, its move map, is the move
+ *                with sigma o P_a o sigma^-1 = P_pi(a); as gather tables (dca_cube3_perm_table) perm[pi(a)][sigma(i)] =
+ *                sigma(perm[a][i]).  24 symmetries keep a move's direction bit, the reflections flip it.  The conjugate S' of a
+ *                row S of sticker ids is S'[sigma(p)] = sigma(S[p]); conjugation commutes with the moves through pi.
+ *   look-up      for a pattern Q = (q_0 ... q_{k-1}) the table byte at the conjugated row needs no conjugated row: it is the
+ *                table read at index rule(R_{sigma,c_0}[location(c_0)], ..., R_{sigma,c_{k-1}}[location(c_{k-1})]) with the
+ *                SOURCE cubies c_j = sigma^-1(q_j) (sigma as a map of cubies, by colour sets) and the location maps R_{sigma,c},
+ *                24 -> 24, fixed by R[home(c)] = home(sigma(c)) and R[move_a(l)] = move_pi(a)(R[l]).
+ *   images       a pattern's images are its DISTINCT source cubie sets {c_j}, in the symmetries' order — the pattern itself
+ *                (the identity) first.  Two symmetries with the same set read equal values; the first one stands for the set.
+ *                max_images = N in 1..48 takes the first min(N, distinct) images of EACH pattern; 48 takes all.  The look-up
+ *                list is pattern 0's images, then pattern 1's, ...  A list of more than DCA_CUBE3_SYM_MAX_LOOKUPS = 64 look-ups
+ *                is refused, the message naming the cap and `+sym:N`.  Six- and seven-edge patterns have 24 images, all eight
+ *                corners one: `korf` and `korf7` with every image are 1 + 24 + 24 = 49 look-ups.
+ *   value        the largest table byte over the list.  max_images = 1 is dca_cube3_pdb_eval's value, bit for bit; the value
+ *                never decreases with max_images.  The any-bytes rule holds as above: a location is < 24 whatever the row's
+ *                bytes are, so every map read is inside its 24-byte row, a mapped location is < 24, and the rank clamps its
+ *                digits.
+ * dca_cube3_pdb_eval_sym: dca_cube3_pdb_eval with that value; the same parameters and refusals, plus max_images outside 1..48
+ * and the cap.  The list (13.8 KB) is kept in device memory by the library: the FIRST call with a new pattern set or new table
+ * addresses allocates and copies it (hipMalloc, hipMemcpy: blocking the host, and NOT allowed under a stream capture — make
+ * a set's first call before capturing); later calls make no HIP call but the launch.  The library keeps eight lists per
+ * entry-point family and frees the oldest for a ninth (hipFree: waits for the device, not allowed under a capture either);
+ * more than eight distinct (set, tables) combinations in use by concurrent host threads are not supported. */
+#define DCA_CUBE3_SYMS 48
+#define DCA_CUBE3_SYM_MAX_LOOKUPS 64
+int dca_cube3_pdb_eval_sym(const uint8_t* states /*[n, ld]*/, int64_t n, int64_t ld, int row_kind, int num_patterns,
+                           const int* kinds /*host [num_patterns]*/, const uint8_t* cubies /*host*/,
+                           const int* ks /*host [num_patterns]*/, const uint8_t* const* tables /*host [num_patterns] of device pointers*/,
+                           int max_images, float* out /*[n]*/, void* stream);
+
 /* Exact LightsOut heuristic (csrc/dca_lightsout_exact.hip; `--env lightsout7 --model_dir exact:gf2`): the true distance of any
  * state, by linear algebra over GF(2) instead of a table.
  *   algebra      pressing cell a flips a fixed set of cells, presses commute, and pressing a cell twice is the identity.  A
@@ -417,6 +458,23 @@ int dca_idastar_cube3(const uint8_t* root /*host [54]*/, int num_patterns, const
                       const uint8_t* const* tables /*host [num_patterns] of device pointers*/, int64_t max_nodes, int* status, int* length,
                       uint8_t* moves /*host [moves_cap]*/, int moves_cap, int* num_thresholds, int* thresholds /*host [thresholds_cap]*/,
                       int64_t* nodes_per_threshold /*host [thresholds_cap]*/, int thresholds_cap, int64_t* total_nodes, void* stream);
+/* dca_idastar_cube3 on the symmetric look-ups ("Symmetric look-ups" above): h = the largest byte over the look-up list of
+ * (pattern set, max_images).  Same state, moves, pruning rules, work items, counting, budget and ending.  The root is
+ * unsolvable if ANY look-up's byte at the root is 0xFE or 0xFF.  A lane may stop reading the list at the first value v with
+ * g + 1 + v > T: the child is pruned exactly when it is under the full maximum, but the f it records for the next threshold may
+ * then be smaller than its exact f.  The contract, whatever the evaluation order:
+ *   - the thresholds increase strictly; the first is h(root) over all look-ups, the last of a solved search the solution length;
+ *   - every threshold of the exact search (h = the full maximum everywhere) occurs among them;
+ *   - a completed threshold's node count is that of the tree at that threshold under the full maximum: a property of the
+ *     tree, not of the schedule, the split into work items or the order of the look-ups.
+ * Same parameters, outputs and refusals as dca_idastar_cube3, plus max_images outside 1..48 and a list over
+ * DCA_CUBE3_SYM_MAX_LOOKUPS.  max_images = 1 runs dca_idastar_cube3's thresholds and completed counts. */
+int dca_idastar_cube3_sym(const uint8_t* root /*host [54]*/, int num_patterns, const int* kinds /*host [num_patterns]*/,
+                          const uint8_t* cubies /*host*/, const int* ks /*host [num_patterns]*/,
+                          const uint8_t* const* tables /*host [num_patterns] of device pointers*/, int max_images, int64_t max_nodes,
+                          int* status, int* length, uint8_t* moves /*host [moves_cap]*/, int moves_cap, int* num_thresholds,
+                          int* thresholds /*host [thresholds_cap]*/, int64_t* nodes_per_threshold /*host [thresholds_cap]*/,
+                          int thresholds_cap, int64_t* total_nodes, void* stream);
 
 /* state hash (a9). The reference's hash VALUES are process-randomised SipHash (cube3.py:17-21)
  * or unpinned boost::hash_range (parallel_weighted_astar.cpp:104-111); what is pinned is key

@@ -75,6 +75,28 @@ int dca_idastar_host_reflected(int dim, const uint8_t* root, int num_patterns, c
 int dca_pdb_eval_host(int dim, const uint8_t* states /*host [n, ld]*/, int64_t n, int64_t ld, int num_patterns,
                       const uint8_t* tiles /*host*/, const int* ks /*host [num_patterns]*/,
                       const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int reflect, float* out /*host [n]*/);
+/* Host-only: the search of dca_idastar_cube3_sym on the CPU from HOST tables, through the code the kernel compiles.  Same
+ * refusals, same outputs; the thresholds and the completed iterations' node counts equal the device's. */
+int dca_idastar_host_sym(const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
+                         const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int max_images, int64_t max_nodes,
+                         int* status, int* length, uint8_t* moves, int moves_cap, int* num_thresholds, int* thresholds,
+                         int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes);
+/* Host-only: what dca_cube3_pdb_eval_sym computes, in a plain loop on the CPU through the row load and the row value the kernel
+ * compiles.  states, tables and out are HOST memory; the refusals are those of dca_cube3_pdb_eval_sym. */
+int dca_cube3_pdb_eval_sym_host(const uint8_t* states /*host [n, ld]*/, int64_t n, int64_t ld, int row_kind, int num_patterns,
+                                const int* kinds, const uint8_t* cubies, const int* ks,
+                                const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int max_images,
+                                float* out /*host [n]*/);
+/* Host-only: the derived symmetries (dca.h "Symmetric look-ups"), in their documented order: sticker_perms [48][54], sigma as
+ * position -> position; move_maps [48][12], pi.  DCA_E_STATE where the derivation failed its checks. */
+int dca_cube3_sym_tables(uint8_t* sticker_perms /*host [48*54]*/, uint8_t* move_maps /*host [48*12]*/);
+/* Host-only: the images of one pattern as the look-up list holds them, the first min(max_images, distinct) of them:
+ * *num_images; per image i the symmetry that stands for it, syms[i]; its source cubies, sources[i*8 + j] for j < k; and their
+ * location maps, maps[(i*8 + j)*24 + l].  syms, sources and maps may each be NULL; room for 48 images.  The refusals of a
+ * pattern (dca_cube3_pdb_bytes, cubies) and of max_images. */
+int dca_cube3_sym_images(int kind, const uint8_t* cubies /*host [k]*/, int k, int max_images, int* num_images,
+                         uint8_t* syms /*host [48] or NULL*/, uint8_t* sources /*host [48*8] or NULL*/,
+                         uint8_t* maps /*host [48*8*24] or NULL*/);
 /* test hook, process-wide: every iteration of the searches above splits its work into items of `depth` prefix moves (a
  * family's own limit where depth is above it: 15 for the puzzles, 6 for cube3); -1 (the default) = chosen from the previous
  * iteration's node count.  Results never depend on it.  DCA_E_BADARG outside -1..15.

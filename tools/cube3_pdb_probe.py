@@ -11,6 +11,9 @@ first leg that does not exit 0 (nothing is started on a device after a leg has f
   search  korf at --weight 1 --semantics cpp, batch 1000, `--max_nodes auto`, on roots taken from the shipped optimal paths at
           remaining distance 8 .. 13: length found against the known distance, nodes generated, seconds; the same under
           builtin:zero while it still fits.
+  eval_sym  dca_cube3_pdb_eval_sym on korf with the first N images of every pattern, N in 1, 2, 4, 8, 24 and all, next to the plain
+          eval on the same rows in the same process: the cost per row against the plain eval.  `--legs eval_sym --append --out
+          profiles/idastar_sym_probe.txt` adds it to the symmetric searches' record.
 No threshold is set on any time: the numbers are recorded, not met."""
 import argparse
 import os
@@ -28,7 +31,7 @@ from deepcubea_amd import _lib  # noqa: E402
 from deepcubea_amd.search_methods.engine import BwasEngine  # noqa: E402
 from deepcubea_amd.utils.cube3_pdb import PRESETS, Cube3PatternDatabase, spec_of  # noqa: E402
 
-LEG_TIMEOUT_S = {"build": 420, "eval": 150, "search": 420}
+LEG_TIMEOUT_S = {"build": 420, "eval": 150, "search": 420, "eval_sym": 150}
 CORNER_HISTOGRAM = [1, 12, 114, 924, 6539, 39528, 199926, 806136, 2761740, 8656152, 22334112, 32420448, 18780864, 2166720, 6624]
 
 
@@ -103,6 +106,21 @@ def eval_leg():
               % (rows, med, low, rows / (med * 1e-6)), flush=True)
 
 
+def eval_sym_leg():
+    from deepcubea_amd.utils.cube3_pdb import sym_lookups
+    korf = Cube3PatternDatabase("korf").build()
+    for rows in (131072, 245760):
+        X = torch.from_numpy(scramble_rows(rows) // 9).cuda()
+        out = torch.empty(rows, dtype=torch.float32, device="cuda")
+        plain, low = median_us(lambda: _lib.cube3_pdb_eval(X, _lib.ROWS_NNET, korf.patterns, korf.tables, out=out))
+        print("eval   cube3 korf         %7d rows   3 look-ups  median %7.1f us  min %7.1f us  %6.3f ns/row" % (rows, plain, low, plain * 1e3 / rows),
+              flush=True)
+        for n in (1, 2, 4, 8, 24, 48):
+            med, low = median_us(lambda: _lib.cube3_pdb_eval(X, _lib.ROWS_NNET, korf.patterns, korf.tables, out=out, sym=n))
+            print("eval   cube3 korf+sym:%-3d %7d rows  %2d look-ups  median %7.1f us  min %7.1f us  %6.3f ns/row  x %.2f of the plain eval"
+                  % (n, rows, sym_lookups(korf.patterns, n), med, low, med * 1e3 / rows, med / plain), flush=True)
+
+
 def path_roots(distances, instances):
     g = np.load(os.path.join(ROOT, "tests", "golden", "golden.npz"))
     perm = _lib.lib().dca_cube3_perm_table()
@@ -150,12 +168,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cube3_pdb_probe.txt"))
     ap.add_argument("--legs", default="build,eval,search")
+    ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it")
     ap.add_argument("--leg", default=None, help="run one leg in this process (what the driver starts under `timeout`)")
     args = ap.parse_args()
     if args.leg:
         _lib.require_gpu()
         print("probe leg %s on %s" % (args.leg, torch.cuda.get_device_name(0)), flush=True)
-        {"build": build_leg, "eval": eval_leg, "search": search_leg}[args.leg]()
+        {"build": build_leg, "eval": eval_leg, "search": search_leg, "eval_sym": eval_sym_leg}[args.leg]()
         return 0
     lines = ["$ python tools/cube3_pdb_probe.py --legs %s" % args.legs]
     rc = 0
@@ -173,7 +192,7 @@ def main():
             rc = child.returncode
             break
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
+    with open(args.out, "a" if args.append else "w") as f:
         f.write("\n".join(lines) + "\n")
     return rc
 

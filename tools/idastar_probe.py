@@ -13,6 +13,11 @@ first leg that does not exit 0 (nothing is started on a device after a leg has f
              the same states and settings with and without the reflected look-up (`+reflect`), on the same built tables in one
              process: a plain run, then a reflected one, then both restricted to the states both ran and solved.  Written to
              profiles/idastar_reflect_probe.txt with `--legs resources,puzzle15_reflect,puzzle24_reflect --out ...`.
+  cube3_sym_korf, cube3_sym_korf7
+             the shipped cube3 states in ascending optimal length with the plain set and with `+sym:N` for N in 2, 4, 8, 24, on
+             the same built tables in one process, --seconds of search per configuration; then every configuration restricted
+             to the states all of them ran and solved, as ratios to the plain run.  Written to profiles/idastar_sym_probe.txt
+             with `--legs resources,cube3_sym_korf,cube3_sym_korf7 --seconds 60 --out ...`.
 A state's node budget is what the rate measured so far gets through in --state_seconds; a state that runs out of it is listed.
 The rate of a family is nodes over seconds summed over its searches of at least 0.05 s (shorter ones time the launches, not the
 kernel).  No threshold is set on any time or rate: the numbers are recorded, not met."""
@@ -28,7 +33,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-LEG_TIMEOUT_S = {"resources": 120, "puzzle15": 500, "puzzle24": 500, "cube3": 700, "puzzle15_reflect": 500, "puzzle24_reflect": 700}
+LEG_TIMEOUT_S = {"resources": 120, "puzzle15": 500, "puzzle24": 500, "cube3": 700, "puzzle15_reflect": 500, "puzzle24_reflect": 700,
+                 "cube3_sym_korf": 800, "cube3_sym_korf7": 800}
+SYM_IMAGES = (2, 4, 8, 24)
 FIRST_BUDGET = 1 << 31  # nodes, until a rate is known
 
 
@@ -167,6 +174,34 @@ def cube3_leg(seconds, state_seconds, verbose):
         del pdb
 
 
+def cube3_sym_leg(spec, seconds, state_seconds, verbose):
+    """The tables built once; the plain search and the searches on the first N images of every pattern over the same states in
+    the same order, compared on the states every configuration solved."""
+    from deepcubea_amd.search_methods.idastar import IDAStar
+    from deepcubea_amd.utils.cube3_pdb import Cube3PatternDatabase, sym_lookups, sym_suffix
+    z = golden()
+    states, lens = z["cube3_test_states"], z["cube3_test_opt_len"].astype(int)
+    ids = np.argsort(lens, kind="stable")
+    t0 = time.time()
+    pdb = Cube3PatternDatabase(spec).build()
+    print("cube3 pdb:%s: %d bytes built in %.2f s" % (spec, pdb.bytes, time.time() - t0), flush=True)
+    runs = {}
+    for n in (0,) + SYM_IMAGES:
+        pdb.sym = n  # the same tables: the suffix changes the look-ups, not the bytes
+        label = "cube3 %s%s" % (spec, sym_suffix(n))
+        print("  %-18s %d look-ups a node at the most" % (label, sym_lookups(pdb.patterns, n) if n else len(pdb.patterns)))
+        runs[n] = run_states(IDAStar("cube3", pdb), label, states[ids], lens[ids], ids, seconds, state_seconds, verbose)[1]
+    both = [i for i in runs[0] if all(i in r and r[i][0] for r in runs.values())]
+    base_nodes, base_secs = sum(runs[0][i][1] for i in both), sum(runs[0][i][2] for i in both)
+    print("  cube3 %s, the %d states every configuration ran and solved (optimal length %s):"
+          % (spec, len(both), "%d .. %d" % (min(lens[both]), max(lens[both])) if both else "-"))
+    for n, r in runs.items():
+        nodes, secs = sum(r[i][1] for i in both), sum(r[i][2] for i in both)
+        print("  %-18s states run %3d solved %3d | nodes %.4g (x %.4f of plain)  seconds %.3f (x %.4f of plain)  %.3g nodes/s"
+              % (spec + sym_suffix(n), len(r), sum(1 for v in r.values() if v[0]), nodes, nodes / base_nodes, secs, secs / base_secs,
+                 nodes / secs), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "idastar_probe.txt"))
@@ -189,6 +224,8 @@ def main():
             reflect_leg("puzzle24", ("6-6-6-6",), args.seconds, args.state_seconds, args.verbose, True)
         elif args.leg == "cube3":
             cube3_leg(args.seconds, args.state_seconds, args.verbose)
+        elif args.leg in ("cube3_sym_korf", "cube3_sym_korf7"):
+            cube3_sym_leg(args.leg.rsplit("_", 1)[1], args.seconds, args.state_seconds, args.verbose)
         else:
             raise ValueError("unknown leg %r" % args.leg)
         return
