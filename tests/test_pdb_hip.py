@@ -21,8 +21,9 @@ P8_ONES = tuple((t,) for t in range(1, 9))
 P15_33 = ((1, 2, 5), (12, 15, 14))
 P24_2 = ((7, 24),)
 P48_2 = ((20, 48),)
+P35_2 = ((8, 35),)
 P24_TRIPLES = tuple((a, a + 1, a + 2) for a in range(1, 25, 3))
-SHAPE_SETS = {9: (3, P8_44), 16: (4, P15_33), 25: (5, P24_2), 49: (7, P48_2)}
+SHAPE_SETS = {9: (3, P8_44), 16: (4, P15_33), 25: (5, P24_2), 36: (6, P35_2), 49: (7, P48_2)}
 
 
 @pytest.fixture(scope="module")
@@ -61,7 +62,8 @@ def perms(n, D, seed):
 
 # ------------------------------------------------------------------------------------------------ 1. build
 @pytest.mark.parametrize("dim,partition,entries,valid", [
-    (3, P8_44, 59049, 15120), (3, P8_35, 531441, 60480), (4, P15_33, 65536, 43680), (5, P24_2, 15625, 13800), (7, P48_2, 117649, 110544)])
+    (3, P8_44, 59049, 15120), (3, P8_35, 531441, 60480), (4, P15_33, 65536, 43680), (5, P24_2, 15625, 13800), (7, P48_2, 117649, 110544),
+    (6, P35_2, 46656, 42840)])
 def test_build_byte_for_byte_against_the_host_reference(L, dim, partition, entries, valid):
     tables = built(L, dim, partition)
     torch.cuda.synchronize()
@@ -118,7 +120,7 @@ def test_the_eight_tile_pattern_is_the_exact_distance(L, table8):
 
 
 # ------------------------------------------------------------------------------------------------ 3. eval shapes, any bytes
-@pytest.mark.parametrize("D", [9, 16, 25, 49])
+@pytest.mark.parametrize("D", [9, 16, 25, 36, 49])
 def test_eval_shapes_strides_and_any_bytes(L, D):
     dim, partition = SHAPE_SETS[D]
     host = [ref.host_table(dim, g) for g in partition]

@@ -82,9 +82,9 @@ def swap_table(dim):
 
 
 def state_h(dim, partition, tables, reflect):
-    """h of one state (a tuple of tiles) by the header's index rule: the plain sum, or the larger of it and the reflected sum."""
+    """h of one state (a tuple of tiles) by the header's index rule: the plain sum, or the larger of it and the reflected sum.
+    A table is anything that gives its byte at an integer index: an array, or an object that reads a table kept elsewhere."""
     N = dim * dim
-    tables = [np.asarray(t) for t in tables]
 
     def h(state):
         pos = [0] * N
@@ -239,7 +239,7 @@ def test_a_self_mirrored_partition_gains_nothing():
 
 
 # ------------------------------------------------------------------------------------------------ any bytes
-@pytest.mark.parametrize("dim", [3, 4, 5, 7])
+@pytest.mark.parametrize("dim", [3, 4, 5, 6, 7])
 def test_any_bytes_rule_with_random_tables(dim):
     from deepcubea_amd import _lib
     N = dim * dim

@@ -76,7 +76,7 @@ def test_kernel_eval_on_the_whole_puzzle8_space(L, pdb8):
     assert int(got.sum()) == 3589500
 
 
-@pytest.mark.parametrize("dim", [3, 4, 5, 7])
+@pytest.mark.parametrize("dim", [3, 4, 5, 6, 7])
 def test_any_bytes_both_load_widths(L, dim):
     """Rows of random bytes on random tables: an aligned base with a row stride that is a multiple of 4 (word loads), with
     ld = N, and a base one byte off with ld = N + 3 (byte loads)."""
