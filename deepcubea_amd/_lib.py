@@ -72,6 +72,7 @@ _SIGNATURES = {
     "dca_cube3_pdb_build": "i ipippp",
     "dca_cube3_pdb_eval": "i plliipppppp",
     "dca_cube3_pdb_eval_sym": "i plliippppipp",
+    "dca_cube3_pdb_eval_dual": "i plliippppipp",
     "dca_lightsout_exact_matrix": "i ip",
     "dca_lightsout_exact_eval": "i ipllpp",
     "dca_lightsout_exact_solve": "i ipllpp",
@@ -79,6 +80,7 @@ _SIGNATURES = {
     "dca_idastar_npuzzle_reflected": "i ipippplpppipppipp",
     "dca_idastar_cube3": "i pipppplpppipppipp",
     "dca_idastar_cube3_sym": "i pippppilpppipppipp",
+    "dca_idastar_cube3_dual": "i pippppilpppipppipp",
     "dca_engine_create": "i piidilii",
     "dca_engine_create_multi": "i piidiliii",
     "dca_engine_num_instances": "i p",
@@ -157,6 +159,9 @@ _SIGNATURES = {
     "dca_pdb_eval_host": "i ipllipppip",
     "dca_idastar_host_sym": "i pippppilpppipppip",
     "dca_cube3_pdb_eval_sym_host": "i plliippppip",
+    "dca_idastar_host_dual": "i pippppilpppipppip",
+    "dca_cube3_pdb_eval_dual_host": "i plliippppip",
+    "dca_cube3_inverse_locs": "i pip",
     "dca_cube3_sym_tables": "i pp",
     "dca_cube3_sym_images": "i ipiipppp",
     "dca_idastar_set_prefix": "i i",
@@ -630,11 +635,16 @@ def cube3_pdb_build(kind: int, cubies, table: Optional[torch.Tensor] = None):
     return _pdb_build("dca_cube3_pdb_build", cube3_pdb_bytes, kind, cubies, table)
 
 
-def cube3_pdb_eval(states: torch.Tensor, row_kind: int, patterns, tables, out: Optional[torch.Tensor] = None, sym: int = 0) -> torch.Tensor:
+def cube3_pdb_eval(states: torch.Tensor, row_kind: int, patterns, tables, out: Optional[torch.Tensor] = None, sym: int = 0,
+                   dual: bool = False) -> torch.Tensor:
     """Max of the patterns' table bytes per row -> f32 [n].  patterns: [(kind, cubies), ...]; states: uint8 device rows
     [n, >= 54] with unit byte stride (a strided view is fine); ANY bytes are in bounds (include/dca.h, the any-bytes rule).
-    sym = N in 1..48: the max over the first N images of every pattern as well (include/dca.h, "Symmetric look-ups"); 0: plain."""
+    sym = N in 1..48: the max over the first N images of every pattern as well (include/dca.h, "Symmetric look-ups"); 0: plain.
+    dual: the larger of that value at the row and at its inverse (include/dca.h, "Dual look-ups"); without sym, of the plain value."""
     groups, kinds = [g for _, g in patterns], [kind for kind, _ in patterns]
+    if dual:
+        return _pdb_eval("cube3_pdb_eval", "dca_cube3_pdb_eval_dual", states, 54, groups, kinds, _cube3_table_bytes, tables, out,
+                         lambda s, n, ld, m, k, c, ks, t, *rest: lib().dca_cube3_pdb_eval_dual(s, n, ld, row_kind, m, k, c, ks, t, int(sym or 1), *rest))
     if not sym:
         return _pdb_eval("cube3_pdb_eval", "dca_cube3_pdb_eval", states, 54, groups, kinds, _cube3_table_bytes, tables, out,
                          lambda s, n, ld, m, *rest: lib().dca_cube3_pdb_eval(s, n, ld, row_kind, m, *rest))
@@ -645,8 +655,8 @@ def cube3_pdb_eval(states: torch.Tensor, row_kind: int, patterns, tables, out: O
 CUBE3_SYMS, CUBE3_SYM_MAX_LOOKUPS = 48, 64  # include/dca.h
 
 
-def cube3_pdb_eval_host(rows, row_kind: int, patterns, tables, sym: int = 1) -> np.ndarray:
-    """cube3_pdb_eval(sym=...) on the CPU (include/dca_debug.h: the kernel's own row value in a plain loop) -> float32 [n].
+def cube3_pdb_eval_host(rows, row_kind: int, patterns, tables, sym: int = 1, dual: bool = False) -> np.ndarray:
+    """cube3_pdb_eval(sym=..., dual=...) on the CPU (include/dca_debug.h: the kernel's own row value in a plain loop) -> float32 [n].
     rows: a uint8 host array [n, >= 54]; tables: one uint8 host array per pattern.  sym = 1 is the plain value.  No device needed."""
     rows = np.asarray(rows)
     if rows.dtype != np.uint8 or rows.ndim != 2:
@@ -655,8 +665,21 @@ def cube3_pdb_eval_host(rows, row_kind: int, patterns, tables, sym: int = 1) -> 
     _table_sizes("cube3_pdb_eval_host", [_cube3_table_bytes(kind, len(g)) for kind, g in patterns], tables, True)
     (kinds, ids, ks), ptrs, _keep = _idastar_set([g for _, g in patterns], [kind for kind, _ in patterns], tables, True)
     out = np.zeros(len(rows), np.float32)
-    check(lib().dca_cube3_pdb_eval_sym_host(rows.ctypes.data_as(C.c_void_p), len(rows), rows.shape[1], row_kind, len(patterns), kinds, ids,
-                                            ks, ptrs, int(sym), out.ctypes.data_as(C.c_void_p)), "dca_cube3_pdb_eval_sym_host")
+    symbol = "dca_cube3_pdb_eval_dual_host" if dual else "dca_cube3_pdb_eval_sym_host"
+    check(getattr(lib(), symbol)(rows.ctypes.data_as(C.c_void_p), len(rows), rows.shape[1], row_kind, len(patterns), kinds, ids,
+                                 ks, ptrs, int(sym), out.ctypes.data_as(C.c_void_p)), symbol)
+    return out
+
+
+def cube3_inverse_locs(rows, row_kind: int) -> np.ndarray:
+    """The location words of the inverse of each row by the inversion rule (include/dca.h, "Dual look-ups"; the replacing form) ->
+    uint64 [n, 2]: the corner word and the edge word, 5 bits a cubie.  rows: uint8 host [n, >= 54], any bytes.  No device needed."""
+    rows = np.ascontiguousarray(rows)
+    if rows.dtype != np.uint8 or rows.ndim != 2 or rows.shape[1] < 54:
+        raise ValueError("cube3_inverse_locs: rows must be a uint8 host array [n, >= 54]")
+    out = np.zeros((len(rows), 2), np.uint64)
+    for i in range(len(rows)):
+        check(lib().dca_cube3_inverse_locs(rows[i].ctypes.data_as(C.c_void_p), row_kind, out[i].ctypes.data_as(C.c_void_p)), "dca_cube3_inverse_locs")
     return out
 
 
@@ -787,11 +810,16 @@ def idastar_npuzzle(dim: int, root, partition, tables, max_nodes: int, reflect: 
                     root, max(dim, 0) ** 2, max_nodes)
 
 
-def idastar_cube3(root, patterns, tables, max_nodes: int, sym: int = 0) -> dict:
+def idastar_cube3(root, patterns, tables, max_nodes: int, sym: int = 0, dual: bool = False) -> dict:
     """Optimal solution of one cube3 root (54 sticker ids) by IDA* on the device tables of `patterns` [(kind, cubies), ...].
-    sym = N in 1..48: h is the max over the first N images of every pattern (include/dca.h, "Symmetric look-ups"); 0: plain."""
+    sym = N in 1..48: h is the max over the first N images of every pattern (include/dca.h, "Symmetric look-ups"); 0: plain.
+    dual: h is the larger of that value at the state and at its inverse (include/dca.h, "Dual look-ups")."""
     _table_sizes("idastar_cube3", [_cube3_table_bytes(kind, len(g)) for kind, g in patterns], tables, False)
     (kinds, ids, ks), ptrs, _keep = _idastar_set([g for _, g in patterns], [kind for kind, _ in patterns], tables, False)
+    if dual:
+        return _idastar("dca_idastar_cube3_dual", lambda r, n, *out: lib().dca_idastar_cube3_dual(r, len(patterns), kinds, ids, ks, ptrs,
+                                                                                                  int(sym or 1), n, *out, stream_ptr()),
+                        root, 54, max_nodes)
     if sym:
         return _idastar("dca_idastar_cube3_sym", lambda r, n, *out: lib().dca_idastar_cube3_sym(r, len(patterns), kinds, ids, ks, ptrs, int(sym),
                                                                                                 n, *out, stream_ptr()), root, 54, max_nodes)
@@ -799,14 +827,17 @@ def idastar_cube3(root, patterns, tables, max_nodes: int, sym: int = 0) -> dict:
                                                                                     stream_ptr()), root, 54, max_nodes)
 
 
-def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int, reflect: bool = False, sym: int = 0) -> dict:
+def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int, reflect: bool = False, sym: int = 0,
+                 dual: bool = False) -> dict:
     """The same search run sequentially on the CPU from HOST tables (include/dca_debug.h): no device needed.  patterns: the
     partition (puzzles) or [(kind, cubies), ...] (cube3); tables: one uint8 array per pattern.  reflect: the reflected search,
-    sliding puzzles only.  sym = N: the search on the symmetric look-ups, cube3 only."""
+    sliding puzzles only.  sym = N: the search on the symmetric look-ups, dual: on the dual look-ups, cube3 only."""
     if reflect and env != ENV_NPUZZLE:
         raise ValueError("idastar_host: the reflected look-up is defined for the sliding puzzles only")
     if sym and env != ENV_CUBE3:
         raise ValueError("idastar_host: the symmetric look-ups are defined for cube3 only")
+    if dual and env != ENV_CUBE3:
+        raise ValueError("idastar_host: the dual look-ups are defined for cube3 only")
     if env == ENV_CUBE3:
         groups, families = [g for _, g in patterns], [kind for kind, _ in patterns]
         sizes, width = [_cube3_table_bytes(kind, len(g)) for kind, g in patterns], 54
@@ -815,6 +846,9 @@ def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int, ref
         sizes, width = [_pdb_table_bytes(dim, len(g)) for g in patterns], max(dim, 0) ** 2
     _table_sizes("idastar_host", sizes, tables, True)
     (kinds, ids, ks), ptrs, _keep = _idastar_set(groups, families, tables, True)
+    if dual:
+        return _idastar("dca_idastar_host_dual", lambda r, n, *out: lib().dca_idastar_host_dual(r, len(groups), kinds, ids, ks, ptrs,
+                                                                                                int(sym or 1), n, *out), root, width, max_nodes)
     if sym:
         return _idastar("dca_idastar_host_sym", lambda r, n, *out: lib().dca_idastar_host_sym(r, len(groups), kinds, ids, ks, ptrs, int(sym),
                                                                                               n, *out), root, width, max_nodes)

@@ -12,6 +12,8 @@
 //            pattern, that of the state's mirror image, in the other half of the lane's eight, and h the larger of the two sums.
 //   sym      C3SymDomain: cube3's search on the symmetric look-ups (include/dca.h) — the same state and moves, h the largest byte
 //            over a look-up list in global memory, left at the first value that already prunes the child (BOUNDED).
+//   dual     C3DualDomain: the symmetric search with the dual look-ups (include/dca.h) — where the list at the state does not
+//            prune the child, the lane inverts its two words in registers and reads the list again at the inverse state.
 //   work     item i of an iteration names a move prefix of P moves, the mixed-radix digits of i (first move = most significant
 //            digit; cube3: radix 12; puzzles: 4 for the first move, then 3 — a digit picks among the moves that do not undo
 //            the one before).  A lane replays the prefix from the root under the pruning rules and the f <= T test and drops the item
@@ -26,7 +28,7 @@
 //            which ends every other lane's item fetch.
 //
 // Rates are in profiles/idastar_probe.txt; the reflected search against the plain one in profiles/idastar_reflect_probe.txt,
-// the symmetric one in profiles/idastar_sym_probe.txt.
+// the symmetric one in profiles/idastar_sym_probe.txt, the dual one in profiles/idastar_dual_probe.txt.
 #include <mutex>
 #include <type_traits>
 
@@ -247,6 +249,24 @@ struct C3SymDomain : C3Domain {
     }
 };
 
+// cube3 on the dual look-ups (include/dca.h "Dual look-ups"): the symmetric search's state, moves, rules, goal and list; h is
+// the larger of the list's value at the state and at the inverse state.  The inverse is not kept in the lane's state — apply,
+// the undo and the stack are the plain search's — but made from the child's two words where it is needed: only a child that
+// the first pass does not prune pays for it (registers only, the or-only form: the root's slots are checked to be distinct).
+// Admissible, NOT consistent: h of a child may be more than one below its parent's.  IDA* needs admissibility alone.
+struct C3DualDomain : C3SymDomain {
+    struct Ctx : C3SymDomain::Ctx {
+        C3DualPass dual;
+    };
+    static DCA_IDA_INLINE uint32_t h(const State& s, const Ctx& c, uint32_t slack) {
+        const uint32_t best = C3SymDomain::h(s, c, slack);
+        if (best > slack) return best;
+        const uint64_t corner = (c.dual.kinds & 1) ? c3_inverse_locs<DCA_CUBE3_CORNERS, false>(s.corner) : 0ull;
+        const uint64_t edge = (c.dual.kinds & 2) ? c3_inverse_locs<DCA_CUBE3_EDGES, false>(s.edge) : 0ull;
+        return c3_dual_value(c.list, c.n, c.dual.lead, corner, edge, best, slack);
+    }
+};
+
 // ------------------------------------------------------------------------------------------------------------ the frame
 // One lane's share of one iteration (threshold T, prefix depth P, n_items = NM * RADIX^(P-1) < 2^31 work items).  stk: the lane's move
 // stack, word w at stk[w * stride].  budget: the nodes this launch may still count; poll: the nodes between a lane's flushes.
@@ -429,6 +449,24 @@ __global__ __launch_bounds__(kIdaThreads) void ida_cube3_sym_kernel(C3Domain::St
     ida_lane<C3SymDomain>(c, root, ctrl, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
 }
 
+__global__ __launch_bounds__(kIdaThreads) void ida_cube3_dual_kernel(C3Domain::State root, C3DualSet set, C3IdaMoves mt, IdaCtrl* ctrl, uint32_t T,
+                                                                     uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
+    __shared__ uint32_t mvw[2 * 12 * kC3Locs / 4];
+    __shared__ uint32_t stk[C3Domain::STACK_WORDS * kIdaThreads];
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < 2 * 12 * kC3Locs / 4; q++) mvw[q] = mt.w[q];
+    }
+    __syncthreads();
+    C3DualDomain::Ctx c;
+    c.mv = (const uint8_t*)mvw;
+    c.set = nullptr;
+    c.list = set.list;
+    c.n = set.n;
+    c.dual = set.dual;
+    ida_lane<C3DualDomain>(c, root, ctrl, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
+}
+
 // ----------------------------------------------------------------------------------------------------------- host side
 struct IdaOut {
     int* status;
@@ -570,6 +608,25 @@ static int ida_check_cube3_root(const char* who, const uint8_t* root) {
             return DCA_E_BADARG;
         }
         seen |= 1ull << t;
+    }
+    return 0;
+}
+
+// The dual search inverts a lane's words in the or-only form (c3_inverse_locs), which needs every cubie of a kind in a slot of
+// its own.  54 distinct sticker ids need not be that (a corner's sticker on an edge): such a root is no cube state — no move
+// sequence takes it to the goal — and is refused.  The moves permute the slots, so the root's property is every node's.
+static int ida_check_cube3_slots(const char* who, const uint8_t* root) {
+    uint32_t w[14];
+    pdb_load_row<54, 1>(root, w);
+    const uint64_t locs[2] = {c3_row_locs<DCA_CUBE3_CORNERS, DCA_ROWS_STATE>(w), c3_row_locs<DCA_CUBE3_EDGES, DCA_ROWS_STATE>(w)};
+    for (int kind = 0; kind < 2; kind++) {
+        const int n = kind == DCA_CUBE3_CORNERS ? 8 : 12, o = kind == DCA_CUBE3_CORNERS ? 3 : 2;
+        uint32_t seen = 0;
+        for (int q = 0; q < n; q++) seen |= 1u << (((locs[kind] >> (5 * q)) & 31u) / o);
+        if (seen != (1u << n) - 1u) {
+            set_error("bad argument: %s: root: the stickers are no cube state: two %s cubies in one slot", who, kind == DCA_CUBE3_CORNERS ? "corner" : "edge");
+            return DCA_E_BADARG;
+        }
     }
     return 0;
 }
@@ -732,52 +789,77 @@ static C3IdaMoves c3_ida_moves() {
 
 // The search on the symmetric look-ups: ida_cube3 with the list in place of the set.  The list's tables are device memory
 // (on_device) or host memory; the root's h is the full maximum, and the root is dead where ANY look-up's byte is >= 0xFE.
-static int ida_cube3_sym(const uint8_t* root, const C3SymList& list, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
+// dual: the search on the dual look-ups — the root's bytes are those of the list at the state and, behind them, those of the
+// second pass at the inverse state (every look-up that does not name all the cubies of its kind).
+static int ida_cube3_sym(const uint8_t* root, const C3SymList& list, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st,
+                         bool dual = false) {
     uint32_t w[14];
     pdb_load_row<54, 1>(root, w);
     C3Domain::State s0;
     s0.corner = c3_row_locs<DCA_CUBE3_CORNERS, DCA_ROWS_STATE>(w);
     s0.edge = c3_row_locs<DCA_CUBE3_EDGES, DCA_ROWS_STATE>(w);
-    uint64_t root_idx[kC3SymMaxLookups] = {};
-    const uint8_t* tables[kC3SymMaxLookups] = {};
-    for (int p = 0; p < list.n; p++) {
+    uint64_t root_idx[2 * kC3SymMaxLookups] = {};
+    const uint8_t* tables[2 * kC3SymMaxLookups] = {};
+    int reads = 0;
+    for (int p = 0; p < list.n; p++, reads++) {
         const C3Lookup& lk = list.lk[p];
-        root_idx[p] = c3_sym_index(&lk, c3_lookup_head(&lk), s0.corner, s0.edge);
-        tables[p] = lk.table;
+        root_idx[reads] = c3_sym_index(&lk, c3_lookup_head(&lk), s0.corner, s0.edge);
+        tables[reads] = lk.table;
     }
-    uint8_t v[kC3SymMaxLookups] = {};
-    if (int rc = ida_root_bytes(on_device, list.n, tables, root_idx, st, v)) return rc;
+    if (dual) {
+        const uint64_t corner = c3_inverse_locs<DCA_CUBE3_CORNERS, false>(s0.corner), edge = c3_inverse_locs<DCA_CUBE3_EDGES, false>(s0.edge);
+        for (int p = 0; p < list.n; p++) {
+            const C3Lookup& lk = list.lk[p];
+            if (c3_lookup_whole(c3_lookup_head(&lk))) continue;
+            root_idx[reads] = c3_sym_index(&lk, c3_lookup_head(&lk), corner, edge);
+            tables[reads++] = lk.table;
+        }
+    }
+    uint8_t v[2 * kC3SymMaxLookups] = {};
+    if (int rc = ida_root_bytes(on_device, reads, tables, root_idx, st, v)) return rc;
     uint32_t h_root = 0;
     bool dead = false;
-    for (int p = 0; p < list.n; p++) {
+    for (int p = 0; p < reads; p++) {
         dead = dead || v[p] >= kPdbInf;
         h_root = h_root > v[p] ? h_root : v[p];
     }
     const C3IdaMoves mt = c3_ida_moves();
     const bool search = !dead && !C3Domain::goal(s0);
-    C3SymSet arg{&list, list.n, list.kinds_used};
+    C3DualSet arg{&list, list.n, list.kinds_used, c3_dual_pass(list)};
     IdaCtrl* dev = nullptr;
     int device = -1;
     if (on_device && search) {
         if (int rc = c3_sym_device_list(list, arg.list)) return rc;
         if (int rc = ida_block_take(dev, device)) return rc;
     }
-    const int rc = ida_drive<C3SymDomain>(h_root, dead, C3Domain::goal(s0), max_nodes, out,
-                                          [&](uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, IdaCtrl& ctrl) {
-        if (on_device)
-            return ida_device_iteration(dev, ctrl, st, "ida_cube3_sym_kernel", [&] {
-                hipLaunchKernelGGL(ida_cube3_sym_kernel, dim3(ida_blocks(n_items)), dim3(kIdaThreads), 0, st, s0, arg, mt, dev, T, P, n_items, budget,
-                                   ida_poll(budget, ida_blocks(n_items) * kIdaThreads));
-            });
-        C3SymDomain::Ctx c;
-        c.mv = (const uint8_t*)mt.w;
-        c.set = nullptr;
-        c.list = &list;
-        c.n = list.n;
-        uint32_t stk[C3Domain::STACK_WORDS] = {};
-        ida_lane<C3SymDomain>(c, s0, &ctrl, stk, 1u, T, P, n_items, budget, ida_poll(budget, 1));
-        return 0;
-    });
+    const auto run = [&](auto domain, const char* name, auto launch) {
+        using D = decltype(domain);
+        return ida_drive<D>(h_root, dead, C3Domain::goal(s0), max_nodes, out,
+                            [&](uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, IdaCtrl& ctrl) {
+            if (on_device)
+                return ida_device_iteration(dev, ctrl, st, name, [&] {
+                    launch(dim3(ida_blocks(n_items)), T, P, n_items, budget, ida_poll(budget, ida_blocks(n_items) * kIdaThreads));
+                });
+            typename D::Ctx c;
+            c.mv = (const uint8_t*)mt.w;
+            c.set = nullptr;
+            c.list = &list;
+            c.n = list.n;
+            if constexpr (std::is_same_v<D, C3DualDomain>) c.dual = arg.dual;
+            uint32_t stk[C3Domain::STACK_WORDS] = {};
+            ida_lane<D>(c, s0, &ctrl, stk, 1u, T, P, n_items, budget, ida_poll(budget, 1));
+            return 0;
+        });
+    };
+    const int rc = dual ? run(C3DualDomain{}, "ida_cube3_dual_kernel",
+                              [&](dim3 blocks, uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
+                                  hipLaunchKernelGGL(ida_cube3_dual_kernel, blocks, dim3(kIdaThreads), 0, st, s0, arg, mt, dev, T, P, n_items, budget, poll);
+                              })
+                        : run(C3SymDomain{}, "ida_cube3_sym_kernel",
+                              [&](dim3 blocks, uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
+                                  const C3SymSet sym{arg.list, arg.n, arg.kinds_used};
+                                  hipLaunchKernelGGL(ida_cube3_sym_kernel, blocks, dim3(kIdaThreads), 0, st, s0, sym, mt, dev, T, P, n_items, budget, poll);
+                              });
     ida_block_give(dev, device, rc == 0);
     return rc;
 }
@@ -904,7 +986,7 @@ static int ida_cube3_entry(const char* who, const uint8_t* root, int num_pattern
 // every refusal of a symmetric cube3 search, then the search: before any HIP call
 static int ida_cube3_sym_entry(const char* who, const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
                                const uint8_t* const* tables, int max_images, int64_t max_nodes, const IdaOut& out, bool on_device,
-                               hipStream_t st) {
+                               hipStream_t st, bool dual = false) {
     if (root == nullptr) {
         set_error("bad argument: %s: root must not be NULL", who);
         return DCA_E_BADARG;
@@ -914,7 +996,9 @@ static int ida_cube3_sym_entry(const char* who, const uint8_t* root, int num_pat
     C3SymList list;
     if (int rc = c3_fill_sym_entry(who, num_patterns, kinds, cubies, ks, tables, max_images, set, list)) return rc;
     if (int rc = ida_check_cube3_root(who, root)) return rc;
-    return ida_cube3_sym(root, list, max_nodes, out, on_device, st);
+    if (dual)
+        if (int rc = ida_check_cube3_slots(who, root)) return rc;
+    return ida_cube3_sym(root, list, max_nodes, out, on_device, st, dual);
 }
 
 }  // namespace dca
@@ -954,6 +1038,14 @@ int dca_idastar_cube3_sym(const uint8_t* root, int num_patterns, const int* kind
     return ida_cube3_sym_entry(__func__, root, num_patterns, kinds, cubies, ks, tables, max_images, max_nodes, out, true, (hipStream_t)stream);
 }
 
+int dca_idastar_cube3_dual(const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
+                           const uint8_t* const* tables, int max_images, int64_t max_nodes, int* status, int* length, uint8_t* moves,
+                           int moves_cap, int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap,
+                           int64_t* total_nodes, void* stream) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    return ida_cube3_sym_entry(__func__, root, num_patterns, kinds, cubies, ks, tables, max_images, max_nodes, out, true, (hipStream_t)stream, true);
+}
+
 int dca_idastar_host(int env, int dim, const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* ids, const int* ks,
                      const uint8_t* const* tables, int64_t max_nodes, int* status, int* length, uint8_t* moves, int moves_cap,
                      int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes) {
@@ -977,6 +1069,14 @@ int dca_idastar_host_sym(const uint8_t* root, int num_patterns, const int* kinds
                          int64_t* total_nodes) {
     const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
     return ida_cube3_sym_entry(__func__, root, num_patterns, kinds, cubies, ks, tables, max_images, max_nodes, out, false, nullptr);
+}
+
+int dca_idastar_host_dual(const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
+                          const uint8_t* const* tables, int max_images, int64_t max_nodes, int* status, int* length, uint8_t* moves,
+                          int moves_cap, int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap,
+                          int64_t* total_nodes) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    return ida_cube3_sym_entry(__func__, root, num_patterns, kinds, cubies, ks, tables, max_images, max_nodes, out, false, nullptr, true);
 }
 
 int dca_idastar_set_prefix(int depth) {

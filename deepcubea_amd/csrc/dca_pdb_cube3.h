@@ -1,6 +1,7 @@
 // dca_pdb_cube3.h — what the cube3 pattern-database code shares between dca_pdb_cube3.hip (build and eval kernels) and
 // dca_idastar.hip (the IDA* search): the cubies derived at compile time, rank / unrank, the row -> locations rule, the eval
-// frame's row value, the cube's 48 symmetries with the look-up list made from them, and the entry points' checks.
+// frame's row value, the cube's 48 symmetries with the look-up list made from them, the inverse state's location words for the
+// dual look-ups, and the entry points' checks.
 // Header-only: every translation unit compiles its own copy, no device symbol crosses a translation unit.
 #pragma once
 #include <stddef.h>
@@ -588,6 +589,153 @@ struct C3EvalSym {
             best = best > v ? best : v;
         }
         return best;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------------------- duality
+// The dual look-ups (include/dca.h "Dual look-ups"): the look-up list read a second time at the location words of the INVERSE
+// state, which are made from the state's own words in registers — no row, no table, no memory access.
+//
+// Where cubie j sits in slot s, the inverse has cubie s in slot j.  Its orientation there: r counts the place, among a slot's
+// ascending positions, of the cubie's smallest colour, and the ascending positions of a corner slot run clockwise round four
+// of the corners and anticlockwise round the other four.  Between two corners of one class the cubie's positions are rotated
+// by r and the inverse rotates back, r' = (3 - r) mod 3; between the classes they are reflected about r, and a reflection is
+// its own inverse, r' = r.  An edge has r' = r = (2 - r) mod 2 either way.  The classes are read off the move table: a quarter
+// turn carries a slot's positions x -> x + c onto a slot of its own class and x -> c - x onto one of the other.
+constexpr uint32_t make_c3_corner_classes() {  // bit s = slot s is not of slot 0's class; 0xFFFFFFFF: the move table has no such classes
+    uint32_t cls = 0, known = 1;
+    for (int round = 0; round < 8; round++)
+        for (int a = 0; a < 12; a++)
+            for (int s = 0; s < 8; s++) {
+                const int t0 = kC3.move[0][a][s * 3], t1 = kC3.move[0][a][s * 3 + 1], t = t0 / 3;
+                if (t1 / 3 != t) return 0xFFFFFFFFu;
+                const uint32_t flips = (t1 - t0 + 3) % 3 == 1 ? 0u : 1u;
+                if (!((known >> s) & 1u)) continue;
+                const uint32_t bit = ((cls >> s) & 1u) ^ flips;
+                if (((known >> t) & 1u) && ((cls >> t) & 1u) != bit) return 0xFFFFFFFFu;
+                known |= 1u << t;
+                cls |= bit << t;
+            }
+    return known == 0xFFu ? cls : 0xFFFFFFFFu;
+}
+inline constexpr uint32_t kC3CornerClasses = make_c3_corner_classes();
+static_assert(kC3CornerClasses < 0x100u && __builtin_popcount(kC3CornerClasses) == 4, "cube3: two classes of four corner slots");
+
+// The inverse state's location words from the state's (5 bits a cubie, every location < 24 as c3_row_locs and the moves leave
+// them): for cubie j = 0 .. n-1 in ascending order at (s_j, r_j), field s_j becomes (j, r'_j).
+//   REPLACE  the field is masked, then set: the last writer wins and a slot no cubie names keeps location 0, so the result's
+//            locations are < 24 for ANY words — the any-bytes rule of the eval kernels.
+//   !REPLACE the field is or-ed onto zero: the same words wherever the n slots are distinct, which a search's state is (its
+//            root is checked, the moves permute the slots); on other words fields would mix.
+template <int KIND, bool REPLACE>
+DCA_C3_INLINE uint64_t c3_inverse_locs(uint64_t locs) {
+    constexpr int n = C3Kind<KIND>::n, o = C3Kind<KIND>::o;
+    uint64_t inv = 0;
+#pragma unroll
+    for (int j = 0; j < n; j++) {
+        const uint32_t l = (uint32_t)(locs >> (5 * j)) & 31u;
+        const uint32_t s = l / (uint32_t)o, r = l - s * (uint32_t)o;
+        uint32_t back = r;
+        if (KIND == DCA_CUBE3_CORNERS) {
+            const bool same = (((kC3CornerClasses >> s) ^ (kC3CornerClasses >> j)) & 1u) == 0u;
+            back = same && r != 0u ? 3u - r : r;
+        }
+        const uint32_t sh = 5u * s;  // s <= 10 even for a field of 31: inside the word
+        if (REPLACE) inv &= ~(31ull << sh);
+        inv |= (uint64_t)((uint32_t)(j * o) + back) << sh;
+    }
+    return inv;
+}
+
+// Does the look-up's pattern name every cubie of its kind?  Then its byte at the inverted words is its byte at the state on
+// every cube state, and the second pass counts it 0.  (An edge pattern has k <= 8 < 12.)
+DCA_C3_INLINE bool c3_lookup_whole(const C3LookupHead& h) {
+    return (h.meta & 0xFFFFu) == ((uint32_t)DCA_CUBE3_CORNERS | (uint32_t)C3Kind<DCA_CUBE3_CORNERS>::n << 8);
+}
+
+// c3_sym_gather4 for the second pass, over the inverted words: p0 is any look-up below n, so p0 + q may pass the list's end —
+// such a look-up is entry 0 again — and a whole look-up counts 0.  (Written out a second time: as one template with
+// c3_sym_gather4 it moved the symmetric kernels' scalar loads, profiles/cube3_dual_isa.txt.)
+DCA_C3_INLINE uint32_t c3_dual_gather4(const C3SymList* list, int p0, uint64_t corner, uint64_t edge) {
+    uint64_t idx[4];
+    C3LookupHead h[4];
+    uint32_t m[4][kPdbMaxK];
+    const C3Lookup* lk[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) lk[q] = &list->lk[p0 + q < kC3SymMaxLookups ? p0 + q : 0];
+#pragma unroll
+    for (int q = 0; q < 4; q++) h[q] = c3_lookup_head(lk[q]);
+#pragma unroll
+    for (int q = 0; q < 4; q++) c3_sym_maps(lk[q], h[q], corner, edge, m[q]);
+#pragma unroll
+    for (int q = 0; q < 4; q++) idx[q] = c3_sym_rank(h[q], m[q]);
+    uint32_t v[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+#ifdef __HIP_DEVICE_COMPILE__
+        v[q] = ((const __attribute__((address_space(1))) uint8_t*)(uintptr_t)h[q].table)[idx[q]];
+#else
+        v[q] = h[q].table[idx[q]];
+#endif
+        v[q] = c3_lookup_whole(h[q]) ? 0u : v[q];
+    }
+    const uint32_t a = v[0] > v[1] ? v[0] : v[1], b = v[2] > v[3] ? v[2] : v[3];
+    return a > b ? a : b;
+}
+
+// What the second pass needs of a list: `lead`, the look-ups in front that name every cubie of their kind (the pass starts
+// behind them; one elsewhere in the list counts 0, c3_dual_gather4), n where there is no other; `kinds`, bit kind = some look-up of
+// that kind is read in the pass, so its word is inverted.
+struct C3DualPass {
+    int lead;
+    int kinds;
+};
+
+static C3DualPass c3_dual_pass(const C3SymList& list) {
+    C3DualPass d{list.n, 0};
+    for (int p = 0; p < list.n; p++) {
+        if (c3_lookup_whole(c3_lookup_head(&list.lk[p]))) continue;
+        d.lead = d.lead < p ? d.lead : p;
+        d.kinds |= 1 << (list.lk[p].meta & 0xFFu);
+    }
+    return d;
+}
+
+struct C3DualSet {  // the kernel argument
+    const C3SymList* list;
+    int n;
+    int kinds_used;
+    C3DualPass dual;
+};
+
+// the second pass: the largest byte over the look-ups from `lead` on at the inverted words, left at the first value above slack
+DCA_C3_INLINE uint32_t c3_dual_value(const C3SymList* list, int n, int lead, uint64_t corner, uint64_t edge, uint32_t best, uint32_t slack) {
+    for (int p0 = lead; p0 < n; p0 += 4) {
+        const uint32_t v = c3_dual_gather4(list, p0, corner, edge);
+        best = best > v ? best : v;
+        if (best > slack) break;
+    }
+    return best;
+}
+
+// what pdb_eval_kernel / pdb_eval_launch take for the dual value: the symmetric value, then the same list at the inverted words
+template <int ROWS>
+struct C3EvalDual {
+    static constexpr int N = 54;
+    using Set = C3DualSet;
+    static constexpr const char* kernel_name = "c3_eval_dual_kernel";
+
+    __host__ __device__ static inline uint32_t row_value(const uint32_t (&w)[14], const C3DualSet& set) {
+        const uint64_t corner = (set.kinds_used & 1) ? c3_row_locs<DCA_CUBE3_CORNERS, ROWS>(w) : 0ull;
+        const uint64_t edge = (set.kinds_used & 2) ? c3_row_locs<DCA_CUBE3_EDGES, ROWS>(w) : 0ull;
+        uint32_t best = 0;
+        for (int p0 = 0; p0 < set.n; p0 += 4) {
+            const uint32_t v = c3_sym_gather4(set.list, p0, corner, edge);
+            best = best > v ? best : v;
+        }
+        const uint64_t icorner = (set.dual.kinds & 1) ? c3_inverse_locs<DCA_CUBE3_CORNERS, true>(corner) : 0ull;
+        const uint64_t iedge = (set.dual.kinds & 2) ? c3_inverse_locs<DCA_CUBE3_EDGES, true>(edge) : 0ull;
+        return c3_dual_value(set.list, set.n, set.dual.lead, icorner, iedge, best, 0xFFFFFFFFu);
     }
 };
 

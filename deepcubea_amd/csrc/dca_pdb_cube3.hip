@@ -19,6 +19,10 @@
 //           row, then trips of four look-ups — their heads by scalar loads, their 32 map reads issued together, four ranks,
 //           four gathers issued together.  The list is global memory.  Cost per row: profiles/idastar_sym_probe.txt.
 //
+//   eval_dual  the symmetric row value, then the location words of the inverse state made from the row's own (c3_inverse_locs, the
+//           replacing form: in bounds for any bytes) and the list's trips again over them, but for the look-ups of a pattern that
+//           names every cubie of its kind (dca_pdb_cube3.h "duality", include/dca.h).  Cost per row: profiles/idastar_dual_probe.txt.
+//
 // What bounds either kernel has not been measured (profiles/cube3_pdb_probe.txt holds only wall-clock times).
 #include "dca_pdb_cube3.h"
 
@@ -203,6 +207,58 @@ int dca_cube3_pdb_eval_sym_host(const uint8_t* states, int64_t n, int64_t ld, in
         out[i] = (float)(row_kind == DCA_ROWS_STATE ? C3EvalSym<DCA_ROWS_STATE>::row_value(w, arg)
                                                     : C3EvalSym<DCA_ROWS_NNET>::row_value(w, arg));
     }
+    return 0;
+}
+
+int dca_cube3_pdb_eval_dual(const uint8_t* states, int64_t n, int64_t ld, int row_kind, int num_patterns, const int* kinds,
+                            const uint8_t* cubies, const int* ks, const uint8_t* const* tables, int max_images, float* out,
+                            void* stream) {
+    DCA_ARG(n >= 0 && n < ((int64_t)1 << 31));
+    DCA_ARG(ld >= 54);
+    DCA_ARG(row_kind == DCA_ROWS_STATE || row_kind == DCA_ROWS_NNET);
+    C3Set set{};
+    C3SymList list;
+    if (int rc = c3_fill_sym_entry(__func__, num_patterns, kinds, cubies, ks, tables, max_images, set, list)) return rc;
+    if (n == 0) return 0;
+    DCA_ARG(states != nullptr && out != nullptr);
+    DCA_ARG(((uintptr_t)out & 3) == 0);
+    C3DualSet arg{nullptr, list.n, list.kinds_used, c3_dual_pass(list)};
+    if (int rc = c3_sym_device_list(list, arg.list)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return row_kind == DCA_ROWS_STATE ? pdb_eval_launch<C3EvalDual<DCA_ROWS_STATE>>(states, n, ld, arg, out, st)
+                                      : pdb_eval_launch<C3EvalDual<DCA_ROWS_NNET>>(states, n, ld, arg, out, st);
+}
+
+int dca_cube3_pdb_eval_dual_host(const uint8_t* states, int64_t n, int64_t ld, int row_kind, int num_patterns, const int* kinds,
+                                 const uint8_t* cubies, const int* ks, const uint8_t* const* tables, int max_images, float* out) {
+    DCA_ARG(n >= 0 && n < ((int64_t)1 << 31));
+    DCA_ARG(ld >= 54);
+    DCA_ARG(row_kind == DCA_ROWS_STATE || row_kind == DCA_ROWS_NNET);
+    C3Set set{};
+    C3SymList list;
+    if (int rc = c3_fill_sym_entry(__func__, num_patterns, kinds, cubies, ks, tables, max_images, set, list)) return rc;
+    if (n == 0) return 0;
+    DCA_ARG(states != nullptr && out != nullptr);
+    const C3DualSet arg{&list, list.n, list.kinds_used, c3_dual_pass(list)};
+    for (int64_t i = 0; i < n; i++) {  // the kernel's row load and row value, one row after another
+        uint32_t w[14];
+        pdb_load_row<54, 1>(states + i * ld, w);
+        out[i] = (float)(row_kind == DCA_ROWS_STATE ? C3EvalDual<DCA_ROWS_STATE>::row_value(w, arg)
+                                                    : C3EvalDual<DCA_ROWS_NNET>::row_value(w, arg));
+    }
+    return 0;
+}
+
+int dca_cube3_inverse_locs(const uint8_t* row, int row_kind, uint64_t* words) {
+    DCA_ARG(row != nullptr && words != nullptr);
+    DCA_ARG(row_kind == DCA_ROWS_STATE || row_kind == DCA_ROWS_NNET);
+    uint32_t w[14];
+    pdb_load_row<54, 1>(row, w);
+    const bool ids = row_kind == DCA_ROWS_STATE;
+    words[0] = c3_inverse_locs<DCA_CUBE3_CORNERS, true>(ids ? c3_row_locs<DCA_CUBE3_CORNERS, DCA_ROWS_STATE>(w)
+                                                            : c3_row_locs<DCA_CUBE3_CORNERS, DCA_ROWS_NNET>(w));
+    words[1] = c3_inverse_locs<DCA_CUBE3_EDGES, true>(ids ? c3_row_locs<DCA_CUBE3_EDGES, DCA_ROWS_STATE>(w)
+                                                          : c3_row_locs<DCA_CUBE3_EDGES, DCA_ROWS_NNET>(w));
     return 0;
 }
 

@@ -263,9 +263,12 @@ def build_parser() -> ArgumentParser:
                              "On cube3: corner / edge cubie tables combined by max, SPEC a "
                              "preset (corners, korf, korf7; no auto) or groups of cubies of one kind such as "
                              "c0,c1,c2,c3/e0,e1,e2,e3,e4,e5; SPEC+sym reads every table again at the state's images under the "
-                             "cube's 48 symmetries and takes the largest value (SPEC+sym:N: the first N images of each pattern).  "
-                             "Admissible and consistent: with --weight 1 --semantics cpp "
-                             "the solutions are optimal.  On lightsout7: exact:gf2 — the exact distance popcount(A^-1 s) by a "
+                             "cube's 48 symmetries and takes the largest value (SPEC+sym:N: the first N images of each pattern); "
+                             "SPEC+dual, or SPEC+sym:N+dual, reads every look-up a second time at the inverse state.  "
+                             "Without +dual admissible and consistent: with --weight 1 --semantics cpp "
+                             "the solutions are optimal.  With +dual the value is admissible but not consistent, and that "
+                             "sentence is not made for it: a node may be popped before its shortest path is found "
+                             "(idastar.py needs admissibility alone and stays optimal).  On lightsout7: exact:gf2 — the exact distance popcount(A^-1 s) by a "
                              "GF(2) solve, no table and nothing to build.  Use it with a weight below 1 (the reference's "
                              "line: --weight 0.2 --batch_size 1000): the solutions are still optimal for any weight in (0, 1), while "
                              "at --weight 1 all 2^h states made by pressing a subset of the solution's cells tie at one f and the "

@@ -4,8 +4,8 @@
         --model_dir pdb:5-5-5 --results_dir results/puzzle15_idastar
 
 The batched A* engine (astar.py) keeps every generated node and stops at its pool's capacity; iterative-deepening A* keeps a move
-stack per lane and runs as long as its node budget lets it.  With an admissible table set — every `pdb:` set is — the solution
-is optimal.  results.pkl has astar.py's format and keys (utils/compare_solutions.py reads it); idastar.pkl next to it holds, per
+stack per lane and runs as long as its node budget lets it.  With an admissible table set — every `pdb:` set is, `+dual`
+included — the solution is optimal.  results.pkl has astar.py's format and keys (utils/compare_solutions.py reads it); idastar.pkl next to it holds, per
 state, `solved`, `status`, `thresholds` and `nodes_per_threshold`.  A state that ends on "budget exhausted" is reported and
 recorded as unsolved — an empty solution in results.pkl, solved = False in idastar.pkl — and the search goes on to the next; so
 is a state whose root the library refuses (wrong parity, no permutation), with status "refused (...)"."""
@@ -47,8 +47,11 @@ def pattern_database(args):
     spec = model.split(":", 1)[1]
     if env_name == "cube3":
         from ..utils.cube3_pdb import Cube3PatternDatabase
-        return Cube3PatternDatabase(spec)  # (takes +sym / +sym:N, refuses a +reflect suffix)
-    from ..utils.cube3_pdb import SYM_SUFFIX
+        return Cube3PatternDatabase(spec)  # (takes +sym / +sym:N and +dual, refuses a +reflect suffix)
+    from ..utils.cube3_pdb import DUAL_SUFFIX, SYM_SUFFIX
+    if any(t.strip().lower().startswith(DUAL_SUFFIX[1:]) for t in spec.split("+")[1:]):
+        raise ValueError("pattern database %r: %s reads a table at the inverse of a state, and is defined for cube3 only; the blank "
+                         "makes the inverse of a sliding-puzzle state no state of the same problem" % (spec, DUAL_SUFFIX))
     if spec.partition("+")[2].strip().lower().startswith(SYM_SUFFIX[1:]):
         raise ValueError("pattern database %r: %s reads a table at the images of a state under the cube's 48 symmetries, and is "
                          "defined for cube3 only; a sliding puzzle's one symmetry is +reflect" % (spec, SYM_SUFFIX))
@@ -80,7 +83,7 @@ class IDAStar:
         if max_nodes is None:
             max_nodes = default_max_nodes(self.env_name)
         if self.env == _lib.ENV_CUBE3:
-            return _lib.idastar_cube3(root, self.pdb.patterns, self.pdb.tables, max_nodes, sym=self.pdb.sym)
+            return _lib.idastar_cube3(root, self.pdb.patterns, self.pdb.tables, max_nodes, sym=self.pdb.sym, dual=self.pdb.dual)
         return _lib.idastar_npuzzle(self.dim, root, self.pdb.partition, self.pdb.tables, max_nodes, reflect=self.pdb.reflect)
 
 
@@ -98,8 +101,9 @@ def build_parser() -> ArgumentParser:
                         help="pdb:SPEC, as for astar.py: a preset (puzzle8 4-4; puzzle15 5-5-5, 6-6-3; puzzle24 6-6-6-6; auto; cube3 "
                              "corners, korf, korf7) or explicit groups.  On a sliding puzzle SPEC+reflect searches on the reflected "
                              "look-up (at most 4 patterns); on cube3 SPEC+sym searches on the symmetric look-ups, every table read again at "
-                             "the state's images under the cube's 48 symmetries (SPEC+sym:N: the first N images of each pattern).  "
-                             "Built on the GPU at start-up")
+                             "the state's images under the cube's 48 symmetries (SPEC+sym:N: the first N images of each pattern), and SPEC+dual "
+                             "or SPEC+sym:N+dual reads every look-up a second time at the inverse state (d(s^-1) = d(s): admissible but "
+                             "not consistent, which IDA* does not need; cube3 only).  Built on the GPU at start-up")
     parser.add_argument('--results_dir', type=str, required=True, help="Directory to save results")
     parser.add_argument('--start_idx', type=int, default=0, help="")
     parser.add_argument('--max_nodes', type=int, default=None,

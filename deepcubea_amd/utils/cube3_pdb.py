@@ -1,6 +1,6 @@
 """Pattern databases for cube3 (include/dca.h "pattern databases for cube3", csrc/dca_pdb_cube3.hip): Korf's distance tables
 over corner cubies and over subsets of the edge cubies, combined by max — an exact admissible, consistent heuristic.  With
-`--env cube3 --model_dir pdb:<spec> --weight 1 --semantics cpp` the engine is an optimal solver.
+`--env cube3 --model_dir pdb:<spec> --weight 1 --semantics cpp` the engine is an optimal solver (a spec without `+dual`).
 
 A set is a tuple of patterns, a pattern a (kind, cubies) pair; `parse_cube3_pdb_spec` turns a preset name or explicit groups
 ("c0,c1,c2/e0,e1,e2,e3") into one and refuses what cannot be built, before any device work.  Patterns may share cubies: the
@@ -8,7 +8,10 @@ max of admissible tables is admissible.
 
 `<spec>+sym` reads every table again at the state's conjugates under the cube's 48 symmetries, each pattern at all of its distinct
 images, and takes the largest value (include/dca.h "Symmetric look-ups"): no table bytes, the same tables.  `<spec>+sym:N` takes
-the first N images of each pattern; `+sym:1` is the plain heuristic."""
+the first N images of each pattern; `+sym:1` is the plain heuristic.
+
+`<spec>+dual` reads every look-up a second time at the INVERSE state and takes the larger value (include/dca.h "Dual look-ups"):
+d(s^-1) = d(s), so the value stays admissible — but it is no longer consistent.  It composes with `+sym`: `<spec>+sym:N+dual`."""
 from __future__ import annotations
 
 import re
@@ -34,6 +37,7 @@ MAX_K = 8
 MAX_TABLE_BYTES = 1 << 34  # one pattern's table (the library's own limit)
 SYM_SUFFIX = "+sym"  # a spec that ends in it, or in +sym:N, asks for the symmetric look-ups; the tables are the same
 SYM_ALL = _lib.CUBE3_SYMS
+DUAL_SUFFIX = "+dual"  # a spec with it asks for the dual look-ups as well; the tables and the look-up list are the same
 
 
 def split_sym(spec: str) -> Tuple[str, int]:
@@ -55,6 +59,22 @@ def split_sym(spec: str) -> Tuple[str, int]:
     return base.strip(), check_sym(sym)
 
 
+def split_suffixes(spec: str) -> Tuple[str, int, bool]:
+    """A spec string -> (the spec parse_cube3_pdb_spec takes, N as split_sym gives it, whether +dual was there).  The suffixes
+    are +sym[:N] and +dual, in either order, each at most once; what is left without +dual goes through split_sym, which words
+    every other refusal."""
+    base, *suffixes = str(spec).strip().split("+")
+    named = [t.strip().lower() for t in suffixes]
+    for t in named:
+        if t.startswith(DUAL_SUFFIX[1:]) and t != DUAL_SUFFIX[1:]:
+            raise ValueError("cube3 pattern database %r: %s takes no argument and no other spelling" % (spec, DUAL_SUFFIX))
+    if named.count(DUAL_SUFFIX[1:]) > 1:
+        raise ValueError("cube3 pattern database %r: the suffix %s, once" % (spec, DUAL_SUFFIX))
+    dual = DUAL_SUFFIX[1:] in named
+    rest = "+".join([base] + [t for t, name in zip(suffixes, named) if name != DUAL_SUFFIX[1:]])
+    return split_sym(rest) + (dual,)
+
+
 def check_sym(sym) -> int:
     sym = int(sym or 0)
     if not 0 <= sym <= SYM_ALL:
@@ -62,8 +82,9 @@ def check_sym(sym) -> int:
     return sym
 
 
-def sym_suffix(sym: int) -> str:
-    return "" if not sym else SYM_SUFFIX if sym == SYM_ALL else "%s:%d" % (SYM_SUFFIX, sym)
+def sym_suffix(sym: int, dual: bool = False) -> str:
+    """The canonical suffix: +sym or +sym:N where there is one, then +dual."""
+    return ("" if not sym else SYM_SUFFIX if sym == SYM_ALL else "%s:%d" % (SYM_SUFFIX, sym)) + (DUAL_SUFFIX if dual else "")
 
 
 def sym_lookups(patterns: PatternSet, sym: int) -> int:
@@ -142,21 +163,23 @@ class Cube3PatternDatabase(_TableSet):
     env_name = "cube3"
     _engine_rows = "network-input"
 
-    def __init__(self, patterns, sym: int = 0):
+    def __init__(self, patterns, sym: int = 0, dual: bool = False):
         super().__init__()
         sym = check_sym(sym)
         if isinstance(patterns, str):
-            patterns, suffix = split_sym(patterns)
+            patterns, suffix, named = split_suffixes(patterns)
             self.patterns = parse_cube3_pdb_spec(patterns)
             sym = suffix or sym
+            dual = bool(dual) or named
         else:
             self.patterns = check_patterns(patterns)
         self.sym = sym  # 0: plain; N: the first N images of each pattern (48: all)
+        self.dual = bool(dual)  # every look-up read again at the inverse state
         check_sym_lookups(self.patterns, self.sym)
 
     @property
     def spec(self) -> str:
-        return spec_of(self.patterns) + sym_suffix(self.sym)
+        return spec_of(self.patterns) + sym_suffix(self.sym, self.dual)
 
     def _table_bytes(self) -> List[int]:
         return table_bytes(self.patterns)
@@ -166,7 +189,7 @@ class Cube3PatternDatabase(_TableSet):
 
     def heuristic(self, states: torch.Tensor, row_kind: int = _lib.ROWS_STATE) -> torch.Tensor:
         self._ready("build() or load() first")
-        return _lib.cube3_pdb_eval(states, row_kind, self.patterns, self.tables, sym=self.sym)
+        return _lib.cube3_pdb_eval(states, row_kind, self.patterns, self.tables, sym=self.sym, dual=self.dual)
 
     def _engine_heuristic(self, states: torch.Tensor) -> torch.Tensor:
         return self.heuristic(states, _lib.ROWS_NNET)  # BwasEngine.step / solve hand a cube3 closure the rows sticker // 9

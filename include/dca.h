@@ -365,6 +365,41 @@ int dca_cube3_pdb_eval_sym(const uint8_t* states /*[n, ld]*/, int64_t n, int64_t
                            const int* ks /*host [num_patterns]*/, const uint8_t* const* tables /*host [num_patterns] of device pointers*/,
                            int max_images, float* out /*[n]*/, void* stream);
 
+/* Dual look-ups (`pdb:<spec>+dual`, `pdb:<spec>+sym:N+dual`; cube3 only; Zahavi, Felner, Holte, Schaeffer 2008, "Duality in
+ * permutation state spaces"): the 12 moves are closed under inversion (a ^ 1), so if s = m_1 ... m_d then s^-1 = m_d^-1 ... m_1^-1
+ * and d(s^-1) = d(s): any table read at the INVERSE state is an admissible bound on d(s).  The pattern's cubies sit elsewhere in
+ * s^-1, so the byte usually differs from the one at s.  The inverse of a conjugate is the conjugate of the inverse, so every
+ * entry of the symmetric look-up list can be read a second time at the inverse: the same tables, the same list, no table bytes.
+ *   inverse row  for a row S of sticker ids that is a cube state, S^-1[S[p]] = p (numpy: argsort(S)).
+ *   dual value   of S under (pattern set, max_images = N): max(v(S), v(S^-1)), v = the value of dca_cube3_pdb_eval_sym at N
+ *                (N = 1: the plain max over the patterns).  Never below v(S); never above d(S).
+ *   in location words   no kernel builds S^-1: the inverse is taken in cubie coordinates, on the two words of the colour rule
+ *                (5 bits a cubie, location = slot * o + r).  INVERSION RULE: start from the all-zero word; for cubie
+ *                j = 0 ... n-1 in ascending order at location (s_j, r_j), REPLACE field s_j by the location (j, r'_j).  The
+ *                orientation: r' = r for an edge.  The corner slots fall into two classes of four (the ascending positions of a
+ *                slot run clockwise round one class and anticlockwise round the other; read off the move table: a quarter turn
+ *                carries a slot's positions x -> x + c onto its own class, x -> c - x onto the other); r' = (3 - r) mod 3
+ *                where slot s_j and slot j are of one class, r' = r where they are not.  On every cube state the result is
+ *                the location words of argsort(S).  A row of colours (DCA_ROWS_NNET) goes through the colour rule first, as
+ *                everywhere, and its words are inverted by the same rule.
+ *   replacing rule   a field is replaced (mask, then or), never or-ed onto stale bits: the last writer wins, a slot that no
+ *                cubie names keeps location 0.  Every inverted location is therefore < 24 for ANY 54 bytes, and every map
+ *                read and every rank stays in bounds as above (the any-bytes rule).  The IDA* lane uses the or-only form —
+ *                the same words wherever the n slots of a kind are distinct — which its root is checked for and the moves keep.
+ *   k = n skip   a pattern that names all n cubies of its kind (the 8-corner table) abstracts nothing of that kind: its byte
+ *                is the distance in the group of that kind's cubies, where d(s^-1) = d(s) too, so its dual byte equals its
+ *                regular byte on every cube state.  Its dual look-ups are skipped: they count 0 in the second pass, on ANY
+ *                bytes.
+ *   order        the whole look-up list is read at the state first, then again at the inverted words (the look-ups that are
+ *                not skipped, in the list's order).  A search computes the inverted words only where the first pass has not
+ *                already pruned the child.
+ * dca_cube3_pdb_eval_dual: dca_cube3_pdb_eval_sym with that value: its parameters, its refusals, its list (unchanged, the cap
+ * stays DCA_CUBE3_SYM_MAX_LOOKUPS list entries) and the library's device copies of it. */
+int dca_cube3_pdb_eval_dual(const uint8_t* states /*[n, ld]*/, int64_t n, int64_t ld, int row_kind, int num_patterns,
+                            const int* kinds /*host [num_patterns]*/, const uint8_t* cubies /*host*/,
+                            const int* ks /*host [num_patterns]*/, const uint8_t* const* tables /*host [num_patterns] of device pointers*/,
+                            int max_images, float* out /*[n]*/, void* stream);
+
 /* Exact LightsOut heuristic (csrc/dca_lightsout_exact.hip; `--env lightsout7 --model_dir exact:gf2`): the true distance of any
  * state, by linear algebra over GF(2) instead of a table.
  *   algebra      pressing cell a flips a fixed set of cells, presses commute, and pressing a cell twice is the identity.  A
@@ -475,6 +510,26 @@ int dca_idastar_cube3_sym(const uint8_t* root /*host [54]*/, int num_patterns, c
                           int* status, int* length, uint8_t* moves /*host [moves_cap]*/, int moves_cap, int* num_thresholds,
                           int* thresholds /*host [thresholds_cap]*/, int64_t* nodes_per_threshold /*host [thresholds_cap]*/,
                           int thresholds_cap, int64_t* total_nodes, void* stream);
+/* dca_idastar_cube3_sym on the dual look-ups ("Dual look-ups" above): h = the dual value of (pattern set, max_images).  The
+ * heuristic is admissible but not consistent (a move can change the byte at the inverse state by more than 1); IDA* needs only
+ * admissibility, and the first solution found is optimal.  No bidirectional pathmax.  Same state, moves, pruning rules, work
+ * items, counting, budget and ending; the inverse is not kept in a lane's state but made from the child's two words, in
+ * registers, where the first pass does not prune the child.  h(root) is computed on the host in full: the root is unsolvable
+ * if ANY regular or dual byte at the root is 0xFE or 0xFF.  Both passes may stop at the first value v with g + 1 + v > T.  The
+ * contract, whatever the evaluation order:
+ *   - the thresholds increase strictly; the first is h(root) over all regular and dual look-ups, the last of a solved search the
+ *     solution length;
+ *   - every threshold of the exact search (h = the full dual value everywhere) occurs among them;
+ *   - a completed threshold's node count is that of the tree at that threshold under the full dual value: a property of the
+ *     tree — and never more than the count of dca_idastar_cube3_sym at the same max_images and threshold, whose tree contains it.
+ * Same parameters, outputs and refusals as dca_idastar_cube3_sym, and one more: a root whose 54 distinct sticker ids put two
+ * cubies of a kind into one slot (no cube state: no move sequence solves it) is DCA_E_BADARG, "root: ...". */
+int dca_idastar_cube3_dual(const uint8_t* root /*host [54]*/, int num_patterns, const int* kinds /*host [num_patterns]*/,
+                           const uint8_t* cubies /*host*/, const int* ks /*host [num_patterns]*/,
+                           const uint8_t* const* tables /*host [num_patterns] of device pointers*/, int max_images, int64_t max_nodes,
+                           int* status, int* length, uint8_t* moves /*host [moves_cap]*/, int moves_cap, int* num_thresholds,
+                           int* thresholds /*host [thresholds_cap]*/, int64_t* nodes_per_threshold /*host [thresholds_cap]*/,
+                           int thresholds_cap, int64_t* total_nodes, void* stream);
 
 /* state hash (a9). The reference's hash VALUES are process-randomised SipHash (cube3.py:17-21)
  * or unpinned boost::hash_range (parallel_weighted_astar.cpp:104-111); what is pinned is key

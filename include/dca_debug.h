@@ -87,6 +87,21 @@ int dca_cube3_pdb_eval_sym_host(const uint8_t* states /*host [n, ld]*/, int64_t 
                                 const int* kinds, const uint8_t* cubies, const int* ks,
                                 const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int max_images,
                                 float* out /*host [n]*/);
+/* Host-only: the search of dca_idastar_cube3_dual on the CPU from HOST tables, through the code the kernel compiles.  Same
+ * refusals, same outputs; the thresholds and the completed iterations' node counts equal the device's. */
+int dca_idastar_host_dual(const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
+                          const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int max_images, int64_t max_nodes,
+                          int* status, int* length, uint8_t* moves, int moves_cap, int* num_thresholds, int* thresholds,
+                          int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes);
+/* Host-only: what dca_cube3_pdb_eval_dual computes, in a plain loop on the CPU through the row load and the row value the kernel
+ * compiles.  states, tables and out are HOST memory; the refusals are those of dca_cube3_pdb_eval_dual. */
+int dca_cube3_pdb_eval_dual_host(const uint8_t* states /*host [n, ld]*/, int64_t n, int64_t ld, int row_kind, int num_patterns,
+                                 const int* kinds, const uint8_t* cubies, const int* ks,
+                                 const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int max_images,
+                                 float* out /*host [n]*/);
+/* Host-only: the inversion rule of dca.h "Dual look-ups" in its replacing form on one row of 54 bytes (any bytes): words[0] =
+ * the corner word, words[1] = the edge word of the inverse, 5 bits a cubie. */
+int dca_cube3_inverse_locs(const uint8_t* row /*host [54]*/, int row_kind, uint64_t* words /*host [2]*/);
 /* Host-only: the derived symmetries (dca.h "Symmetric look-ups"), in their documented order: sticker_perms [48][54], sigma as
  * position -> position; move_maps [48][12], pi.  DCA_E_STATE where the derivation failed its checks. */
 int dca_cube3_sym_tables(uint8_t* sticker_perms /*host [48*54]*/, uint8_t* move_maps /*host [48*12]*/);

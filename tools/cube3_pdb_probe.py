@@ -14,6 +14,9 @@ first leg that does not exit 0 (nothing is started on a device after a leg has f
   eval_sym  dca_cube3_pdb_eval_sym on korf with the first N images of every pattern, N in 1, 2, 4, 8, 24 and all, next to the plain
           eval on the same rows in the same process: the cost per row against the plain eval.  `--legs eval_sym --append --out
           profiles/idastar_sym_probe.txt` adds it to the symmetric searches' record.
+  eval_dual  dca_cube3_pdb_eval_dual on korf with `+dual` alone and with `+sym:N+dual` for N in 4, 8 and all, next to the plain
+          eval and the symmetric eval at the same N on the same rows in the same process: the cost per row against both.
+          `--legs eval_dual --append --out profiles/idastar_dual_probe.txt` adds it to the dual searches' record.
 No threshold is set on any time: the numbers are recorded, not met."""
 import argparse
 import os
@@ -31,7 +34,7 @@ from deepcubea_amd import _lib  # noqa: E402
 from deepcubea_amd.search_methods.engine import BwasEngine  # noqa: E402
 from deepcubea_amd.utils.cube3_pdb import PRESETS, Cube3PatternDatabase, spec_of  # noqa: E402
 
-LEG_TIMEOUT_S = {"build": 420, "eval": 150, "search": 420, "eval_sym": 150}
+LEG_TIMEOUT_S = {"build": 420, "eval": 150, "search": 420, "eval_sym": 150, "eval_dual": 150}
 CORNER_HISTOGRAM = [1, 12, 114, 924, 6539, 39528, 199926, 806136, 2761740, 8656152, 22334112, 32420448, 18780864, 2166720, 6624]
 
 
@@ -121,6 +124,26 @@ def eval_sym_leg():
                   % (n, rows, sym_lookups(korf.patterns, n), med, low, med * 1e3 / rows, med / plain), flush=True)
 
 
+def eval_dual_leg():
+    from deepcubea_amd.utils.cube3_pdb import sym_lookups
+    korf = Cube3PatternDatabase("korf").build()
+    for rows in (131072, 245760):
+        X = torch.from_numpy(scramble_rows(rows) // 9).cuda()
+        out = torch.empty(rows, dtype=torch.float32, device="cuda")
+        plain, low = median_us(lambda: _lib.cube3_pdb_eval(X, _lib.ROWS_NNET, korf.patterns, korf.tables, out=out))
+        print("eval   cube3 korf              %7d rows   3 look-ups          median %7.1f us  min %7.1f us  %6.3f ns/row"
+              % (rows, plain, low, plain * 1e3 / rows), flush=True)
+        for n in (1, 4, 8, 48):
+            lookups = sym_lookups(korf.patterns, n)
+            whole = sum(1 for kind, g in korf.patterns if len(g) == _lib.CUBE3_PDB_SLOTS[kind][0])  # one image each, skipped in the second pass
+            base, low = median_us(lambda: _lib.cube3_pdb_eval(X, _lib.ROWS_NNET, korf.patterns, korf.tables, out=out, sym=n))
+            print("eval   cube3 korf+sym:%-3d      %7d rows  %2d look-ups          median %7.1f us  min %7.1f us  %6.3f ns/row  x %.2f of the plain eval"
+                  % (n, rows, lookups, base, low, base * 1e3 / rows, base / plain), flush=True)
+            med, low = median_us(lambda: _lib.cube3_pdb_eval(X, _lib.ROWS_NNET, korf.patterns, korf.tables, out=out, sym=n, dual=True))
+            print("eval   cube3 korf+sym:%-3d+dual %7d rows  %2d + %2d look-ups     median %7.1f us  min %7.1f us  %6.3f ns/row  x %.2f of the plain eval,"
+                  " x %.2f of +sym:%d" % (n, rows, lookups, lookups - whole, med, low, med * 1e3 / rows, med / plain, med / base, n), flush=True)
+
+
 def path_roots(distances, instances):
     g = np.load(os.path.join(ROOT, "tests", "golden", "golden.npz"))
     perm = _lib.lib().dca_cube3_perm_table()
@@ -174,7 +197,7 @@ def main():
     if args.leg:
         _lib.require_gpu()
         print("probe leg %s on %s" % (args.leg, torch.cuda.get_device_name(0)), flush=True)
-        {"build": build_leg, "eval": eval_leg, "search": search_leg, "eval_sym": eval_sym_leg}[args.leg]()
+        {"build": build_leg, "eval": eval_leg, "search": search_leg, "eval_sym": eval_sym_leg, "eval_dual": eval_dual_leg}[args.leg]()
         return 0
     lines = ["$ python tools/cube3_pdb_probe.py --legs %s" % args.legs]
     rc = 0

@@ -18,6 +18,10 @@ first leg that does not exit 0 (nothing is started on a device after a leg has f
              the same built tables in one process, --seconds of search per configuration; then every configuration restricted
              to the states all of them ran and solved, as ratios to the plain run.  Written to profiles/idastar_sym_probe.txt
              with `--legs resources,cube3_sym_korf,cube3_sym_korf7 --seconds 60 --out ...`.
+  cube3_dual_korf, cube3_dual_korf7
+             the same method for the dual look-ups: plain, `+dual`, `+sym:4`, `+sym:4+dual`, `+sym:8`, `+sym:8+dual` and `+sym+dual`,
+             plain first; per configuration also whether a state of 21 moves or more was reached.  Written to
+             profiles/idastar_dual_probe.txt with `--legs resources,cube3_dual_korf,cube3_dual_korf7 --seconds 60 --out ...`.
 A state's node budget is what the rate measured so far gets through in --state_seconds; a state that runs out of it is listed.
 The rate of a family is nodes over seconds summed over its searches of at least 0.05 s (shorter ones time the launches, not the
 kernel).  No threshold is set on any time or rate: the numbers are recorded, not met."""
@@ -34,8 +38,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 LEG_TIMEOUT_S = {"resources": 120, "puzzle15": 500, "puzzle24": 500, "cube3": 700, "puzzle15_reflect": 500, "puzzle24_reflect": 700,
-                 "cube3_sym_korf": 800, "cube3_sym_korf7": 800}
+                 "cube3_sym_korf": 800, "cube3_sym_korf7": 800, "cube3_dual_korf": 1000, "cube3_dual_korf7": 1000}
 SYM_IMAGES = (2, 4, 8, 24)
+DUAL_CONFIGS = ((0, False), (0, True), (4, False), (4, True), (8, False), (8, True), (48, True))  # (N of +sym:N, +dual), plain first
 FIRST_BUDGET = 1 << 31  # nodes, until a rate is known
 
 
@@ -202,6 +207,44 @@ def cube3_sym_leg(spec, seconds, state_seconds, verbose):
                  nodes / secs), flush=True)
 
 
+def cube3_dual_leg(spec, seconds, state_seconds, verbose):
+    """cube3_sym_leg's method over DUAL_CONFIGS: the tables built once, every configuration over the same states in the same
+    order, compared on the states every configuration solved, as ratios to the plain run."""
+    from deepcubea_amd.search_methods.idastar import IDAStar
+    from deepcubea_amd.utils.cube3_pdb import Cube3PatternDatabase, sym_lookups, sym_suffix
+    z = golden()
+    states, lens = z["cube3_test_states"], z["cube3_test_opt_len"].astype(int)
+    ids = np.argsort(lens, kind="stable")
+    t0 = time.time()
+    pdb = Cube3PatternDatabase(spec).build()
+    print("cube3 pdb:%s: %d bytes built in %.2f s" % (spec, pdb.bytes, time.time() - t0), flush=True)
+    whole = sum(1 for kind, g in pdb.patterns if len(g) == (8 if kind == 0 else 12))  # skipped in the second pass
+    runs = {}
+    for n, dual in DUAL_CONFIGS:
+        pdb.sym, pdb.dual = n, dual  # the same tables: the suffixes change the look-ups, not the bytes
+        label = "cube3 %s%s" % (spec, sym_suffix(n, dual))
+        first = sym_lookups(pdb.patterns, n) if n else len(pdb.patterns)
+        print("  %-24s %d%s look-ups a node at the most" % (label, first, " + %d" % (first - whole) if dual else ""))
+        runs[(n, dual)] = run_states(IDAStar("cube3", pdb), label, states[ids], lens[ids], ids, seconds, state_seconds, verbose)[1]
+    both = [i for i in runs[(0, False)] if all(i in r and r[i][0] for r in runs.values())]
+    base_nodes, base_secs = (sum(runs[(0, False)][i][k] for i in both) for k in (1, 2))
+    print("  cube3 %s, the %d states every configuration ran and solved (optimal length %s):"
+          % (spec, len(both), "%d .. %d" % (min(lens[both]), max(lens[both])) if both else "-"))
+    for (n, dual), r in runs.items():
+        nodes, secs = sum(r[i][1] for i in both), sum(r[i][2] for i in both)
+        deepest = max([int(lens[i]) for i in r], default=0)
+        print("  %-18s states run %3d solved %3d | nodes %.4g (x %.4f of plain)  seconds %.3f (x %.4f of plain)  %.3g nodes/s | deepest "
+              "state run %d moves: %s" % (spec + sym_suffix(n, dual), len(r), sum(1 for v in r.values() if v[0]), nodes, nodes / base_nodes, secs,
+                                          secs / base_secs, nodes / secs, deepest, "21 or more reached" if deepest >= 21 else "none of 21 or more"),
+              flush=True)
+    for n in sorted({n for n, dual in DUAL_CONFIGS if dual and (n, False) in runs}):
+        a, b = runs[(n, False)], runs[(n, True)]
+        pair = [i for i in a if i in b and a[i][0] and b[i][0]]
+        nodes, secs = [sum(r[i][1] for i in pair) for r in (a, b)], [sum(r[i][2] for i in pair) for r in (a, b)]
+        print("  %-18s against %s on the %d states both solved: nodes x %.4f, seconds x %.4f"
+              % (spec + sym_suffix(n, True), spec + sym_suffix(n) if n else "plain", len(pair), nodes[1] / nodes[0], secs[1] / secs[0]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "idastar_probe.txt"))
@@ -226,6 +269,8 @@ def main():
             cube3_leg(args.seconds, args.state_seconds, args.verbose)
         elif args.leg in ("cube3_sym_korf", "cube3_sym_korf7"):
             cube3_sym_leg(args.leg.rsplit("_", 1)[1], args.seconds, args.state_seconds, args.verbose)
+        elif args.leg in ("cube3_dual_korf", "cube3_dual_korf7"):
+            cube3_dual_leg(args.leg.rsplit("_", 1)[1], args.seconds, args.state_seconds, args.verbose)
         else:
             raise ValueError("unknown leg %r" % args.leg)
         return
@@ -235,9 +280,14 @@ def main():
     for leg in args.legs.split(","):
         cmd = ["timeout", "-k", "10", str(LEG_TIMEOUT_S[leg]), sys.executable, os.path.abspath(__file__), "--leg", leg, "--seconds", str(args.seconds),
                "--state_seconds", str(args.state_seconds)] + (["--verbose"] if args.verbose else [])
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
-        lines += ["---- leg %s (exit %d)" % (leg, p.returncode)] + p.stdout.rstrip().split("\n") + [""]
-        print("\n".join(lines[-(len(p.stdout.rstrip().split("\n")) + 2):]), flush=True)
+        print("---- leg %s" % leg, flush=True)
+        p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
+        out = []
+        for ln in p.stdout:  # passed on as it comes: a leg of several minutes is not silent
+            print(ln, end="", flush=True)
+            out.append(ln.rstrip("\n"))
+        p.wait()
+        lines += ["---- leg %s (exit %d)" % (leg, p.returncode)] + out + [""]
         if p.returncode != 0:
             lines.append("leg %s failed: the visit ends here" % leg)
             break
