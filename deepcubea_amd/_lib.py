@@ -642,17 +642,21 @@ def cube3_pdb_eval(states: torch.Tensor, row_kind: int, patterns, tables, out: O
     sym = N in 1..48: the max over the first N images of every pattern as well (include/dca.h, "Symmetric look-ups"); 0: plain.
     dual: the larger of that value at the row and at its inverse (include/dca.h, "Dual look-ups"); without sym, of the plain value."""
     groups, kinds = [g for _, g in patterns], [kind for kind, _ in patterns]
-    if dual:
-        return _pdb_eval("cube3_pdb_eval", "dca_cube3_pdb_eval_dual", states, 54, groups, kinds, _cube3_table_bytes, tables, out,
-                         lambda s, n, ld, m, k, c, ks, t, *rest: lib().dca_cube3_pdb_eval_dual(s, n, ld, row_kind, m, k, c, ks, t, int(sym or 1), *rest))
-    if not sym:
-        return _pdb_eval("cube3_pdb_eval", "dca_cube3_pdb_eval", states, 54, groups, kinds, _cube3_table_bytes, tables, out,
-                         lambda s, n, ld, m, *rest: lib().dca_cube3_pdb_eval(s, n, ld, row_kind, m, *rest))
-    return _pdb_eval("cube3_pdb_eval", "dca_cube3_pdb_eval_sym", states, 54, groups, kinds, _cube3_table_bytes, tables, out,
-                     lambda s, n, ld, m, k, c, ks, t, *rest: lib().dca_cube3_pdb_eval_sym(s, n, ld, row_kind, m, k, c, ks, t, int(sym), *rest))
+    infix, images = _cube3_mode(sym, dual)
+    symbol = "dca_cube3_pdb_eval" + infix
+    return _pdb_eval("cube3_pdb_eval", symbol, states, 54, groups, kinds, _cube3_table_bytes, tables, out,
+                     lambda s, n, ld, m, k, c, ks, t, *rest: getattr(lib(), symbol)(s, n, ld, row_kind, m, k, c, ks, t, *images, *rest))
 
 
 CUBE3_SYMS, CUBE3_SYM_MAX_LOOKUPS = 48, 64  # include/dca.h
+
+
+def _cube3_mode(sym: int, dual: bool):
+    """A cube3 look-up mode's entry points -> (their symbols' infix, the max_images argument they take behind `tables`): plain,
+    the first `sym` images of every pattern, or the dual look-ups (on the patterns alone without sym)."""
+    if dual:
+        return "_dual", (int(sym or 1),)
+    return ("_sym", (int(sym),)) if sym else ("", ())
 
 
 def cube3_pdb_eval_host(rows, row_kind: int, patterns, tables, sym: int = 1, dual: bool = False) -> np.ndarray:
@@ -665,7 +669,8 @@ def cube3_pdb_eval_host(rows, row_kind: int, patterns, tables, sym: int = 1, dua
     _table_sizes("cube3_pdb_eval_host", [_cube3_table_bytes(kind, len(g)) for kind, g in patterns], tables, True)
     (kinds, ids, ks), ptrs, _keep = _idastar_set([g for _, g in patterns], [kind for kind, _ in patterns], tables, True)
     out = np.zeros(len(rows), np.float32)
-    symbol = "dca_cube3_pdb_eval_dual_host" if dual else "dca_cube3_pdb_eval_sym_host"
+    infix, _ = _cube3_mode(sym or 1, dual)  # (no plain host eval: sym = 1 is that value, and the library words sym = 0's refusal)
+    symbol = "dca_cube3_pdb_eval%s_host" % infix
     check(getattr(lib(), symbol)(rows.ctypes.data_as(C.c_void_p), len(rows), rows.shape[1], row_kind, len(patterns), kinds, ids,
                                  ks, ptrs, int(sym), out.ctypes.data_as(C.c_void_p)), symbol)
     return out
@@ -816,15 +821,10 @@ def idastar_cube3(root, patterns, tables, max_nodes: int, sym: int = 0, dual: bo
     dual: h is the larger of that value at the state and at its inverse (include/dca.h, "Dual look-ups")."""
     _table_sizes("idastar_cube3", [_cube3_table_bytes(kind, len(g)) for kind, g in patterns], tables, False)
     (kinds, ids, ks), ptrs, _keep = _idastar_set([g for _, g in patterns], [kind for kind, _ in patterns], tables, False)
-    if dual:
-        return _idastar("dca_idastar_cube3_dual", lambda r, n, *out: lib().dca_idastar_cube3_dual(r, len(patterns), kinds, ids, ks, ptrs,
-                                                                                                  int(sym or 1), n, *out, stream_ptr()),
-                        root, 54, max_nodes)
-    if sym:
-        return _idastar("dca_idastar_cube3_sym", lambda r, n, *out: lib().dca_idastar_cube3_sym(r, len(patterns), kinds, ids, ks, ptrs, int(sym),
-                                                                                                n, *out, stream_ptr()), root, 54, max_nodes)
-    return _idastar("dca_idastar_cube3", lambda r, n, *out: lib().dca_idastar_cube3(r, len(patterns), kinds, ids, ks, ptrs, n, *out,
-                                                                                    stream_ptr()), root, 54, max_nodes)
+    infix, images = _cube3_mode(sym, dual)
+    symbol = "dca_idastar_cube3" + infix
+    return _idastar(symbol, lambda r, n, *out: getattr(lib(), symbol)(r, len(patterns), kinds, ids, ks, ptrs, *images, n, *out, stream_ptr()),
+                    root, 54, max_nodes)
 
 
 def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int, reflect: bool = False, sym: int = 0,
@@ -846,12 +846,11 @@ def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int, ref
         sizes, width = [_pdb_table_bytes(dim, len(g)) for g in patterns], max(dim, 0) ** 2
     _table_sizes("idastar_host", sizes, tables, True)
     (kinds, ids, ks), ptrs, _keep = _idastar_set(groups, families, tables, True)
-    if dual:
-        return _idastar("dca_idastar_host_dual", lambda r, n, *out: lib().dca_idastar_host_dual(r, len(groups), kinds, ids, ks, ptrs,
-                                                                                                int(sym or 1), n, *out), root, width, max_nodes)
-    if sym:
-        return _idastar("dca_idastar_host_sym", lambda r, n, *out: lib().dca_idastar_host_sym(r, len(groups), kinds, ids, ks, ptrs, int(sym),
-                                                                                              n, *out), root, width, max_nodes)
+    infix, images = _cube3_mode(sym, dual)
+    if infix:
+        symbol = "dca_idastar_host" + infix
+        return _idastar(symbol, lambda r, n, *out: getattr(lib(), symbol)(r, len(groups), kinds, ids, ks, ptrs, *images, n, *out),
+                        root, width, max_nodes)
     if reflect:
         return _idastar("dca_idastar_host_reflected", lambda r, n, *out: lib().dca_idastar_host_reflected(dim, r, len(groups), ids, ks, ptrs,
                                                                                                           n, *out), root, width, max_nodes)

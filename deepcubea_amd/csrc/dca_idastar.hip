@@ -14,6 +14,13 @@
 //            over a look-up list in global memory, left at the first value that already prunes the child (BOUNDED).
 //   dual     C3DualDomain: the symmetric search with the dual look-ups (include/dca.h) — where the list at the state does not
 //            prune the child, the lane inverts its two words in registers and reads the list again at the inverse state.
+//   kernels  ida_puzzle_kernel<DIM, REFLECT>, and ONE ida_cube3_kernel<D> for C3Domain, C3SymDomain and C3DualDomain: a domain
+//            names the kernel's argument (Arg), makes a lane's Ctx from the staged move tables and that argument (ctx()), and
+//            carries the kernel's name as messages give it (kernel_name).
+//   host     ida_search<D> is every search's host frame: the root's table bytes, the argument's device memory and a control
+//            block where a search will run on the device, ida_drive's threshold loop around one "device iteration or host lane"
+//            body — the host lane's Ctx through the same D::ctx — and the block handed back.  ida_puzzle, ida_cube3 and
+//            ida_cube3_sym only prepare their family's state, reads and argument.
 //   work     item i of an iteration names a move prefix of P moves, the mixed-radix digits of i (first move = most significant
 //            digit; cube3: radix 12; puzzles: 4 for the first move, then 3 — a digit picks among the moves that do not undo
 //            the one before).  A lane replays the prefix from the root under the pruning rules and the f <= T test and drops the item
@@ -72,10 +79,18 @@ struct PzMapsReflect : PzMaps {  // and tile t -> the same of phi(t), the patter
     uint32_t rp[32];
 };
 
+template <bool REFLECT>
+using PzMapsOf = std::conditional_t<REFLECT, PzMapsReflect, PzMaps>;
+
+template <int DIM, bool REFLECT>
+struct PzArgs;  // the kernel argument, behind the domain: it holds the root
+
 // REFLECT: the reflected look-up (include/dca.h): slots np .. 2 np - 1 of State::idx are the running indices of the state's
 // mirror image in the main diagonal, and h is the larger of the two sums.  Without it nothing below differs from the plain search.
 template <int DIM, bool REFLECT = false>
 struct PzDomain {
+    using Arg = PzArgs<DIM, REFLECT>;
+    static constexpr const char* kernel_name = "ida_puzzle_kernel";
     static constexpr int N = DIM * DIM, NM = 4, RADIX = 3, MOVE_BITS = 2, MAX_PREFIX = 15, STACK_WORDS = 16;
     static constexpr int BITS = N <= 16 ? 4 : 5;
     static constexpr bool BOUNDED = false;  // h(s, c): the whole value, whatever the threshold
@@ -93,6 +108,21 @@ struct PzDomain {
         const uint64_t* rtile_w;  // REFLECT only
         const uint32_t* rtile_p;
     };
+    // what a lane reads: the tile maps where they stand (the kernel's copy in LDS, the host's own) and the argument's tables
+    static DCA_IDA_INLINE Ctx ctx(const PzMapsOf<REFLECT>& maps, const Arg& a) {
+        Ctx c;
+        c.tile_w = maps.w;
+        c.tile_p = maps.p;
+        if constexpr (REFLECT) {
+            c.rtile_w = maps.rw;
+            c.rtile_p = maps.rp;
+        }
+#pragma unroll
+        for (int q = 0; q < kIdaPuzzlePatterns; q++) c.table[q] = a.table[q];
+        c.np = a.np;
+        return c;
+    }
+    static int device_arg(Arg&) { return 0; }  // nothing of the argument is device memory of the search's own
     static constexpr Board MASK = (1u << BITS) - 1u;
     static constexpr Board goal_board() {
         Board b = 0;
@@ -174,6 +204,17 @@ struct C3Domain {
         const uint8_t* mv;  // [2][12][24]: kind, move, location -> location
         const C3Set* set;
     };
+    // Every cube3 domain: Arg, what ida_cube3_kernel<D> is handed; ctx(), what a lane reads, from the move tables where they
+    // stand (LDS, or the host's words) and that argument; device_arg(), whatever of the argument needs a device copy.
+    using Arg = C3Set;
+    static constexpr const char* kernel_name = "ida_cube3_kernel";
+    static DCA_IDA_INLINE Ctx ctx(const uint8_t* mv, const Arg& a) {
+        Ctx c;
+        c.mv = mv;
+        c.set = &a;
+        return c;
+    }
+    static int device_arg(Arg&) { return 0; }
     static constexpr uint64_t home(int n, int o) {
         uint64_t w = 0;
         for (int q = 0; q < n; q++) w |= (uint64_t)(q * o) << (5 * q);
@@ -235,6 +276,17 @@ struct C3SymDomain : C3Domain {
         const C3SymList* list;
         int n;
     };
+    using Arg = C3SymSet;
+    static constexpr const char* kernel_name = "ida_cube3_sym_kernel";
+    static DCA_IDA_INLINE Ctx ctx(const uint8_t* mv, const Arg& a) {
+        Ctx c;
+        c.mv = mv;
+        c.set = nullptr;
+        c.list = a.list;
+        c.n = a.n;
+        return c;
+    }
+    static int device_arg(Arg& a) { return c3_sym_device_list(*a.list, a.list); }
     // The largest byte over the list, or — the early exit — over its first look-ups once that is above `slack` = T - g - 1:
     // f > T either way, so the same children are pruned as under the full maximum; only the f a pruned child records for the
     // next threshold may be smaller than its exact f (include/dca.h: the thresholds of the exact search still all occur).
@@ -258,6 +310,17 @@ struct C3DualDomain : C3SymDomain {
     struct Ctx : C3SymDomain::Ctx {
         C3DualPass dual;
     };
+    using Arg = C3DualSet;
+    static constexpr const char* kernel_name = "ida_cube3_dual_kernel";
+    static DCA_IDA_INLINE Ctx ctx(const uint8_t* mv, const Arg& a) {
+        Ctx c;
+        c.mv = mv;
+        c.set = nullptr;
+        c.list = a.list;
+        c.n = a.n;
+        c.dual = a.dual;
+        return c;
+    }
     static DCA_IDA_INLINE uint32_t h(const State& s, const Ctx& c, uint32_t slack) {
         const uint32_t best = C3SymDomain::h(s, c, slack);
         if (best > slack) return best;
@@ -366,15 +429,12 @@ DCA_IDA_INLINE void ida_lane(const typename D::Ctx& c, const typename D::State& 
 }
 
 // -------------------------------------------------------------------------------------------------------------- kernels
-template <int DIM, bool REFLECT = false>
+template <int DIM, bool REFLECT>
 struct PzArgs {
     typename PzDomain<DIM, REFLECT>::State root;
     const uint8_t* table[kIdaPuzzlePatterns];
     int np;
 };
-
-template <bool REFLECT>
-using PzMapsOf = std::conditional_t<REFLECT, PzMapsReflect, PzMaps>;
 
 template <int DIM, bool REFLECT = false>
 __global__ __launch_bounds__(kIdaThreads) void ida_puzzle_kernel(PzArgs<DIM, REFLECT> args, PzMapsOf<REFLECT> maps, IdaCtrl* ctrl, uint32_t T,
@@ -390,6 +450,8 @@ __global__ __launch_bounds__(kIdaThreads) void ida_puzzle_kernel(PzArgs<DIM, REF
             tile_p[t] = maps.p[t];
         }
     }
+    // (The context is filled here, not by D::ctx: staging the maps as one PzMaps in LDS for it moved the scalar loads and
+    // renumbered the scalar registers of all six kernels, outside the machine-code rule.)
     typename D::Ctx c;
     if constexpr (REFLECT) {  // the second pair of tile maps, staged like the first
         __shared__ uint64_t rtile_w[32];
@@ -417,7 +479,9 @@ struct C3IdaMoves {
     uint32_t w[2 * 12 * kC3Locs / 4];  // both kinds' location-move tables as words
 };
 
-__global__ __launch_bounds__(kIdaThreads) void ida_cube3_kernel(C3Domain::State root, C3Set set, C3IdaMoves mt, IdaCtrl* ctrl, uint32_t T,
+// the plain, the symmetric and the dual search: what differs is the domain's argument and the context made from it
+template <typename D>
+__global__ __launch_bounds__(kIdaThreads) void ida_cube3_kernel(C3Domain::State root, typename D::Arg set, C3IdaMoves mt, IdaCtrl* ctrl, uint32_t T,
                                                                 uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
     __shared__ uint32_t mvw[2 * 12 * kC3Locs / 4];
     __shared__ uint32_t stk[C3Domain::STACK_WORDS * kIdaThreads];
@@ -426,45 +490,7 @@ __global__ __launch_bounds__(kIdaThreads) void ida_cube3_kernel(C3Domain::State 
         for (int q = 0; q < 2 * 12 * kC3Locs / 4; q++) mvw[q] = mt.w[q];
     }
     __syncthreads();
-    C3Domain::Ctx c;
-    c.mv = (const uint8_t*)mvw;
-    c.set = &set;
-    ida_lane<C3Domain>(c, root, ctrl, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
-}
-
-__global__ __launch_bounds__(kIdaThreads) void ida_cube3_sym_kernel(C3Domain::State root, C3SymSet set, C3IdaMoves mt, IdaCtrl* ctrl, uint32_t T,
-                                                                    uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
-    __shared__ uint32_t mvw[2 * 12 * kC3Locs / 4];
-    __shared__ uint32_t stk[C3Domain::STACK_WORDS * kIdaThreads];
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < 2 * 12 * kC3Locs / 4; q++) mvw[q] = mt.w[q];
-    }
-    __syncthreads();
-    C3SymDomain::Ctx c;
-    c.mv = (const uint8_t*)mvw;
-    c.set = nullptr;
-    c.list = set.list;
-    c.n = set.n;
-    ida_lane<C3SymDomain>(c, root, ctrl, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
-}
-
-__global__ __launch_bounds__(kIdaThreads) void ida_cube3_dual_kernel(C3Domain::State root, C3DualSet set, C3IdaMoves mt, IdaCtrl* ctrl, uint32_t T,
-                                                                     uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
-    __shared__ uint32_t mvw[2 * 12 * kC3Locs / 4];
-    __shared__ uint32_t stk[C3Domain::STACK_WORDS * kIdaThreads];
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < 2 * 12 * kC3Locs / 4; q++) mvw[q] = mt.w[q];
-    }
-    __syncthreads();
-    C3DualDomain::Ctx c;
-    c.mv = (const uint8_t*)mvw;
-    c.set = nullptr;
-    c.list = set.list;
-    c.n = set.n;
-    c.dual = set.dual;
-    ida_lane<C3DualDomain>(c, root, ctrl, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
+    ida_lane<D>(D::ctx((const uint8_t*)mvw, set), root, ctrl, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
 }
 
 // ----------------------------------------------------------------------------------------------------------- host side
@@ -612,13 +638,19 @@ static int ida_check_cube3_root(const char* who, const uint8_t* root) {
     return 0;
 }
 
+// a root's 54 sticker ids as the search's state: the two location words
+static C3Domain::State c3_root_state(const uint8_t* root) {
+    uint32_t w[14];
+    pdb_load_row<54, 1>(root, w);
+    return {c3_row_locs<DCA_CUBE3_CORNERS, DCA_ROWS_STATE>(w), c3_row_locs<DCA_CUBE3_EDGES, DCA_ROWS_STATE>(w)};
+}
+
 // The dual search inverts a lane's words in the or-only form (c3_inverse_locs), which needs every cubie of a kind in a slot of
 // its own.  54 distinct sticker ids need not be that (a corner's sticker on an edge): such a root is no cube state — no move
 // sequence takes it to the goal — and is refused.  The moves permute the slots, so the root's property is every node's.
 static int ida_check_cube3_slots(const char* who, const uint8_t* root) {
-    uint32_t w[14];
-    pdb_load_row<54, 1>(root, w);
-    const uint64_t locs[2] = {c3_row_locs<DCA_CUBE3_CORNERS, DCA_ROWS_STATE>(w), c3_row_locs<DCA_CUBE3_EDGES, DCA_ROWS_STATE>(w)};
+    const C3Domain::State s0 = c3_root_state(root);
+    const uint64_t locs[2] = {s0.corner, s0.edge};
     for (int kind = 0; kind < 2; kind++) {
         const int n = kind == DCA_CUBE3_CORNERS ? 8 : 12, o = kind == DCA_CUBE3_CORNERS ? 3 : 2;
         uint32_t seen = 0;
@@ -702,6 +734,44 @@ static int ida_device_iteration(IdaCtrl* dev, IdaCtrl& ctrl, hipStream_t st, con
     return 0;
 }
 
+constexpr int kIdaMaxReads = 2 * kC3SymMaxLookups;  // the root's table bytes: the dual search's two passes over a full list
+
+// The frame every search shares, over its domain D.  root: the root's state; reads, tables, idx: the root's table bytes to
+// read; reduce(v, reads): the family's h of the root from those bytes (any byte >= 0xFE: the root is dead, whatever the family);
+// arg: the kernel's argument as the host lane reads it (D::device_arg makes its device memory, in a copy the launches get);
+// maps: what D::ctx takes beside it on the host; launch(arg, blocks, ctrl, T, P, n_items, budget, poll): the family's kernel.
+// The order of the HIP calls: the root's bytes, the argument's device memory and a control block — both only where a search
+// will run on the device — and per threshold a device iteration (or the host lane); then the block goes back or is freed.
+template <typename D, typename Maps, typename Reduce, typename Launch>
+static int ida_search(const typename D::State& root, int reads, const uint8_t* const* tables, const uint64_t* idx, Reduce reduce,
+                      const typename D::Arg& arg, const Maps& maps, Launch launch, int64_t max_nodes, const IdaOut& out, bool on_device,
+                      hipStream_t st) {
+    uint8_t v[kIdaMaxReads] = {};
+    if (int rc = ida_root_bytes(on_device, reads, tables, idx, st, v)) return rc;
+    bool dead = false;
+    for (int p = 0; p < reads; p++) dead = dead || v[p] >= kPdbInf;
+    const uint32_t h_root = reduce(v, reads);
+    const bool goal = D::goal(root);
+    typename D::Arg dev_arg = arg;
+    IdaCtrl* dev = nullptr;
+    int device = -1;
+    if (on_device && !dead && !goal) {
+        if (int rc = D::device_arg(dev_arg)) return rc;
+        if (int rc = ida_block_take(dev, device)) return rc;
+    }
+    const int rc = ida_drive<D>(h_root, dead, goal, max_nodes, out, [&](uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, IdaCtrl& ctrl) {
+        if (on_device)
+            return ida_device_iteration(dev, ctrl, st, D::kernel_name, [&] {
+                launch(dev_arg, dim3(ida_blocks(n_items)), dev, T, P, n_items, budget, ida_poll(budget, ida_blocks(n_items) * kIdaThreads));
+            });
+        uint32_t stk[D::STACK_WORDS] = {};
+        ida_lane<D>(D::ctx(maps, arg), root, &ctrl, stk, 1u, T, P, n_items, budget, ida_poll(budget, 1));
+        return 0;
+    });
+    ida_block_give(dev, device, rc == 0);
+    return rc;
+}
+
 template <int DIM, bool REFLECT>
 static int ida_puzzle(const uint8_t* root, const PdbSet& set, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
     using D = PzDomain<DIM, REFLECT>;
@@ -740,42 +810,17 @@ static int ida_puzzle(const uint8_t* root, const PdbSet& set, int64_t max_nodes,
             root_idx[set.np + p] = args.root.idx[set.np + p] + pdb_refl<DIM>(args.root.blank);
         }
     }
-    const int slots = REFLECT ? 2 * set.np : set.np;
-    uint8_t v[kIdaPuzzlePatterns] = {};
-    if (int rc = ida_root_bytes(on_device, slots, args.table, root_idx, st, v)) return rc;
-    uint32_t h_root = 0, h_mirror = 0;
-    bool dead = false;
-    for (int p = 0; p < slots; p++) {
-        dead = dead || v[p] >= kPdbInf;
-        (p < set.np ? h_root : h_mirror) += v[p];
-    }
-    h_root = h_root > h_mirror ? h_root : h_mirror;
-    IdaCtrl* dev = nullptr;
-    int device = -1;
-    if (on_device && !dead && !D::goal(args.root))
-        if (int rc = ida_block_take(dev, device)) return rc;
-    const int rc = ida_drive<D>(h_root, dead, D::goal(args.root), max_nodes, out,
-                                [&](uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, IdaCtrl& ctrl) {
-        if (on_device)
-            return ida_device_iteration(dev, ctrl, st, "ida_puzzle_kernel", [&] {
-                hipLaunchKernelGGL((ida_puzzle_kernel<DIM, REFLECT>), dim3(ida_blocks(n_items)), dim3(kIdaThreads), 0, st, args, maps, dev, T, P, n_items, budget,
-                                   ida_poll(budget, ida_blocks(n_items) * kIdaThreads));
-            });
-        typename D::Ctx c;
-        c.tile_w = maps.w;
-        c.tile_p = maps.p;
-        if constexpr (REFLECT) {
-            c.rtile_w = maps.rw;
-            c.rtile_p = maps.rp;
-        }
-        for (int q = 0; q < kIdaPuzzlePatterns; q++) c.table[q] = args.table[q];
-        c.np = args.np;
-        uint32_t stk[D::STACK_WORDS] = {};
-        ida_lane<D>(c, args.root, &ctrl, stk, 1u, T, P, n_items, budget, ida_poll(budget, 1));
-        return 0;
-    });
-    ida_block_give(dev, device, rc == 0);
-    return rc;
+    const auto larger_sum = [&](const uint8_t* v, int slots) {  // the patterns' sum, or the larger of it and the mirror image's
+        uint32_t h_root = 0, h_mirror = 0;
+        for (int p = 0; p < slots; p++) (p < set.np ? h_root : h_mirror) += v[p];
+        return h_root > h_mirror ? h_root : h_mirror;
+    };
+    return ida_search<D>(
+        args.root, REFLECT ? 2 * set.np : set.np, args.table, root_idx, larger_sum, args, maps,
+        [&](const PzArgs<DIM, REFLECT>& arg, dim3 blocks, IdaCtrl* ctrl, uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
+            hipLaunchKernelGGL((ida_puzzle_kernel<DIM, REFLECT>), blocks, dim3(kIdaThreads), 0, st, arg, maps, ctrl, T, P, n_items, budget, poll);
+        },
+        max_nodes, out, on_device, st);
 }
 
 static C3IdaMoves c3_ida_moves() {
@@ -787,19 +832,33 @@ static C3IdaMoves c3_ida_moves() {
     return mt;
 }
 
+// A cube3 search of any family from its root, the root's reads and its argument: h of the root is the largest byte.
+template <typename D>
+static int ida_cube3_search(const C3Domain::State& s0, int reads, const uint8_t* const* tables, const uint64_t* idx, const typename D::Arg& arg,
+                            int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
+    const C3IdaMoves mt = c3_ida_moves();
+    const auto largest = [](const uint8_t* v, int n) {
+        uint32_t h_root = 0;
+        for (int p = 0; p < n; p++) h_root = h_root > v[p] ? h_root : v[p];
+        return h_root;
+    };
+    return ida_search<D>(
+        s0, reads, tables, idx, largest, arg, (const uint8_t*)mt.w,  // little-endian words: byte l of a row is location l
+        [&](const typename D::Arg& a, dim3 blocks, IdaCtrl* ctrl, uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
+            hipLaunchKernelGGL(ida_cube3_kernel<D>, blocks, dim3(kIdaThreads), 0, st, s0, a, mt, ctrl, T, P, n_items, budget, poll);
+        },
+        max_nodes, out, on_device, st);
+}
+
 // The search on the symmetric look-ups: ida_cube3 with the list in place of the set.  The list's tables are device memory
 // (on_device) or host memory; the root's h is the full maximum, and the root is dead where ANY look-up's byte is >= 0xFE.
 // dual: the search on the dual look-ups — the root's bytes are those of the list at the state and, behind them, those of the
 // second pass at the inverse state (every look-up that does not name all the cubies of its kind).
 static int ida_cube3_sym(const uint8_t* root, const C3SymList& list, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st,
                          bool dual = false) {
-    uint32_t w[14];
-    pdb_load_row<54, 1>(root, w);
-    C3Domain::State s0;
-    s0.corner = c3_row_locs<DCA_CUBE3_CORNERS, DCA_ROWS_STATE>(w);
-    s0.edge = c3_row_locs<DCA_CUBE3_EDGES, DCA_ROWS_STATE>(w);
-    uint64_t root_idx[2 * kC3SymMaxLookups] = {};
-    const uint8_t* tables[2 * kC3SymMaxLookups] = {};
+    const C3Domain::State s0 = c3_root_state(root);
+    uint64_t root_idx[kIdaMaxReads] = {};
+    const uint8_t* tables[kIdaMaxReads] = {};
     int reads = 0;
     for (int p = 0; p < list.n; p++, reads++) {
         const C3Lookup& lk = list.lk[p];
@@ -815,94 +874,19 @@ static int ida_cube3_sym(const uint8_t* root, const C3SymList& list, int64_t max
             tables[reads++] = lk.table;
         }
     }
-    uint8_t v[2 * kC3SymMaxLookups] = {};
-    if (int rc = ida_root_bytes(on_device, reads, tables, root_idx, st, v)) return rc;
-    uint32_t h_root = 0;
-    bool dead = false;
-    for (int p = 0; p < reads; p++) {
-        dead = dead || v[p] >= kPdbInf;
-        h_root = h_root > v[p] ? h_root : v[p];
-    }
-    const C3IdaMoves mt = c3_ida_moves();
-    const bool search = !dead && !C3Domain::goal(s0);
-    C3DualSet arg{&list, list.n, list.kinds_used, c3_dual_pass(list)};
-    IdaCtrl* dev = nullptr;
-    int device = -1;
-    if (on_device && search) {
-        if (int rc = c3_sym_device_list(list, arg.list)) return rc;
-        if (int rc = ida_block_take(dev, device)) return rc;
-    }
-    const auto run = [&](auto domain, const char* name, auto launch) {
-        using D = decltype(domain);
-        return ida_drive<D>(h_root, dead, C3Domain::goal(s0), max_nodes, out,
-                            [&](uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, IdaCtrl& ctrl) {
-            if (on_device)
-                return ida_device_iteration(dev, ctrl, st, name, [&] {
-                    launch(dim3(ida_blocks(n_items)), T, P, n_items, budget, ida_poll(budget, ida_blocks(n_items) * kIdaThreads));
-                });
-            typename D::Ctx c;
-            c.mv = (const uint8_t*)mt.w;
-            c.set = nullptr;
-            c.list = &list;
-            c.n = list.n;
-            if constexpr (std::is_same_v<D, C3DualDomain>) c.dual = arg.dual;
-            uint32_t stk[C3Domain::STACK_WORDS] = {};
-            ida_lane<D>(c, s0, &ctrl, stk, 1u, T, P, n_items, budget, ida_poll(budget, 1));
-            return 0;
-        });
-    };
-    const int rc = dual ? run(C3DualDomain{}, "ida_cube3_dual_kernel",
-                              [&](dim3 blocks, uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
-                                  hipLaunchKernelGGL(ida_cube3_dual_kernel, blocks, dim3(kIdaThreads), 0, st, s0, arg, mt, dev, T, P, n_items, budget, poll);
-                              })
-                        : run(C3SymDomain{}, "ida_cube3_sym_kernel",
-                              [&](dim3 blocks, uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
-                                  const C3SymSet sym{arg.list, arg.n, arg.kinds_used};
-                                  hipLaunchKernelGGL(ida_cube3_sym_kernel, blocks, dim3(kIdaThreads), 0, st, s0, sym, mt, dev, T, P, n_items, budget, poll);
-                              });
-    ida_block_give(dev, device, rc == 0);
-    return rc;
+    C3DualSet arg;
+    c3_list_arg(list, arg);
+    return dual ? ida_cube3_search<C3DualDomain>(s0, reads, tables, root_idx, arg, max_nodes, out, on_device, st)
+                : ida_cube3_search<C3SymDomain>(s0, reads, tables, root_idx, arg, max_nodes, out, on_device, st);
 }
 
 static int ida_cube3(const uint8_t* root, const C3Set& set, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
-    uint32_t w[14];
-    pdb_load_row<54, 1>(root, w);
-    C3Domain::State s0;
-    s0.corner = c3_row_locs<DCA_CUBE3_CORNERS, DCA_ROWS_STATE>(w);
-    s0.edge = c3_row_locs<DCA_CUBE3_EDGES, DCA_ROWS_STATE>(w);
+    const C3Domain::State s0 = c3_root_state(root);
     uint64_t root_idx[kPdbMaxPatterns] = {};
     for (int p = 0; p < set.np; p++)
         root_idx[p] = set.kind[p] == DCA_CUBE3_CORNERS ? c3_index<DCA_CUBE3_CORNERS>(s0.corner, set.pat[p], set.k[p])
                                                       : c3_index<DCA_CUBE3_EDGES>(s0.edge, set.pat[p], set.k[p]);
-    uint8_t v[kPdbMaxPatterns] = {};
-    if (int rc = ida_root_bytes(on_device, set.np, set.table, root_idx, st, v)) return rc;
-    uint32_t h_root = 0;
-    bool dead = false;
-    for (int p = 0; p < set.np; p++) {
-        dead = dead || v[p] >= kPdbInf;
-        h_root = h_root > v[p] ? h_root : v[p];
-    }
-    const C3IdaMoves mt = c3_ida_moves();
-    IdaCtrl* dev = nullptr;
-    int device = -1;
-    if (on_device && !dead && !C3Domain::goal(s0))
-        if (int rc = ida_block_take(dev, device)) return rc;
-    const int rc = ida_drive<C3Domain>(h_root, dead, C3Domain::goal(s0), max_nodes, out,
-                                       [&](uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, IdaCtrl& ctrl) {
-        if (on_device)
-            return ida_device_iteration(dev, ctrl, st, "ida_cube3_kernel", [&] {
-                hipLaunchKernelGGL(ida_cube3_kernel, dim3(ida_blocks(n_items)), dim3(kIdaThreads), 0, st, s0, set, mt, dev, T, P, n_items, budget,
-                                   ida_poll(budget, ida_blocks(n_items) * kIdaThreads));
-            });
-        C3Domain::Ctx c;
-        c.mv = (const uint8_t*)mt.w;  // little-endian words: byte l of a row is location l
-        c.set = &set;
-        uint32_t stk[C3Domain::STACK_WORDS] = {};
-        ida_lane<C3Domain>(c, s0, &ctrl, stk, 1u, T, P, n_items, budget, ida_poll(budget, 1));
-        return 0;
-    });
-    ida_block_give(dev, device, rc == 0);
-    return rc;
+    return ida_cube3_search<C3Domain>(s0, set.np, set.table, root_idx, set, max_nodes, out, on_device, st);
 }
 
 // every refusal of a puzzle search, then the search: before any HIP call
@@ -971,14 +955,7 @@ static int ida_cube3_entry(const char* who, const uint8_t* root, int num_pattern
     }
     if (int rc = ida_check_out(who, max_nodes, out)) return rc;
     C3Set set{};
-    if (int rc = pdb_fill_set(
-            who, set, num_patterns, cubies, ks, tables, [&](int p) { return c3_bytes_checked(who, kinds[p], ks[p]); },
-            [&](int p, const uint8_t* c) { return c3_check_cubies(who, kinds[p], c, ks[p]); }))
-        return rc;
-    for (int p = 0; p < num_patterns; p++) {
-        set.kind[p] = (uint8_t)kinds[p];
-        set.kinds_used |= 1 << kinds[p];
-    }
+    if (int rc = c3_fill_set(who, num_patterns, kinds, cubies, ks, tables, set)) return rc;
     if (int rc = ida_check_cube3_root(who, root)) return rc;
     return ida_cube3(root, set, max_nodes, out, on_device, st);
 }

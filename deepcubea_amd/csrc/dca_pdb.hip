@@ -126,16 +126,6 @@ static int pdb_build_launch(uint8_t* table, uint64_t total, int k, const PdbPatt
 }
 
 // ---------------------------------------------------------------------------------------------------------------- eval
-// the eval frame's loop on the CPU: the kernels' own row load and row_value, one row after another (dca_pdb_eval_host)
-template <typename F>
-static void pdb_eval_rows_host(const uint8_t* states, int64_t n, int64_t ld, const PdbSet& set, float* out) {
-    for (int64_t i = 0; i < n; i++) {
-        uint32_t w[(F::N + 3) / 4];
-        pdb_load_row<F::N, 1>(states + i * ld, w);
-        out[i] = (float)F::row_value(w, set);
-    }
-}
-
 template <int DIM>
 static int pdb_eval_run(const uint8_t* states, int64_t n, int64_t ld, const PdbSet& set, float* out, bool reflect, bool host, hipStream_t st) {
     if (host) {

@@ -701,12 +701,17 @@ static C3DualPass c3_dual_pass(const C3SymList& list) {
     return d;
 }
 
-struct C3DualSet {  // the kernel argument
-    const C3SymList* list;
-    int n;
-    int kinds_used;
+struct C3DualSet : C3SymSet {  // the kernel argument
     C3DualPass dual;
 };
+
+// a list's kernel argument, the list where it stands (a device launch then names its device copy, c3_sym_device_list)
+static void c3_list_arg(const C3SymList& list, C3DualSet& arg) {
+    arg.list = &list;
+    arg.n = list.n;
+    arg.kinds_used = list.kinds_used;
+    arg.dual = c3_dual_pass(list);
+}
 
 // the second pass: the largest byte over the look-ups from `lead` on at the inverted words, left at the first value above slack
 DCA_C3_INLINE uint32_t c3_dual_value(const C3SymList* list, int n, int lead, uint64_t corner, uint64_t edge, uint32_t best, uint32_t slack) {
@@ -718,7 +723,9 @@ DCA_C3_INLINE uint32_t c3_dual_value(const C3SymList* list, int n, int lead, uin
     return best;
 }
 
-// what pdb_eval_kernel / pdb_eval_launch take for the dual value: the symmetric value, then the same list at the inverted words
+// what pdb_eval_kernel / pdb_eval_launch take for the dual value: the symmetric value, then the same list at the inverted words.
+// (C3EvalSym's list loop is written out a second time: as one inline function the two share it flipped the dual eval kernels'
+// branch senses, profiles/cube3_lookups_isa.txt.)
 template <int ROWS>
 struct C3EvalDual {
     static constexpr int N = 54;
@@ -778,6 +785,21 @@ static int c3_check_cubies(const char* who, int kind, const uint8_t* cubies, int
     return 0;
 }
 
+// A cube3 entry point's pattern set from its arrays (num_patterns in range, no array NULL: the caller's own refusals): every
+// pattern's size, cubies and table checked, then the kinds.
+static int c3_fill_set(const char* who, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
+                       const uint8_t* const* tables, C3Set& set) {
+    if (int rc = pdb_fill_set(
+            who, set, num_patterns, cubies, ks, tables, [&](int p) { return c3_bytes_checked(who, kinds[p], ks[p]); },
+            [&](int p, const uint8_t* c) { return c3_check_cubies(who, kinds[p], c, ks[p]); }))
+        return rc;
+    for (int p = 0; p < num_patterns; p++) {
+        set.kind[p] = (uint8_t)kinds[p];
+        set.kinds_used |= 1 << kinds[p];
+    }
+    return 0;
+}
+
 // A symmetric entry point's pattern set and look-up list from its arrays: the refusals of dca_cube3_pdb_eval, then those of
 // the list.
 static int c3_fill_sym_entry(const char* who, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
@@ -790,14 +812,7 @@ static int c3_fill_sym_entry(const char* who, int num_patterns, const int* kinds
         set_error("bad argument: %s: kinds, cubies, ks and tables must not be NULL", who);
         return DCA_E_BADARG;
     }
-    if (int rc = pdb_fill_set(
-            who, set, num_patterns, cubies, ks, tables, [&](int p) { return c3_bytes_checked(who, kinds[p], ks[p]); },
-            [&](int p, const uint8_t* c) { return c3_check_cubies(who, kinds[p], c, ks[p]); }))
-        return rc;
-    for (int p = 0; p < num_patterns; p++) {
-        set.kind[p] = (uint8_t)kinds[p];
-        set.kinds_used |= 1 << kinds[p];
-    }
+    if (int rc = c3_fill_set(who, num_patterns, kinds, cubies, ks, tables, set)) return rc;
     return c3_fill_sym_list(who, set, max_images, list);
 }
 

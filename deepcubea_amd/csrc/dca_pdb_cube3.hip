@@ -103,6 +103,62 @@ static int64_t c3_host_index(int kind, const PdbPattern& pat, int k, const uint8
                                      : (int64_t)c3_index<DCA_CUBE3_EDGES>(c3_row_locs<DCA_CUBE3_EDGES, ROWS>(w), pat, k);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- eval
+enum C3Mode { kC3Plain, kC3Sym, kC3Dual };  // which look-ups an eval reads (include/dca.h)
+
+// a family's kernels or the host loop, for rows of sticker ids or of colours
+template <template <int> class F>
+static int c3_eval_run(const uint8_t* states, int64_t n, int64_t ld, int row_kind, const typename F<DCA_ROWS_STATE>::Set& set, float* out,
+                       bool host, hipStream_t st) {
+    if (host) {
+        if (row_kind == DCA_ROWS_STATE)
+            pdb_eval_rows_host<F<DCA_ROWS_STATE>>(states, n, ld, set, out);
+        else
+            pdb_eval_rows_host<F<DCA_ROWS_NNET>>(states, n, ld, set, out);
+        return 0;
+    }
+    return row_kind == DCA_ROWS_STATE ? pdb_eval_launch<F<DCA_ROWS_STATE>>(states, n, ld, set, out, st)
+                                      : pdb_eval_launch<F<DCA_ROWS_NNET>>(states, n, ld, set, out, st);
+}
+
+#define DCA_C3_ARG(cond)                                   \
+    do {                                                   \
+        if (!(cond)) {                                     \
+            set_error("bad argument: %s: %s", who, #cond); \
+            return DCA_E_BADARG;                           \
+        }                                                  \
+    } while (0)
+
+// what the five eval entry points share: every refusal, before any HIP call, then the mode's kernels or the host loop.
+// (max_images is not read in the plain mode; the host loop writes `out` float by float, so only a kernel needs it aligned.)
+static int c3_eval_entry(const char* who, const uint8_t* states, int64_t n, int64_t ld, int row_kind, int num_patterns, const int* kinds,
+                         const uint8_t* cubies, const int* ks, const uint8_t* const* tables, int max_images, float* out, C3Mode mode,
+                         bool host, hipStream_t st) {
+    DCA_C3_ARG(n >= 0 && n < ((int64_t)1 << 31));
+    DCA_C3_ARG(ld >= 54);
+    DCA_C3_ARG(row_kind == DCA_ROWS_STATE || row_kind == DCA_ROWS_NNET);
+    C3Set set{};
+    C3SymList list;
+    if (mode == kC3Plain) {
+        DCA_C3_ARG(num_patterns >= 1 && num_patterns <= 24);
+        DCA_C3_ARG(kinds != nullptr && cubies != nullptr && ks != nullptr && tables != nullptr);
+        if (int rc = c3_fill_set(who, num_patterns, kinds, cubies, ks, tables, set)) return rc;
+    } else if (int rc = c3_fill_sym_entry(who, num_patterns, kinds, cubies, ks, tables, max_images, set, list)) {
+        return rc;
+    }
+    if (n == 0) return 0;
+    DCA_C3_ARG(states != nullptr && out != nullptr);
+    if (!host) DCA_C3_ARG(((uintptr_t)out & 3) == 0);
+    if (mode == kC3Plain) return c3_eval_run<C3Eval>(states, n, ld, row_kind, set, out, host, st);
+    C3DualSet arg;
+    c3_list_arg(list, arg);
+    if (!host)
+        if (int rc = c3_sym_device_list(list, arg.list)) return rc;
+    return mode == kC3Dual ? c3_eval_run<C3EvalDual>(states, n, ld, row_kind, arg, out, host, st)
+                           : c3_eval_run<C3EvalSym>(states, n, ld, row_kind, arg, out, host, st);
+}
+#undef DCA_C3_ARG
+
 }  // namespace dca
 
 using namespace dca;
@@ -148,105 +204,29 @@ int dca_cube3_pdb_build(int kind, const uint8_t* cubies, int k, uint8_t* table, 
 
 int dca_cube3_pdb_eval(const uint8_t* states, int64_t n, int64_t ld, int row_kind, int num_patterns, const int* kinds,
                        const uint8_t* cubies, const int* ks, const uint8_t* const* tables, float* out, void* stream) {
-    DCA_ARG(n >= 0 && n < ((int64_t)1 << 31));
-    DCA_ARG(ld >= 54);
-    DCA_ARG(row_kind == DCA_ROWS_STATE || row_kind == DCA_ROWS_NNET);
-    DCA_ARG(num_patterns >= 1 && num_patterns <= 24);
-    DCA_ARG(kinds != nullptr && cubies != nullptr && ks != nullptr && tables != nullptr);
-    C3Set set{};
-    const char* who = __func__;
-    if (int rc = pdb_fill_set(
-            who, set, num_patterns, cubies, ks, tables, [&](int p) { return c3_bytes_checked(who, kinds[p], ks[p]); },
-            [&](int p, const uint8_t* c) { return c3_check_cubies(who, kinds[p], c, ks[p]); }))
-        return rc;
-    for (int p = 0; p < num_patterns; p++) {
-        set.kind[p] = (uint8_t)kinds[p];
-        set.kinds_used |= 1 << kinds[p];
-    }
-    if (n == 0) return 0;
-    DCA_ARG(states != nullptr && out != nullptr);
-    DCA_ARG(((uintptr_t)out & 3) == 0);
-    hipStream_t st = (hipStream_t)stream;
-    return row_kind == DCA_ROWS_STATE ? pdb_eval_launch<C3Eval<DCA_ROWS_STATE>>(states, n, ld, set, out, st)
-                                      : pdb_eval_launch<C3Eval<DCA_ROWS_NNET>>(states, n, ld, set, out, st);
+    return c3_eval_entry(__func__, states, n, ld, row_kind, num_patterns, kinds, cubies, ks, tables, 0, out, kC3Plain, false, (hipStream_t)stream);
 }
 
 int dca_cube3_pdb_eval_sym(const uint8_t* states, int64_t n, int64_t ld, int row_kind, int num_patterns, const int* kinds,
                            const uint8_t* cubies, const int* ks, const uint8_t* const* tables, int max_images, float* out,
                            void* stream) {
-    DCA_ARG(n >= 0 && n < ((int64_t)1 << 31));
-    DCA_ARG(ld >= 54);
-    DCA_ARG(row_kind == DCA_ROWS_STATE || row_kind == DCA_ROWS_NNET);
-    C3Set set{};
-    C3SymList list;
-    if (int rc = c3_fill_sym_entry(__func__, num_patterns, kinds, cubies, ks, tables, max_images, set, list)) return rc;
-    if (n == 0) return 0;
-    DCA_ARG(states != nullptr && out != nullptr);
-    DCA_ARG(((uintptr_t)out & 3) == 0);
-    C3SymSet arg{nullptr, list.n, list.kinds_used};
-    if (int rc = c3_sym_device_list(list, arg.list)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return row_kind == DCA_ROWS_STATE ? pdb_eval_launch<C3EvalSym<DCA_ROWS_STATE>>(states, n, ld, arg, out, st)
-                                      : pdb_eval_launch<C3EvalSym<DCA_ROWS_NNET>>(states, n, ld, arg, out, st);
+    return c3_eval_entry(__func__, states, n, ld, row_kind, num_patterns, kinds, cubies, ks, tables, max_images, out, kC3Sym, false, (hipStream_t)stream);
 }
 
 int dca_cube3_pdb_eval_sym_host(const uint8_t* states, int64_t n, int64_t ld, int row_kind, int num_patterns, const int* kinds,
                                 const uint8_t* cubies, const int* ks, const uint8_t* const* tables, int max_images, float* out) {
-    DCA_ARG(n >= 0 && n < ((int64_t)1 << 31));
-    DCA_ARG(ld >= 54);
-    DCA_ARG(row_kind == DCA_ROWS_STATE || row_kind == DCA_ROWS_NNET);
-    C3Set set{};
-    C3SymList list;
-    if (int rc = c3_fill_sym_entry(__func__, num_patterns, kinds, cubies, ks, tables, max_images, set, list)) return rc;
-    if (n == 0) return 0;
-    DCA_ARG(states != nullptr && out != nullptr);
-    const C3SymSet arg{&list, list.n, list.kinds_used};
-    for (int64_t i = 0; i < n; i++) {  // the kernel's row load and row value, one row after another
-        uint32_t w[14];
-        pdb_load_row<54, 1>(states + i * ld, w);
-        out[i] = (float)(row_kind == DCA_ROWS_STATE ? C3EvalSym<DCA_ROWS_STATE>::row_value(w, arg)
-                                                    : C3EvalSym<DCA_ROWS_NNET>::row_value(w, arg));
-    }
-    return 0;
+    return c3_eval_entry(__func__, states, n, ld, row_kind, num_patterns, kinds, cubies, ks, tables, max_images, out, kC3Sym, true, nullptr);
 }
 
 int dca_cube3_pdb_eval_dual(const uint8_t* states, int64_t n, int64_t ld, int row_kind, int num_patterns, const int* kinds,
                             const uint8_t* cubies, const int* ks, const uint8_t* const* tables, int max_images, float* out,
                             void* stream) {
-    DCA_ARG(n >= 0 && n < ((int64_t)1 << 31));
-    DCA_ARG(ld >= 54);
-    DCA_ARG(row_kind == DCA_ROWS_STATE || row_kind == DCA_ROWS_NNET);
-    C3Set set{};
-    C3SymList list;
-    if (int rc = c3_fill_sym_entry(__func__, num_patterns, kinds, cubies, ks, tables, max_images, set, list)) return rc;
-    if (n == 0) return 0;
-    DCA_ARG(states != nullptr && out != nullptr);
-    DCA_ARG(((uintptr_t)out & 3) == 0);
-    C3DualSet arg{nullptr, list.n, list.kinds_used, c3_dual_pass(list)};
-    if (int rc = c3_sym_device_list(list, arg.list)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return row_kind == DCA_ROWS_STATE ? pdb_eval_launch<C3EvalDual<DCA_ROWS_STATE>>(states, n, ld, arg, out, st)
-                                      : pdb_eval_launch<C3EvalDual<DCA_ROWS_NNET>>(states, n, ld, arg, out, st);
+    return c3_eval_entry(__func__, states, n, ld, row_kind, num_patterns, kinds, cubies, ks, tables, max_images, out, kC3Dual, false, (hipStream_t)stream);
 }
 
 int dca_cube3_pdb_eval_dual_host(const uint8_t* states, int64_t n, int64_t ld, int row_kind, int num_patterns, const int* kinds,
                                  const uint8_t* cubies, const int* ks, const uint8_t* const* tables, int max_images, float* out) {
-    DCA_ARG(n >= 0 && n < ((int64_t)1 << 31));
-    DCA_ARG(ld >= 54);
-    DCA_ARG(row_kind == DCA_ROWS_STATE || row_kind == DCA_ROWS_NNET);
-    C3Set set{};
-    C3SymList list;
-    if (int rc = c3_fill_sym_entry(__func__, num_patterns, kinds, cubies, ks, tables, max_images, set, list)) return rc;
-    if (n == 0) return 0;
-    DCA_ARG(states != nullptr && out != nullptr);
-    const C3DualSet arg{&list, list.n, list.kinds_used, c3_dual_pass(list)};
-    for (int64_t i = 0; i < n; i++) {  // the kernel's row load and row value, one row after another
-        uint32_t w[14];
-        pdb_load_row<54, 1>(states + i * ld, w);
-        out[i] = (float)(row_kind == DCA_ROWS_STATE ? C3EvalDual<DCA_ROWS_STATE>::row_value(w, arg)
-                                                    : C3EvalDual<DCA_ROWS_NNET>::row_value(w, arg));
-    }
-    return 0;
+    return c3_eval_entry(__func__, states, n, ld, row_kind, num_patterns, kinds, cubies, ks, tables, max_images, out, kC3Dual, true, nullptr);
 }
 
 int dca_cube3_inverse_locs(const uint8_t* row, int row_kind, uint64_t* words) {

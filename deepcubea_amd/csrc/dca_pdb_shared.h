@@ -1,6 +1,6 @@
 // dca_pdb_shared.h — what the pattern-database files share (dca_pdb.hip: sliding puzzles, additive; dca_pdb_cube3.hip: cube3,
 // max): the limits, the set a kernel is handed, the host loop of a build, and the frame of an eval — row load, grid-stride
-// kernel, launcher and the entry points' set filling.  A family supplies the row value (eval) and
+// kernel, launcher, its loop on the CPU and the entry points' set filling.  A family supplies the row value (eval) and
 // the sweep (build); nothing here is dispatched at run time on the device.
 #pragma once
 #include <stdint.h>
@@ -123,6 +123,16 @@ static int pdb_eval_launch(const uint8_t* states, int64_t n, int64_t ld, const t
     else
         hipLaunchKernelGGL((pdb_eval_kernel<F, 1>), dim3(blocks), dim3(kPdbThreads), 0, st, states, n, ld, set, out);
     return launch_check(F::kernel_name);
+}
+
+// the eval frame's loop on the CPU: the kernels' own row load and row_value, one row after another (the *_host entry points)
+template <typename F>
+static void pdb_eval_rows_host(const uint8_t* states, int64_t n, int64_t ld, const typename F::Set& set, float* out) {
+    for (int64_t i = 0; i < n; i++) {
+        uint32_t w[(F::N + 3) / 4];
+        pdb_load_row<F::N, 1>(states + i * ld, w);
+        out[i] = (float)F::row_value(w, set);
+    }
 }
 
 // An eval entry point's set from its arrays, every refusal before any HIP call: per pattern the family's `bytes(p)` (< 0: a
