@@ -78,6 +78,7 @@ _SIGNATURES = {
     "dca_lightsout_exact_solve": "i ipllpp",
     "dca_idastar_npuzzle": "i ipippplpppipppipp",
     "dca_idastar_npuzzle_reflected": "i ipippplpppipppipp",
+    "dca_idastar_npuzzle_batch": "i ipiipppilpppipppipp",
     "dca_idastar_cube3": "i pipppplpppipppipp",
     "dca_idastar_cube3_sym": "i pippppilpppipppipp",
     "dca_idastar_cube3_dual": "i pippppilpppipppipp",
@@ -156,6 +157,7 @@ _SIGNATURES = {
     "dca_debug_tune": "i ii",
     "dca_idastar_host": "i iipipppplpppipppip",
     "dca_idastar_host_reflected": "i ipippplpppipppip",
+    "dca_idastar_host_batch": "i ipiipppilpppipppip",
     "dca_pdb_eval_host": "i ipllipppip",
     "dca_idastar_host_sym": "i pippppilpppipppip",
     "dca_cube3_pdb_eval_sym_host": "i plliippppip",
@@ -747,6 +749,7 @@ IDASTAR_OVERSHOOT = IDASTAR_MAX_LANES * IDASTAR_POLL_NODES  # total_nodes <= max
 IDASTAR_MAX_PREFIX = {ENV_NPUZZLE: 15, ENV_CUBE3: 6}  # moves a work item's prefix has at the most
 IDASTAR_MAX_PUZZLE_PATTERNS = 8
 IDASTAR_MAX_REFLECT_PATTERNS = 4  # a running index and a reflected one per pattern share the 8 a lane keeps
+IDASTAR_MAX_BATCH = 1024  # DCA_IDASTAR_MAX_BATCH: roots of one dca_idastar_npuzzle_batch call
 
 
 def _idastar(symbol: str, call, root, width: int, max_nodes: int) -> dict:
@@ -769,6 +772,31 @@ def _idastar(symbol: str, call, root, width: int, max_nodes: int) -> dict:
     return {"solved": solved, "status": IDASTAR_STATUS[status.value], "moves": [int(m) for m in moves[:length.value]] if solved else [],
             "path_cost": float(length.value) if solved else float("inf"), "nodes_generated": int(total.value),
             "thresholds": [int(t) for t in thresholds[:n]], "nodes_per_threshold": [int(c) for c in per[:n]]}
+
+
+def _idastar_batch(symbol: str, call, roots, width: int, max_nodes: int) -> list:
+    """_idastar for a batch: the roots' bytes [n, width], the output arrays, and one dict per root.  call(roots, n, max_nodes,
+    *outputs) makes the entry point's call."""
+    roots = np.ascontiguousarray(roots, dtype=np.uint8)
+    if roots.ndim != 2 or roots.shape[1] != width:
+        raise ValueError("%s: roots of shape %s, not [n, %d]" % (symbol, tuple(roots.shape), width))
+    n, cap = len(roots), IDASTAR_MAX_MOVES + 2
+    status, length, count = np.full(n, -1, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    total, moves = np.zeros(n, np.int64), np.zeros((n, cap), np.uint8)
+    thresholds, per = np.zeros((n, cap), np.int32), np.zeros((n, cap), np.int64)
+
+    def as_p(a):
+        return a.ctypes.data_as(C.c_void_p)
+    check(call(as_p(roots), n, int(max_nodes), as_p(status), as_p(length), as_p(moves), cap, as_p(count), as_p(thresholds), as_p(per), cap,
+               as_p(total)), symbol)
+    out = []
+    for r in range(n):
+        k, solved = min(int(count[r]), cap), int(status[r]) == IDASTAR_SOLVED
+        out.append({"solved": solved, "status": IDASTAR_STATUS[int(status[r])],
+                    "moves": [int(m) for m in moves[r, :length[r]]] if solved else [],
+                    "path_cost": float(length[r]) if solved else float("inf"), "nodes_generated": int(total[r]),
+                    "thresholds": [int(t) for t in thresholds[r, :k]], "nodes_per_threshold": [int(c) for c in per[r, :k]]})
+    return out
 
 
 def _no_size(family: int, k: int) -> None:
@@ -813,6 +841,24 @@ def idastar_npuzzle(dim: int, root, partition, tables, max_nodes: int, reflect: 
     symbol = "dca_idastar_npuzzle_reflected" if reflect else "dca_idastar_npuzzle"
     return _idastar(symbol, lambda r, n, *out: getattr(lib(), symbol)(dim, r, len(partition), ids, ks, ptrs, n, *out, stream_ptr()),
                     root, max(dim, 0) ** 2, max_nodes)
+
+
+def idastar_npuzzle_batch(dim: int, roots, partition, tables, max_nodes: int, reflect: bool = False) -> list:
+    """A batch of sliding-puzzle roots [n, dim * dim], n in 1..IDASTAR_MAX_BATCH, searched in rounds of one launch each
+    (include/dca.h "batch") -> one dict per root, each what idastar_npuzzle gives for that root alone; max_nodes is per root.
+    Synchronises once per round.  A bad root refuses the whole batch: DcaError, "roots[i]: ..."."""
+    _table_sizes("idastar_npuzzle_batch", [_pdb_table_bytes(dim, len(g)) for g in partition], tables, False)
+    (_, ids, ks), ptrs, _keep = _idastar_set(partition, (dim,) * len(partition), tables, False)
+    return _idastar_batch("dca_idastar_npuzzle_batch", lambda r, n, m, *out: lib().dca_idastar_npuzzle_batch(
+        dim, r, n, len(partition), ids, ks, ptrs, int(bool(reflect)), m, *out, stream_ptr()), roots, max(dim, 0) ** 2, max_nodes)
+
+
+def idastar_host_batch(dim: int, roots, partition, tables, max_nodes: int, reflect: bool = False) -> list:
+    """idastar_npuzzle_batch run on the CPU from HOST tables (include/dca_debug.h): no device needed."""
+    _table_sizes("idastar_host_batch", [_pdb_table_bytes(dim, len(g)) for g in partition], tables, True)
+    (_, ids, ks), ptrs, _keep = _idastar_set(partition, (dim,) * len(partition), tables, True)
+    return _idastar_batch("dca_idastar_host_batch", lambda r, n, m, *out: lib().dca_idastar_host_batch(
+        dim, r, n, len(partition), ids, ks, ptrs, int(bool(reflect)), m, *out), roots, max(dim, 0) ** 2, max_nodes)
 
 
 def idastar_cube3(root, patterns, tables, max_nodes: int, sym: int = 0, dual: bool = False) -> dict:

@@ -21,6 +21,9 @@
 //            block where a search will run on the device, ida_drive's threshold loop around one "device iteration or host lane"
 //            body — the host lane's Ctx through the same D::ctx — and the block handed back.  ida_puzzle, ida_cube3 and
 //            ida_cube3_sym only prepare their family's state, reads and argument.
+//   batch    ida_puzzle_batch: many puzzle roots on one pattern set, one launch of ida_puzzle_batch_kernel<DIM, REFLECT> per
+//            round — the next threshold of every root still searching, each root on its own blocks with its own control block.
+//            A root's thresholds go through the same IdaRun steps as ida_drive's one root, so its results are the single search's.
 //   work     item i of an iteration names a move prefix of P moves, the mixed-radix digits of i (first move = most significant
 //            digit; cube3: radix 12; puzzles: 4 for the first move, then 3 — a digit picks among the moves that do not undo
 //            the one before).  A lane replays the prefix from the root under the pruning rules and the f <= T test and drops the item
@@ -36,8 +39,10 @@
 //
 // Rates are in profiles/idastar_probe.txt; the reflected search against the plain one in profiles/idastar_reflect_probe.txt,
 // the symmetric one in profiles/idastar_sym_probe.txt, the dual one in profiles/idastar_dual_probe.txt.
+#include <cstdio>
 #include <mutex>
 #include <type_traits>
+#include <vector>
 
 #include "dca_pdb_cube3.h"
 #include "dca_pdb_puzzle.h"
@@ -475,6 +480,83 @@ __global__ __launch_bounds__(kIdaThreads) void ida_puzzle_kernel(PzArgs<DIM, REF
     ida_lane<D>(c, args.root, ctrl, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
 }
 
+// A root of a batch as one round's launch reads it (device memory, uploaded in front of every round): the root, what
+// ida_puzzle_kernel takes as launch parameters, and the first of the root's blocks in the round's grid.
+template <int DIM, bool REFLECT>
+struct PzBatchRoot {
+    typename PzDomain<DIM, REFLECT>::State root;
+    unsigned long long budget;
+    uint32_t T, P, n_items, poll;
+    uint32_t first_block;  // ascending over the round's roots, 0 for the first: root j owns first_block[j] .. first_block[j + 1] - 1
+    uint32_t pad;
+};
+
+template <int DIM, bool REFLECT>
+struct PzBatchArgs {
+    const PzBatchRoot<DIM, REFLECT>* roots;  // [n_roots]
+    uint32_t n_roots;                        // >= 1; the grid is the sum of the roots' blocks
+    const uint8_t* table[kIdaPuzzlePatterns];
+    int np;
+};
+
+// One round of a batch: the next threshold of every root still searching, root j on its own blocks with its own control
+// block ctrl[j] — the pattern set and the tile maps are the batch's, staged as ida_puzzle_kernel stages them.  A block finds its
+// root by a binary search of blockIdx.x in the descriptors' first blocks: kernel argument, block index and read-only memory
+// only, so the search, the descriptor and the root sit in scalar registers (profiles/idastar_batch_isa.txt).
+// The grid may be larger than what is resident, and then only queues: after the LDS staging no lane waits for any other lane
+// or block — no barrier, no spin (ida_lane, "work") — so a block that starts late finds its root's item counter where the
+// earlier ones left it, takes what is left or nothing, and ends.  A root that stops (solved, out of budget) closes only its own
+// item counter, in its own control block; the other roots' blocks never read it.
+// (The staging is written out again, not shared with ida_puzzle_kernel: as one inline function of both it moved that kernel's
+// scalar loads in front, parked scalars in a VGPR's lanes and took the reflected kernels from 6 and 5 waves a SIMD to 4.)
+template <int DIM, bool REFLECT = false>
+__global__ __launch_bounds__(kIdaThreads) void ida_puzzle_batch_kernel(PzBatchArgs<DIM, REFLECT> args, PzMapsOf<REFLECT> maps, IdaCtrl* ctrl) {
+    using D = PzDomain<DIM, REFLECT>;
+    __shared__ uint64_t tile_w[32];
+    __shared__ uint32_t tile_p[32];
+    __shared__ uint32_t stk[D::STACK_WORDS * kIdaThreads];
+    const PzBatchRoot<DIM, REFLECT>* __restrict__ roots = args.roots;
+    uint32_t lo = 0, hi = args.n_roots;  // the last root whose first block is <= blockIdx.x (the first root's is 0)
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (roots[mid].first_block <= blockIdx.x)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const typename D::State root = roots[lo].root;  // read in front of every store: scalar loads, as the kernel argument's are
+    const unsigned long long budget = roots[lo].budget;
+    const uint32_t T = roots[lo].T, P = roots[lo].P, n_items = roots[lo].n_items, poll = roots[lo].poll;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int t = 0; t < 32; t++) {
+            tile_w[t] = maps.w[t];
+            tile_p[t] = maps.p[t];
+        }
+    }
+    typename D::Ctx c;
+    if constexpr (REFLECT) {
+        __shared__ uint64_t rtile_w[32];
+        __shared__ uint32_t rtile_p[32];
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int t = 0; t < 32; t++) {
+                rtile_w[t] = maps.rw[t];
+                rtile_p[t] = maps.rp[t];
+            }
+        }
+        c.rtile_w = rtile_w;
+        c.rtile_p = rtile_p;
+    }
+    __syncthreads();
+    c.tile_w = tile_w;
+    c.tile_p = tile_p;
+#pragma unroll
+    for (int q = 0; q < kIdaPuzzlePatterns; q++) c.table[q] = args.table[q];
+    c.np = args.np;
+    ida_lane<D>(c, root, ctrl + lo, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
+}
+
 struct C3IdaMoves {
     uint32_t w[2 * 12 * kC3Locs / 4];  // both kinds' location-move tables as words
 };
@@ -532,45 +614,65 @@ static uint32_t ida_poll(unsigned long long budget, int lanes) {
     return (uint32_t)(p < 1 ? 1 : p < kIdaPoll ? p : kIdaPoll);
 }
 
-// The threshold loop both searches share.  run(T, P, n_items, budget, ctrl) runs one iteration and fills `ctrl` (host copy).
-template <typename D, typename Run>
-static int ida_drive(uint32_t h_root, bool root_dead, bool root_goal, int64_t max_nodes, const IdaOut& out, Run run) {
-    *out.status = DCA_IDASTAR_UNSOLVABLE;
-    *out.length = 0;
-    *out.num_thresholds = 0;
-    *out.total_nodes = 0;
-    if (root_dead) return 0;  // a table says the goal cannot be reached from the root
-    if (root_goal) {
-        *out.status = DCA_IDASTAR_SOLVED;
-        return 0;
+// One root's threshold loop as a state: what ida_drive keeps for its one root, and the batch driver per root.
+struct IdaRun {
+    IdaOut out;
+    int64_t max_nodes, total, prev;  // prev: the count of the threshold before (0 in front of the first), what the prefix rule reads
+    uint32_t T;                      // the next threshold
+    int it;                          // thresholds run
+    bool active;                     // a next threshold is to run
+
+    // The root's outputs in front of any threshold; the search is over at once for a dead root and for the goal.
+    void begin(uint32_t h_root, bool root_dead, bool root_goal, int64_t nodes, const IdaOut& o) {
+        out = o;
+        max_nodes = nodes;
+        total = prev = 0;
+        T = h_root;
+        it = 0;
+        *out.status = DCA_IDASTAR_UNSOLVABLE;
+        *out.length = 0;
+        *out.num_thresholds = 0;
+        *out.total_nodes = 0;
+        if (root_goal && !root_dead) *out.status = DCA_IDASTAR_SOLVED;
+        active = !root_dead && !root_goal && T <= kIdaMaxT;  // (dead: a table says the goal cannot be reached from the root)
     }
-    int64_t total = 0, prev = 0;
-    uint32_t T = h_root;
-    for (int it = 0; T <= kIdaMaxT; it++) {
-        const uint32_t P = ida_prefix<D>(prev);
-        const uint32_t n_items = ida_items<D>(P);
-        IdaCtrl ctrl{};
-        if (int rc = run(T, P, n_items, (unsigned long long)(max_nodes - total), ctrl)) return rc;
+    unsigned long long budget() const { return (unsigned long long)(max_nodes - total); }
+    // Takes threshold T's control block: totals, status, and the next T or the end.
+    void step(const IdaCtrl& ctrl) {
         prev = (int64_t)ctrl.nodes;
         total += prev;
         if (it < out.thresholds_cap) {
             out.thresholds[it] = (int)T;
             out.nodes_per_threshold[it] = prev;
         }
-        *out.num_thresholds = it + 1;
+        *out.num_thresholds = ++it;
         *out.total_nodes = total;
+        active = false;
         if (ctrl.stop & kIdaSolved) {
             *out.status = DCA_IDASTAR_SOLVED;
             *out.length = (int)ctrl.length;
             for (int d = 0; d < (int)ctrl.length && d < out.moves_cap; d++) out.moves[d] = ctrl.moves[d];
-            return 0;
+            return;
         }
         if ((ctrl.stop & kIdaBudget) || total >= max_nodes) {
             *out.status = DCA_IDASTAR_BUDGET;
-            return 0;
+            return;
         }
-        if (ctrl.best == 0u) return 0;  // no child above the threshold: the whole space was searched
+        if (ctrl.best == 0u) return;  // no child above the threshold: the whole space was searched
         T = 0xFFFFFFFFu - ctrl.best;
+        active = T <= kIdaMaxT;
+    }
+};
+
+// The threshold loop of one root.  run(T, P, n_items, budget, ctrl) runs one iteration and fills `ctrl` (host copy).
+template <typename D, typename Run>
+static int ida_drive(uint32_t h_root, bool root_dead, bool root_goal, int64_t max_nodes, const IdaOut& out, Run run) {
+    IdaRun r;
+    for (r.begin(h_root, root_dead, root_goal, max_nodes, out); r.active;) {
+        const uint32_t P = ida_prefix<D>(r.prev);
+        IdaCtrl ctrl{};
+        if (int rc = run(r.T, P, ida_items<D>(P), r.budget(), ctrl)) return rc;
+        r.step(ctrl);
     }
     return 0;
 }
@@ -595,19 +697,19 @@ static int ida_check_out(const char* who, int64_t max_nodes, const IdaOut& o) {
     return 0;
 }
 
-// the root's bytes: a permutation of 0..N-1 of the goal's parity, or a refusal
-static int ida_check_puzzle_root(const char* who, int dim, const uint8_t* root) {
+// the root's bytes: a permutation of 0..N-1 of the goal's parity, or a refusal that names it as `what`
+static int ida_check_puzzle_root(const char* who, int dim, const uint8_t* root, const char* what = "root") {
     const int N = dim * dim;
     uint64_t seen = 0;
     int blank = 0;
     for (int i = 0; i < N; i++) {
         const int t = root[i];
         if (t >= N) {
-            set_error("bad argument: %s: root: byte %d at position %d is not a tile of a %d x %d board", who, t, i, dim, dim);
+            set_error("bad argument: %s: %s: byte %d at position %d is not a tile of a %d x %d board", who, what, t, i, dim, dim);
             return DCA_E_BADARG;
         }
         if ((seen >> t) & 1) {
-            set_error("bad argument: %s: root: tile %d appears twice", who, t);
+            set_error("bad argument: %s: %s: tile %d appears twice", who, what, t);
             return DCA_E_BADARG;
         }
         seen |= 1ull << t;
@@ -619,7 +721,7 @@ static int ida_check_puzzle_root(const char* who, int dim, const uint8_t* root) 
     // a horizontal blank move keeps the tiles' order; a vertical one carries a tile past dim - 1 others
     const int parity = (inv + (dim % 2 == 0 ? dim - 1 - blank / dim : 0)) & 1;
     if (parity) {
-        set_error("bad argument: %s: root: the permutation has the wrong parity, the goal cannot be reached from it", who);
+        set_error("bad argument: %s: %s: the permutation has the wrong parity, the goal cannot be reached from it", who, what);
         return DCA_E_BADARG;
     }
     return 0;
@@ -675,14 +777,20 @@ static int ida_blocks(uint32_t n_items) {
     return (int)(b < (uint32_t)cap ? b : (uint32_t)cap);
 }
 
+// queues the copies of one root's table bytes out of device memory; the caller synchronises, after a failure too
+static hipError_t ida_root_bytes_queue(int np, const uint8_t* const* table, const uint64_t* idx, hipStream_t st, uint8_t* v) {
+    hipError_t e = hipSuccess;
+    for (int p = 0; p < np && e == hipSuccess; p++) e = hipMemcpyAsync(v + p, table[p] + idx[p], 1, hipMemcpyDeviceToHost, st);
+    return e;
+}
+
 // The root's table bytes, v[p] = table[p][idx[p]]: device memory (the copies queued, then one synchronise) or host memory.
 static int ida_root_bytes(bool on_device, int np, const uint8_t* const* table, const uint64_t* idx, hipStream_t st, uint8_t* v) {
     if (!on_device) {
         for (int p = 0; p < np; p++) v[p] = table[p][idx[p]];
         return 0;
     }
-    hipError_t e = hipSuccess;
-    for (int p = 0; p < np && e == hipSuccess; p++) e = hipMemcpyAsync(v + p, table[p] + idx[p], 1, hipMemcpyDeviceToHost, st);
+    hipError_t e = ida_root_bytes_queue(np, table, idx, st, v);
     const hipError_t sync = hipStreamSynchronize(st);  // also after a failure: no copy into v is left pending
     if (e == hipSuccess) e = sync;
     return e == hipSuccess ? 0 : hip_fail(e, "IDA*: the root's table bytes");
@@ -772,15 +880,17 @@ static int ida_search(const typename D::State& root, int reads, const uint8_t* c
     return rc;
 }
 
+// A pattern set and one root's bytes as the search reads them: the tile maps and the table slots (the set's alone, whatever
+// the root), and the root's state with the table index of each of its `reads` root bytes.
 template <int DIM, bool REFLECT>
-static int ida_puzzle(const uint8_t* root, const PdbSet& set, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
+static void pz_prepare(const uint8_t* root, const PdbSet& set, PzMapsOf<REFLECT>& maps, PzArgs<DIM, REFLECT>& args, uint64_t* root_idx) {
     using D = PzDomain<DIM, REFLECT>;
     constexpr int N = D::N;
-    PzMapsOf<REFLECT> maps{};
+    maps = {};
     for (int t = 0; t < 32; t++) maps.p[t] = 0xFFu;
     if constexpr (REFLECT)
         for (int t = 0; t < 32; t++) maps.rp[t] = 0xFFu;
-    PzArgs<DIM, REFLECT> args{};
+    args = {};
     args.np = set.np;
     int pos[N];
     for (int i = 0; i < N; i++) {
@@ -788,7 +898,6 @@ static int ida_puzzle(const uint8_t* root, const PdbSet& set, int64_t max_nodes,
         args.root.board |= (typename D::Board)root[i] << (D::BITS * i);
     }
     args.root.blank = (uint32_t)pos[0];
-    uint64_t root_idx[kIdaPuzzlePatterns] = {};
     for (int p = 0; p < set.np; p++) {
         uint64_t w = N;  // the blank is digit 0, tiles[j] digit j + 1
         for (int j = 0; j < set.k[p]; j++, w *= N) {
@@ -810,17 +919,140 @@ static int ida_puzzle(const uint8_t* root, const PdbSet& set, int64_t max_nodes,
             root_idx[set.np + p] = args.root.idx[set.np + p] + pdb_refl<DIM>(args.root.blank);
         }
     }
-    const auto larger_sum = [&](const uint8_t* v, int slots) {  // the patterns' sum, or the larger of it and the mirror image's
-        uint32_t h_root = 0, h_mirror = 0;
-        for (int p = 0; p < slots; p++) (p < set.np ? h_root : h_mirror) += v[p];
-        return h_root > h_mirror ? h_root : h_mirror;
-    };
+}
+
+// h of a puzzle root from its bytes: the patterns' sum, or the larger of it and the mirror image's
+static uint32_t pz_larger_sum(const uint8_t* v, int slots, int np) {
+    uint32_t h_root = 0, h_mirror = 0;
+    for (int p = 0; p < slots; p++) (p < np ? h_root : h_mirror) += v[p];
+    return h_root > h_mirror ? h_root : h_mirror;
+}
+
+template <int DIM, bool REFLECT>
+static int ida_puzzle(const uint8_t* root, const PdbSet& set, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
+    using D = PzDomain<DIM, REFLECT>;
+    PzMapsOf<REFLECT> maps;
+    PzArgs<DIM, REFLECT> args;
+    uint64_t root_idx[kIdaPuzzlePatterns] = {};
+    pz_prepare<DIM, REFLECT>(root, set, maps, args, root_idx);
+    const auto larger_sum = [&](const uint8_t* v, int slots) { return pz_larger_sum(v, slots, set.np); };
     return ida_search<D>(
         args.root, REFLECT ? 2 * set.np : set.np, args.table, root_idx, larger_sum, args, maps,
         [&](const PzArgs<DIM, REFLECT>& arg, dim3 blocks, IdaCtrl* ctrl, uint32_t T, uint32_t P, uint32_t n_items, unsigned long long budget, uint32_t poll) {
             hipLaunchKernelGGL((ida_puzzle_kernel<DIM, REFLECT>), blocks, dim3(kIdaThreads), 0, st, arg, maps, ctrl, T, P, n_items, budget, poll);
         },
         max_nodes, out, on_device, st);
+}
+
+// root r's outputs out of the batch's arrays
+static IdaOut ida_out_at(const IdaOut& o, int r) {
+    const size_t m = (size_t)r * (size_t)o.moves_cap, t = (size_t)r * (size_t)o.thresholds_cap;
+    return {o.status + r, o.length + r, o.moves ? o.moves + m : nullptr, o.moves_cap, o.num_thresholds + r,
+            o.thresholds ? o.thresholds + t : nullptr, o.nodes_per_threshold ? o.nodes_per_threshold + t : nullptr, o.thresholds_cap,
+            o.total_nodes + r};
+}
+
+// A batch of puzzle roots on one pattern set (include/dca.h "batches"): ida_search's frame with an IdaRun per root and rounds in
+// place of one root's thresholds.  A round is the next threshold of every root still active, each with the T, P, items,
+// budget, poll interval and blocks its single search would give it.  The order of the HIP calls: every root's table bytes
+// queued and one synchronise; the control blocks and the descriptors in one allocation (only where a root is active); per
+// round one memset of the round's control blocks, one upload of its descriptors, one launch, one read-back, one synchronise;
+// the free.  The host twin runs a round's roots one after the other on ida_lane, as ida_search does its one root.
+// P is the single search's rule on the root's own previous count.  A shallower one for batches — the deepest P whose items
+// times the round's roots pass D::worth, fewer items a root wasting less replay — was measured and was slower at every batch
+// size (profiles/idastar_batch_probe.txt): the deep prefix is also what balances a round whose roots differ a thousandfold.
+template <int DIM, bool REFLECT>
+static int ida_puzzle_batch(const uint8_t* roots, int n_roots, const PdbSet& set, int64_t max_nodes, const IdaOut& out, bool on_device,
+                            hipStream_t st) {
+    using D = PzDomain<DIM, REFLECT>;
+    using Root = PzBatchRoot<DIM, REFLECT>;
+    const int reads = REFLECT ? 2 * set.np : set.np;
+    PzMapsOf<REFLECT> maps;
+    PzArgs<DIM, REFLECT> args;
+    std::vector<typename D::State> state((size_t)n_roots);
+    std::vector<uint8_t> v((size_t)n_roots * kIdaPuzzlePatterns);
+    hipError_t e = hipSuccess;
+    for (int r = 0; r < n_roots; r++) {
+        uint64_t root_idx[kIdaPuzzlePatterns] = {};
+        pz_prepare<DIM, REFLECT>(roots + (size_t)r * D::N, set, maps, args, root_idx);
+        state[r] = args.root;
+        uint8_t* bytes = v.data() + (size_t)r * kIdaPuzzlePatterns;
+        if (!on_device)
+            for (int p = 0; p < reads; p++) bytes[p] = args.table[p][root_idx[p]];
+        else if (e == hipSuccess)
+            e = ida_root_bytes_queue(reads, args.table, root_idx, st, bytes);
+    }
+    if (on_device) {
+        const hipError_t sync = hipStreamSynchronize(st);  // also after a failure: no copy into v is left pending
+        if (e == hipSuccess) e = sync;
+        if (e != hipSuccess) return hip_fail(e, "IDA*: the roots' table bytes");
+    }
+    std::vector<IdaRun> run((size_t)n_roots);
+    bool any = false;
+    for (int r = 0; r < n_roots; r++) {
+        const uint8_t* bytes = v.data() + (size_t)r * kIdaPuzzlePatterns;
+        bool dead = false;
+        for (int p = 0; p < reads; p++) dead = dead || bytes[p] >= kPdbInf;
+        run[r].begin(pz_larger_sum(bytes, reads, set.np), dead, D::goal(state[r]), max_nodes, ida_out_at(out, r));
+        any = any || run[r].active;
+    }
+    if (!any) return 0;
+    std::vector<Root> desc((size_t)n_roots);
+    std::vector<IdaCtrl> ctrl((size_t)n_roots);
+    std::vector<int> slot((size_t)n_roots);  // the round's j-th root
+    constexpr size_t kCtrlBytes = sizeof(IdaCtrl), kRootBytes = sizeof(Root);
+    static_assert(kCtrlBytes % 16 == 0, "the descriptors stand behind the control blocks");
+    IdaCtrl* dev_ctrl = nullptr;
+    if (on_device) DCA_HIP(hipMalloc((void**)&dev_ctrl, (size_t)n_roots * (kCtrlBytes + kRootBytes)));
+    Root* dev_desc = on_device ? (Root*)(dev_ctrl + n_roots) : nullptr;
+    const auto round = [&](int n, uint32_t blocks) -> int {
+        if (!on_device) {
+            const typename D::Ctx c = D::ctx(maps, args);
+            for (int j = 0; j < n; j++) {
+                uint32_t stk[D::STACK_WORDS] = {};
+                ctrl[j] = IdaCtrl{};
+                ida_lane<D>(c, desc[j].root, &ctrl[j], stk, 1u, desc[j].T, desc[j].P, desc[j].n_items, desc[j].budget, desc[j].poll);
+            }
+            return 0;
+        }
+        PzBatchArgs<DIM, REFLECT> a{};
+        a.roots = dev_desc;
+        a.n_roots = (uint32_t)n;
+        for (int q = 0; q < kIdaPuzzlePatterns; q++) a.table[q] = args.table[q];
+        a.np = args.np;
+        DCA_HIP(hipMemsetAsync(dev_ctrl, 0, (size_t)n * kCtrlBytes, st));
+        DCA_HIP(hipMemcpyAsync(dev_desc, desc.data(), (size_t)n * kRootBytes, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL((ida_puzzle_batch_kernel<DIM, REFLECT>), dim3(blocks), dim3(kIdaThreads), 0, st, a, maps, dev_ctrl);
+        if (int rc = launch_check("ida_puzzle_batch_kernel")) return rc;
+        DCA_HIP(hipMemcpyAsync(ctrl.data(), dev_ctrl, (size_t)n * kCtrlBytes, hipMemcpyDeviceToHost, st));
+        DCA_HIP(hipStreamSynchronize(st));
+        return 0;
+    };
+    int rc = 0;
+    while (rc == 0) {
+        int n = 0;
+        uint32_t blocks = 0;
+        for (int r = 0; r < n_roots; r++) {
+            if (!run[r].active) continue;
+            Root& d = desc[n];
+            d = Root{};
+            d.root = state[r];
+            d.budget = run[r].budget();
+            d.T = run[r].T;
+            d.P = ida_prefix<D>(run[r].prev);
+            d.n_items = ida_items<D>(d.P);
+            const int own = on_device ? ida_blocks(d.n_items) : 1;
+            d.poll = ida_poll(d.budget, on_device ? own * kIdaThreads : 1);
+            d.first_block = blocks;
+            blocks += (uint32_t)own;
+            slot[n++] = r;
+        }
+        if (n == 0) break;  // every root has left the batch
+        rc = round(n, blocks);
+        for (int j = 0; j < n && rc == 0; j++) run[slot[j]].step(ctrl[j]);
+    }
+    if (dev_ctrl != nullptr) (void)hipFree(dev_ctrl);  // (after an error a launch may still be writing: the free waits for it)
+    return rc;
 }
 
 static C3IdaMoves c3_ida_moves() {
@@ -889,10 +1121,9 @@ static int ida_cube3(const uint8_t* root, const C3Set& set, int64_t max_nodes, c
     return ida_cube3_search<C3Domain>(s0, set.np, set.table, root_idx, set, max_nodes, out, on_device, st);
 }
 
-// every refusal of a puzzle search, then the search: before any HIP call
-static int ida_npuzzle_entry(const char* who, int dim, const uint8_t* root, int num_patterns, const uint8_t* tiles, const int* ks,
-                             const uint8_t* const* tables, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st,
-                             bool reflect = false) {
+// every refusal of a puzzle search but the root's own (root: the root, or a batch's roots), and the pattern set
+static int ida_npuzzle_set(const char* who, int dim, const uint8_t* root, int num_patterns, const uint8_t* tiles, const int* ks,
+                           const uint8_t* const* tables, int64_t max_nodes, const IdaOut& out, bool reflect, PdbSet& set) {
     if (dim < 3 || dim > 7) {
         set_error("bad argument: %s: dim: unsupported puzzle dim %d (3..5)", who, dim);
         return DCA_E_BADARG;
@@ -917,18 +1148,25 @@ static int ida_npuzzle_entry(const char* who, int dim, const uint8_t* root, int 
     }
     if (int rc = ida_check_out(who, max_nodes, out)) return rc;
     const int N = dim * dim;
-    PdbSet set{};
+    set = {};
     uint64_t seen = 0;
-    if (int rc = pdb_fill_set(
-            who, set, num_patterns, tiles, ks, tables, [&](int p) { return pdb_bytes_checked(who, dim, ks[p]); },
-            [&](int p, const uint8_t* t) {
-                if (ks[p] > kPdbMaxK) {
-                    set_error("bad argument: %s: ks: pattern %d has %d tiles, over %d", who, p, ks[p], kPdbMaxK);
-                    return DCA_E_BADARG;
-                }
-                return pdb_check_tiles(who, N, t, ks[p], seen);
-            }))
-        return rc;
+    return pdb_fill_set(
+        who, set, num_patterns, tiles, ks, tables, [&](int p) { return pdb_bytes_checked(who, dim, ks[p]); },
+        [&](int p, const uint8_t* t) {
+            if (ks[p] > kPdbMaxK) {
+                set_error("bad argument: %s: ks: pattern %d has %d tiles, over %d", who, p, ks[p], kPdbMaxK);
+                return DCA_E_BADARG;
+            }
+            return pdb_check_tiles(who, N, t, ks[p], seen);
+        });
+}
+
+// every refusal of a puzzle search, then the search: before any HIP call
+static int ida_npuzzle_entry(const char* who, int dim, const uint8_t* root, int num_patterns, const uint8_t* tiles, const int* ks,
+                             const uint8_t* const* tables, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st,
+                             bool reflect = false) {
+    PdbSet set;
+    if (int rc = ida_npuzzle_set(who, dim, root, num_patterns, tiles, ks, tables, max_nodes, out, reflect, set)) return rc;
     if (int rc = ida_check_puzzle_root(who, dim, root)) return rc;
     if (reflect)
         switch (dim) {
@@ -940,6 +1178,34 @@ static int ida_npuzzle_entry(const char* who, int dim, const uint8_t* root, int 
         case 3: return ida_puzzle<3, false>(root, set, max_nodes, out, on_device, st);
         case 4: return ida_puzzle<4, false>(root, set, max_nodes, out, on_device, st);
         default: return ida_puzzle<5, false>(root, set, max_nodes, out, on_device, st);
+    }
+}
+
+// every refusal of a batch of puzzle searches, a bad root by its index, then the batch: before any HIP call and any output
+static int ida_npuzzle_batch_entry(const char* who, int dim, const uint8_t* roots, int n_roots, int num_patterns, const uint8_t* tiles,
+                                   const int* ks, const uint8_t* const* tables, bool reflect, int64_t max_nodes, const IdaOut& out,
+                                   bool on_device, hipStream_t st) {
+    if (n_roots < 1 || n_roots > DCA_IDASTAR_MAX_BATCH) {
+        set_error("bad argument: %s: n_roots = %d is not in 1..%d", who, n_roots, DCA_IDASTAR_MAX_BATCH);
+        return DCA_E_BADARG;
+    }
+    PdbSet set;
+    if (int rc = ida_npuzzle_set(who, dim, roots, num_patterns, tiles, ks, tables, max_nodes, out, reflect, set)) return rc;
+    for (int r = 0; r < n_roots; r++) {
+        char what[32];
+        snprintf(what, sizeof(what), "roots[%d]", r);
+        if (int rc = ida_check_puzzle_root(who, dim, roots + (size_t)r * (size_t)(dim * dim), what)) return rc;
+    }
+    if (reflect)
+        switch (dim) {
+            case 3: return ida_puzzle_batch<3, true>(roots, n_roots, set, max_nodes, out, on_device, st);
+            case 4: return ida_puzzle_batch<4, true>(roots, n_roots, set, max_nodes, out, on_device, st);
+            default: return ida_puzzle_batch<5, true>(roots, n_roots, set, max_nodes, out, on_device, st);
+        }
+    switch (dim) {
+        case 3: return ida_puzzle_batch<3, false>(roots, n_roots, set, max_nodes, out, on_device, st);
+        case 4: return ida_puzzle_batch<4, false>(roots, n_roots, set, max_nodes, out, on_device, st);
+        default: return ida_puzzle_batch<5, false>(roots, n_roots, set, max_nodes, out, on_device, st);
     }
 }
 
@@ -997,6 +1263,24 @@ int dca_idastar_npuzzle_reflected(int dim, const uint8_t* root, int num_patterns
                                   int64_t* total_nodes, void* stream) {
     const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
     return ida_npuzzle_entry(__func__, dim, root, num_patterns, tiles, ks, tables, max_nodes, out, true, (hipStream_t)stream, true);
+}
+
+int dca_idastar_npuzzle_batch(int dim, const uint8_t* roots, int n_roots, int num_patterns, const uint8_t* tiles, const int* ks,
+                              const uint8_t* const* tables, int reflect, int64_t max_nodes, int* status, int* length, uint8_t* moves,
+                              int moves_cap, int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap,
+                              int64_t* total_nodes, void* stream) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    return ida_npuzzle_batch_entry(__func__, dim, roots, n_roots, num_patterns, tiles, ks, tables, reflect != 0, max_nodes, out, true,
+                                   (hipStream_t)stream);
+}
+
+int dca_idastar_host_batch(int dim, const uint8_t* roots, int n_roots, int num_patterns, const uint8_t* tiles, const int* ks,
+                           const uint8_t* const* tables, int reflect, int64_t max_nodes, int* status, int* length, uint8_t* moves,
+                           int moves_cap, int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap,
+                           int64_t* total_nodes) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    return ida_npuzzle_batch_entry(__func__, dim, roots, n_roots, num_patterns, tiles, ks, tables, reflect != 0, max_nodes, out, false,
+                                   nullptr);
 }
 
 int dca_idastar_cube3(const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,

@@ -8,7 +8,11 @@ stack per lane and runs as long as its node budget lets it.  With an admissible 
 included — the solution is optimal.  results.pkl has astar.py's format and keys (utils/compare_solutions.py reads it); idastar.pkl next to it holds, per
 state, `solved`, `status`, `thresholds` and `nodes_per_threshold`.  A state that ends on "budget exhausted" is reported and
 recorded as unsolved — an empty solution in results.pkl, solved = False in idastar.pkl — and the search goes on to the next; so
-is a state whose root the library refuses (wrong parity, no permutation), with status "refused (...)"."""
+is a state whose root the library refuses (wrong parity, no permutation), with status "refused (...)".
+
+`--batch K` (sliding puzzles, opt-in) searches the states in groups of K as batches of roots: one launch per round runs the next
+threshold of every state of the group that is still searching (include/dca.h, dca_idastar_npuzzle_batch).  Every state's result
+is what its single search gives; the files keep their formats, and `times` holds a group's wall seconds over its size."""
 from __future__ import annotations
 
 import os
@@ -86,11 +90,53 @@ class IDAStar:
             return _lib.idastar_cube3(root, self.pdb.patterns, self.pdb.tables, max_nodes, sym=self.pdb.sym, dual=self.pdb.dual)
         return _lib.idastar_npuzzle(self.dim, root, self.pdb.partition, self.pdb.tables, max_nodes, reflect=self.pdb.reflect)
 
+    def solve_batch(self, roots, max_nodes: int = None) -> List[Dict[str, Any]]:
+        """A batch of 1 .. IDASTAR_MAX_BATCH sliding-puzzle roots searched in rounds, one launch per round (include/dca.h
+        "batch") -> per root what solve() gives for it alone; max_nodes is per root.  One refused root refuses the whole batch:
+        DcaError, "roots[i]: ...".  ValueError on cube3: a cube3 search of a shipped state fills the chip by itself."""
+        if self.env == _lib.ENV_CUBE3:
+            raise ValueError("IDA*: a batch of roots is searched on the sliding puzzles only; a cube3 search fills the chip by itself")
+        if max_nodes is None:
+            max_nodes = default_max_nodes(self.env_name)
+        return _lib.idastar_npuzzle_batch(self.dim, roots, self.pdb.partition, self.pdb.tables, max_nodes, reflect=self.pdb.reflect)
+
 
 def refused_root(err: Exception) -> Dict[str, Any]:
     """The result the CLI records for a root the library refuses (wrong parity, no permutation): unsolved, nothing searched."""
     return {"solved": False, "status": "refused (%s)" % str(err).split("bad argument: ", 1)[-1], "moves": [], "path_cost": float("inf"),
             "nodes_generated": 0, "thresholds": [], "nodes_per_threshold": []}
+
+
+def solve_one(search: IDAStar, root, max_nodes: int) -> Dict[str, Any]:
+    """The single search of one root; a root the library refuses is a result (refused_root), any other error is raised."""
+    try:
+        return search.solve(root, max_nodes)
+    except _lib.DcaError as err:
+        if "bad argument" not in str(err) or ": root:" not in str(err):
+            raise  # a failed device call is no property of this state
+        return refused_root(err)
+
+
+def solve_group(search: IDAStar, roots, max_nodes: int) -> List[Dict[str, Any]]:
+    """One group of the CLI's states: a single root on the single search, several as one batch.  A batch the library refuses for
+    one of its roots ("roots[i]: ...") is run again root by root on the single search, which records the refused root and
+    searches the others."""
+    if len(roots) > 1:
+        try:
+            return search.solve_batch(np.stack(roots), max_nodes)
+        except _lib.DcaError as err:
+            if "bad argument" not in str(err) or ": roots[" not in str(err):
+                raise
+    return [solve_one(search, root, max_nodes) for root in roots]
+
+
+def check_batch(env_name: str, batch: int) -> int:
+    """--batch: 1 .. IDASTAR_MAX_BATCH, and 1 on cube3.  ValueError with no device touched."""
+    if not 1 <= batch <= _lib.IDASTAR_MAX_BATCH:
+        raise ValueError("--batch must be in 1..%d, not %d" % (_lib.IDASTAR_MAX_BATCH, batch))
+    if batch > 1 and str(env_name).lower() == "cube3":
+        raise ValueError("--batch %d: a batch of roots is searched on the sliding puzzles only; a cube3 search fills the chip by itself" % batch)
+    return batch
 
 
 def build_parser() -> ArgumentParser:
@@ -110,6 +156,12 @@ def build_parser() -> ArgumentParser:
                         help="node budget of one search; a state that runs out of it is recorded as unsolved.  The default is "
                              "about a minute of search on one MI355X at the measured rate: %d on the puzzles, %d on cube3"
                              % (DEFAULT_MAX_NODES["puzzle"], DEFAULT_MAX_NODES["cube3"]))
+    parser.add_argument('--batch', type=int, default=1,
+                        help="sliding puzzles: search the states in groups of this many consecutive states, every group as one batch "
+                             "(one launch per round runs the next threshold of every state of the group still searching; 1 .. %d).  "
+                             "Each state's result is what its single search gives; --max_nodes is per state; `times` holds the group's "
+                             "wall seconds divided by the group's size.  A group with a state the library refuses is run again state by "
+                             "state.  The default, 1, searches state by state; cube3 takes no other value" % _lib.IDASTAR_MAX_BATCH)
     parser.add_argument('--verbose', action='store_true', default=False, help="print every threshold's node count")
     parser.add_argument('--debug', action='store_true', default=False, help="do not copy the output to results_dir/output.txt")
     return parser
@@ -118,6 +170,7 @@ def build_parser() -> ArgumentParser:
 def main(argv=None):
     args = build_parser().parse_args(argv)
     pdb = pattern_database(args)  # every refusal of the model and the environment: before any device or file work
+    check_batch(args.env, args.batch)
     if args.max_nodes is None:
         args.max_nodes = default_max_nodes(args.env)
     if args.max_nodes <= 0:
@@ -135,14 +188,12 @@ def main(argv=None):
                                                 "nodes_per_threshold")}
     results["states"] = states
     for idx, state in enumerate(states):
-        start = time.time()
-        try:
-            res = search.solve(np.ascontiguousarray(env._get_arr(state), dtype=np.uint8), args.max_nodes)
-        except _lib.DcaError as err:
-            if "bad argument" not in str(err) or ": root:" not in str(err):
-                raise  # a failed device call is no property of this state
-            res = refused_root(err)
-        elapsed = time.time() - start
+        if idx % args.batch == 0:  # the next group of --batch consecutive states (1: this state alone, on the single search)
+            group = [np.ascontiguousarray(env._get_arr(s), dtype=np.uint8) for s in states[idx:idx + args.batch]]
+            start = time.time()
+            found = solve_group(search, group, args.max_nodes)
+            elapsed = (time.time() - start) / len(group)
+        res = found[idx % args.batch]
         soln: List[int] = res["moves"]
         path, cur = [state], state
         for move in soln:

@@ -488,6 +488,29 @@ int dca_idastar_npuzzle_reflected(int dim, const uint8_t* root /*host [N]*/, int
                                   int* length, uint8_t* moves /*host [moves_cap]*/, int moves_cap, int* num_thresholds,
                                   int* thresholds /*host [thresholds_cap]*/, int64_t* nodes_per_threshold /*host [thresholds_cap]*/,
                                   int thresholds_cap, int64_t* total_nodes, void* stream);
+/* A batch of sliding-puzzle roots on one pattern set, searched in rounds: one launch runs the next threshold of every root
+ * still searching, each root on its own blocks with its own counters, so that a states file's independent roots fill the chip
+ * that one small search cannot.  roots: n_roots boards of N bytes; reflect != 0: the reflected search.  Every output is an
+ * array, root r's at index r (moves: r * moves_cap, thresholds and nodes_per_threshold: r * thresholds_cap).
+ * The contract: root r's outputs are those of dca_idastar_npuzzle (or dca_idastar_npuzzle_reflected where reflect != 0) called
+ * on that root alone with the same max_nodes: the status, the length, a move list that solves the root at that length (it need
+ * not be the same list), the thresholds and every completed threshold's count; the last threshold's count varies, as it does
+ * there.  max_nodes is per root and the budget bounds are the single search's, per root: root r's launch of a round has
+ * the blocks, lanes, items and interval of "work items" and "status" above, from that root's own previous count.  One root's
+ * budget or solution does not end another's search: a root that is solved, out of budget, unsolvable, dead at the root or
+ * already the goal leaves the batch, and the call ends with the round that has no root left.
+ * Per round the call SYNCHRONISES the stream once; the control blocks and the root descriptors are allocated once per call.
+ * DCA_E_BADARG before any HIP call and with no output written: what dca_idastar_npuzzle refuses (reflect: num_patterns in
+ * 1..4), n_roots outside 1..DCA_IDASTAR_MAX_BATCH, and a bad root, which the message names by its index ("roots[i]: tile 3
+ * appears twice", "roots[i]: ... the wrong parity"): the whole call is refused. */
+#define DCA_IDASTAR_MAX_BATCH 1024
+int dca_idastar_npuzzle_batch(int dim, const uint8_t* roots /*host [n_roots, N]*/, int n_roots, int num_patterns,
+                              const uint8_t* tiles /*host*/, const int* ks /*host [num_patterns]*/,
+                              const uint8_t* const* tables /*host [num_patterns] of device pointers*/, int reflect,
+                              int64_t max_nodes /*per root*/, int* status /*[n_roots]*/, int* length /*[n_roots]*/,
+                              uint8_t* moves /*[n_roots, moves_cap]*/, int moves_cap, int* num_thresholds /*[n_roots]*/,
+                              int* thresholds /*[n_roots, thresholds_cap]*/, int64_t* nodes_per_threshold /*[n_roots, thresholds_cap]*/,
+                              int thresholds_cap, int64_t* total_nodes /*[n_roots]*/, void* stream);
 int dca_idastar_cube3(const uint8_t* root /*host [54]*/, int num_patterns, const int* kinds /*host [num_patterns]*/,
                       const uint8_t* cubies /*host*/, const int* ks /*host [num_patterns]*/,
                       const uint8_t* const* tables /*host [num_patterns] of device pointers*/, int64_t max_nodes, int* status, int* length,

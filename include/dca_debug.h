@@ -69,6 +69,13 @@ int dca_idastar_host_reflected(int dim, const uint8_t* root, int num_patterns, c
                                const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int64_t max_nodes, int* status,
                                int* length, uint8_t* moves, int moves_cap, int* num_thresholds, int* thresholds,
                                int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes);
+/* Host-only: the batch of dca_idastar_npuzzle_batch on the CPU from HOST tables: the same driver and rounds, a round's roots run
+ * one after the other on the sequential search of dca_idastar_host (reflect != 0: of dca_idastar_host_reflected).  Same
+ * refusals, same outputs. */
+int dca_idastar_host_batch(int dim, const uint8_t* roots /*host [n_roots, N]*/, int n_roots, int num_patterns, const uint8_t* tiles,
+                           const int* ks, const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int reflect,
+                           int64_t max_nodes, int* status, int* length, uint8_t* moves, int moves_cap, int* num_thresholds,
+                           int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes);
 /* Host-only: what dca_pdb_eval computes where reflect == 0, what dca_pdb_eval_reflected computes otherwise, in a plain loop on
  * the CPU, through the row load and the row value the kernels compile.  states, tables and out are HOST memory; the refusals are those of dca_pdb_eval.
  * So that the any-bytes rule and the reflected index have a test on a machine without a GPU. */

@@ -22,6 +22,13 @@ first leg that does not exit 0 (nothing is started on a device after a leg has f
              the same method for the dual look-ups: plain, `+dual`, `+sym:4`, `+sym:4+dual`, `+sym:8`, `+sym:8+dual` and `+sym+dual`,
              plain first; per configuration also whether a state of 21 moves or more was reached.  Written to
              profiles/idastar_dual_probe.txt with `--legs resources,cube3_dual_korf,cube3_dual_korf7 --seconds 60 --out ...`.
+  puzzle15_batch, puzzle24_batch
+             batches of roots (`--batch`, dca_idastar_npuzzle_batch) against the single search, on the same built tables in one
+             process: all 500 shipped puzzle15 states with 5-5-5 and with 6-6-3, plain and `+reflect`, in groups of 1, 16, 64 and
+             500, and the 44 easiest shipped puzzle24 states with 6-6-6-6 in groups of 1, 16 and 44; the single path first and
+             once more at the end.  Total seconds, nodes and nodes per second per pass, and every state's thresholds and completed
+             counts checked against the single path's.  Written to profiles/idastar_batch_probe.txt with
+             `--legs resources,puzzle15_batch,puzzle24_batch --out ...`.
 A state's node budget is what the rate measured so far gets through in --state_seconds; a state that runs out of it is listed.
 The rate of a family is nodes over seconds summed over its searches of at least 0.05 s (shorter ones time the launches, not the
 kernel).  No threshold is set on any time or rate: the numbers are recorded, not met."""
@@ -38,7 +45,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 LEG_TIMEOUT_S = {"resources": 120, "puzzle15": 500, "puzzle24": 500, "cube3": 700, "puzzle15_reflect": 500, "puzzle24_reflect": 700,
-                 "cube3_sym_korf": 800, "cube3_sym_korf7": 800, "cube3_dual_korf": 1000, "cube3_dual_korf7": 1000}
+                 "cube3_sym_korf": 800, "cube3_sym_korf7": 800, "cube3_dual_korf": 1000, "cube3_dual_korf7": 1000,
+                 "puzzle15_batch": 560, "puzzle24_batch": 560}
 SYM_IMAGES = (2, 4, 8, 24)
 DUAL_CONFIGS = ((0, False), (0, True), (4, False), (4, True), (8, False), (8, True), (48, True))  # (N of +sym:N, +dual), plain first
 FIRST_BUDGET = 1 << 31  # nodes, until a rate is known
@@ -165,6 +173,56 @@ def reflect_leg(env_name, specs, seconds, state_seconds, verbose, in_order):
         del pdb
 
 
+BATCH_SIZES = (1, 16, 64, 500)
+BATCH_BUDGET = 1 << 36  # nodes per state, the same for every batch size: no shipped state of these legs comes near it
+
+
+def batch_leg(env_name, specs, reflects, count, in_order):
+    """Per spec and look-up: the tables built once, then the first `count` states searched in groups of each of BATCH_SIZES
+    through the CLI's own group function (search_methods/idastar.solve_group: 1 is the single search, state by state), the
+    single path first and once more at the end (the spread of the same work in the same process).  A leg's time is a host clock
+    around the whole pass, which ends in a device synchronise; every state must come out solved at the shipped optimal length
+    with the single path's thresholds and completed counts.  Seconds and rates are recorded, not met."""
+    import torch
+    from deepcubea_amd.search_methods.idastar import IDAStar, solve_group
+    from deepcubea_amd.utils.pattern_db import PatternDatabase
+    z = golden()
+    states, lens = z["%s_test_states" % env_name], z["%s_test_opt_len" % env_name].astype(int)
+    ids = (np.argsort(lens, kind="stable") if in_order else np.arange(len(lens)))[:count]
+    roots = [np.ascontiguousarray(states[i], dtype=np.uint8) for i in ids]
+    for spec in specs:
+        t0 = time.time()
+        pdb = PatternDatabase(env_name, spec).build()
+        print("%s pdb:%s: %d bytes built in %.2f s" % (env_name, spec, pdb.bytes, time.time() - t0), flush=True)
+        for reflect in reflects:
+            pdb.reflect = reflect  # the same tables: the suffix changes the look-up, not the bytes
+            search = IDAStar(env_name, pdb)
+            solve_group(search, roots[:1], BATCH_BUDGET)  # both kernels' code objects loaded in front of the first timed pass
+            solve_group(search, roots[:2], BATCH_BUDGET)
+            base = None
+            for size in tuple(s for s in BATCH_SIZES if s < len(roots)) + (len(roots), 1):
+                torch.cuda.synchronize()
+                t0 = time.time()
+                found = []
+                for first in range(0, len(roots), size):
+                    found += solve_group(search, roots[first:first + size], BATCH_BUDGET)
+                torch.cuda.synchronize()
+                dt = time.time() - t0
+                for i, want, res in zip(ids, lens[ids], found):
+                    assert res["solved"] and len(res["moves"]) == want, "state %d: %s, shipped optimal %d" % (i, res["status"], want)
+                if base is None:
+                    base = (found, dt)
+                for i, res, one in zip(ids, found, base[0]):
+                    assert res["thresholds"] == one["thresholds"] and res["nodes_per_threshold"][:-1] == one["nodes_per_threshold"][:-1], \
+                        "state %d: batch %d differs from the single search" % (i, size)
+                nodes = sum(res["nodes_generated"] for res in found)
+                print("  %-22s batch %4d: %d states solved at the shipped optimal length, results equal the single path's | %8.2f s  "
+                      "nodes %.4g  %.3g nodes/s  (x %.3f of the first single pass)"
+                      % ("%s %s%s" % (env_name, spec, "+reflect" if reflect else ""), size, len(found), dt, nodes, nodes / dt, dt / base[1]),
+                      flush=True)
+        del pdb
+
+
 def cube3_leg(seconds, state_seconds, verbose):
     from deepcubea_amd.search_methods.idastar import IDAStar
     from deepcubea_amd.utils.cube3_pdb import Cube3PatternDatabase
@@ -265,6 +323,10 @@ def main():
             reflect_leg("puzzle15", ("5-5-5", "6-6-3"), 1e9, args.state_seconds, args.verbose, False)
         elif args.leg == "puzzle24_reflect":
             reflect_leg("puzzle24", ("6-6-6-6",), args.seconds, args.state_seconds, args.verbose, True)
+        elif args.leg == "puzzle15_batch":
+            batch_leg("puzzle15", ("5-5-5", "6-6-3"), (False, True), 500, False)
+        elif args.leg == "puzzle24_batch":
+            batch_leg("puzzle24", ("6-6-6-6",), (False,), 44, True)
         elif args.leg == "cube3":
             cube3_leg(args.seconds, args.state_seconds, args.verbose)
         elif args.leg in ("cube3_sym_korf", "cube3_sym_korf7"):
