@@ -82,6 +82,7 @@ _SIGNATURES = {
     "dca_idastar_cube3": "i pipppplpppipppipp",
     "dca_idastar_cube3_sym": "i pippppilpppipppipp",
     "dca_idastar_cube3_dual": "i pippppilpppipppipp",
+    "dca_idastar_cube3_batch": "i piippppiiplpppipppipp",
     "dca_engine_create": "i piidilii",
     "dca_engine_create_multi": "i piidiliii",
     "dca_engine_num_instances": "i p",
@@ -162,6 +163,7 @@ _SIGNATURES = {
     "dca_idastar_host_sym": "i pippppilpppipppip",
     "dca_cube3_pdb_eval_sym_host": "i plliippppip",
     "dca_idastar_host_dual": "i pippppilpppipppip",
+    "dca_idastar_host_cube3_batch": "i piippppiiplpppipppip",
     "dca_cube3_pdb_eval_dual_host": "i plliippppip",
     "dca_cube3_inverse_locs": "i pip",
     "dca_cube3_sym_tables": "i pp",
@@ -742,14 +744,15 @@ def lightsout_exact_solve(states: torch.Tensor, out: Optional[torch.Tensor] = No
 
 
 # ------------------------------------------------------------------------------ IDA* on the pattern databases
-IDASTAR_SOLVED, IDASTAR_BUDGET, IDASTAR_UNSOLVABLE = 0, 1, 2
-IDASTAR_STATUS = {IDASTAR_SOLVED: "solved", IDASTAR_BUDGET: "budget exhausted", IDASTAR_UNSOLVABLE: "unsolvable"}
+IDASTAR_SOLVED, IDASTAR_BUDGET, IDASTAR_UNSOLVABLE, IDASTAR_BOUNDED = 0, 1, 2, 3
+IDASTAR_STATUS = {IDASTAR_SOLVED: "solved", IDASTAR_BUDGET: "budget exhausted", IDASTAR_UNSOLVABLE: "unsolvable",
+                  IDASTAR_BOUNDED: "bounded"}  # bounded: no solution within the root's max_length (the bounded batches alone)
 IDASTAR_POLL_NODES, IDASTAR_MAX_LANES, IDASTAR_MAX_MOVES = 512, 1 << 19, 254  # include/dca.h
 IDASTAR_OVERSHOOT = IDASTAR_MAX_LANES * IDASTAR_POLL_NODES  # total_nodes <= max_nodes + this, whatever the launch
 IDASTAR_MAX_PREFIX = {ENV_NPUZZLE: 15, ENV_CUBE3: 6}  # moves a work item's prefix has at the most
 IDASTAR_MAX_PUZZLE_PATTERNS = 8
 IDASTAR_MAX_REFLECT_PATTERNS = 4  # a running index and a reflected one per pattern share the 8 a lane keeps
-IDASTAR_MAX_BATCH = 1024  # DCA_IDASTAR_MAX_BATCH: roots of one dca_idastar_npuzzle_batch call
+IDASTAR_MAX_BATCH = 1024  # DCA_IDASTAR_MAX_BATCH: roots of one dca_idastar_npuzzle_batch or dca_idastar_cube3_batch call
 
 
 def _idastar(symbol: str, call, root, width: int, max_nodes: int) -> dict:
@@ -871,6 +874,37 @@ def idastar_cube3(root, patterns, tables, max_nodes: int, sym: int = 0, dual: bo
     symbol = "dca_idastar_cube3" + infix
     return _idastar(symbol, lambda r, n, *out: getattr(lib(), symbol)(r, len(patterns), kinds, ids, ks, ptrs, *images, n, *out, stream_ptr()),
                     root, 54, max_nodes)
+
+
+def _max_length(max_length, n: int):
+    """A bounded batch's max_length argument -> (the int32 array kept alive or None, its pointer or None)."""
+    if max_length is None:
+        return None, None
+    bound = np.ascontiguousarray(np.broadcast_to(np.asarray(max_length, dtype=np.int32), (n,)))
+    return bound, bound.ctypes.data_as(C.c_void_p)
+
+
+def _idastar_cube3_batch(symbol: str, host: bool, roots, patterns, tables, max_length, max_nodes: int, sym: int, dual: bool) -> list:
+    _table_sizes(symbol, [_cube3_table_bytes(kind, len(g)) for kind, g in patterns], tables, host)
+    (kinds, ids, ks), ptrs, _keep = _idastar_set([g for _, g in patterns], [kind for kind, _ in patterns], tables, host)
+    images = _cube3_mode(sym, dual)[1] or (0,)
+    _bound, bound = _max_length(max_length, len(roots))
+    stream = () if host else (stream_ptr(),)
+    return _idastar_batch(symbol, lambda r, n, m, *out: getattr(lib(), symbol)(
+        r, n, len(patterns), kinds, ids, ks, ptrs, *images, int(bool(dual)), bound, m, *out, *stream), roots, 54, max_nodes)
+
+
+def idastar_cube3_batch(roots, patterns, tables, max_nodes: int, max_length=None, sym: int = 0, dual: bool = False) -> list:
+    """A bounded batch of cube3 roots [n, 54], n in 1..IDASTAR_MAX_BATCH, searched in rounds of one launch each (include/dca.h
+    "Bounded batches") -> one dict per root, each what idastar_cube3 gives for that root alone, except that a root with no
+    solution of at most max_length[r] moves (an int for all roots, one per root, or None: no bound) ends with status "bounded".
+    For shallow roots; max_nodes is per root.  A bad root refuses the whole batch: DcaError, "roots[i]: ..."."""
+    return _idastar_cube3_batch("dca_idastar_cube3_batch", False, roots, patterns, tables, max_length, max_nodes, sym, dual)
+
+
+def idastar_host_cube3_batch(roots, patterns, tables, max_nodes: int, max_length=None, sym: int = 0, dual: bool = False) -> list:
+    """idastar_cube3_batch run on the CPU from HOST tables (include/dca_debug.h): no device needed."""
+    return _idastar_cube3_batch("dca_idastar_host_cube3_batch", True, roots, patterns, tables, max_length, max_nodes, sym, dual)
 
 
 def idastar_host(env: int, dim: int, root, patterns, tables, max_nodes: int, reflect: bool = False, sym: int = 0,

@@ -24,6 +24,9 @@
 //   batch    ida_puzzle_batch: many puzzle roots on one pattern set, one launch of ida_puzzle_batch_kernel<DIM, REFLECT> per
 //            round — the next threshold of every root still searching, each root on its own blocks with its own control block.
 //            A root's thresholds go through the same IdaRun steps as ida_drive's one root, so its results are the single search's.
+//            ida_cube3_batch: the same for cube3 roots on one pattern set and look-up mode, ida_cube3_batch_kernel<D>, each root
+//            with a bound on its solution's length (include/dca.h "bounded batches") — many shallow roots, such as the windows
+//            of a found solution.  ida_batch_rounds is both families' rounds.
 //   work     item i of an iteration names a move prefix of P moves, the mixed-radix digits of i (first move = most significant
 //            digit; cube3: radix 12; puzzles: 4 for the first move, then 3 — a digit picks among the moves that do not undo
 //            the one before).  A lane replays the prefix from the root under the pruning rules and the f <= T test and drops the item
@@ -575,6 +578,43 @@ __global__ __launch_bounds__(kIdaThreads) void ida_cube3_kernel(C3Domain::State 
     ida_lane<D>(D::ctx((const uint8_t*)mvw, set), root, ctrl, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
 }
 
+// A cube3 root of a batch as one round's launch reads it: PzBatchRoot's fields around the two location words.
+struct C3BatchRoot {
+    C3Domain::State root;
+    unsigned long long budget;
+    uint32_t T, P, n_items, poll;
+    uint32_t first_block;  // ascending over the round's roots, 0 for the first
+    uint32_t pad;
+};
+
+// One round of a cube3 batch, for the plain, the symmetric and the dual search: ida_puzzle_batch_kernel's scheme (the scalar
+// binary search for the block's root, the root's own control block ctrl[j], a grid that may only queue) around
+// ida_cube3_kernel<D>'s staging — the move tables once per block — and the unchanged ida_lane.  After the staging's barrier
+// no lane waits for another lane or block.
+template <typename D>
+__global__ __launch_bounds__(kIdaThreads) void ida_cube3_batch_kernel(const C3BatchRoot* __restrict__ roots, uint32_t n_roots, typename D::Arg set,
+                                                                      C3IdaMoves mt, IdaCtrl* ctrl) {
+    __shared__ uint32_t mvw[2 * 12 * kC3Locs / 4];
+    __shared__ uint32_t stk[C3Domain::STACK_WORDS * kIdaThreads];
+    uint32_t lo = 0, hi = n_roots;  // the last root whose first block is <= blockIdx.x (the first root's is 0)
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (roots[mid].first_block <= blockIdx.x)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const C3Domain::State root = roots[lo].root;  // read in front of every store: scalar loads, as the kernel argument's are
+    const unsigned long long budget = roots[lo].budget;
+    const uint32_t T = roots[lo].T, P = roots[lo].P, n_items = roots[lo].n_items, poll = roots[lo].poll;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < 2 * 12 * kC3Locs / 4; q++) mvw[q] = mt.w[q];
+    }
+    __syncthreads();
+    ida_lane<D>(D::ctx((const uint8_t*)mvw, set), root, ctrl + lo, stk + threadIdx.x, kIdaThreads, T, P, n_items, budget, poll);
+}
+
 // ----------------------------------------------------------------------------------------------------------- host side
 struct IdaOut {
     int* status;
@@ -619,22 +659,30 @@ struct IdaRun {
     IdaOut out;
     int64_t max_nodes, total, prev;  // prev: the count of the threshold before (0 in front of the first), what the prefix rule reads
     uint32_t T;                      // the next threshold
+    uint32_t bound;                  // no threshold above it runs: kIdaMaxT, or the caller's bound on the solution's length
     int it;                          // thresholds run
     bool active;                     // a next threshold is to run
 
     // The root's outputs in front of any threshold; the search is over at once for a dead root and for the goal.
-    void begin(uint32_t h_root, bool root_dead, bool root_goal, int64_t nodes, const IdaOut& o) {
+    void begin(uint32_t h_root, bool root_dead, bool root_goal, int64_t nodes, const IdaOut& o, uint32_t max_length = kIdaMaxT) {
         out = o;
+        bound = max_length < kIdaMaxT ? max_length : kIdaMaxT;
         max_nodes = nodes;
         total = prev = 0;
         T = h_root;
         it = 0;
+        active = false;
         *out.status = DCA_IDASTAR_UNSOLVABLE;
         *out.length = 0;
         *out.num_thresholds = 0;
         *out.total_nodes = 0;
         if (root_goal && !root_dead) *out.status = DCA_IDASTAR_SOLVED;
-        active = !root_dead && !root_goal && T <= kIdaMaxT;  // (dead: a table says the goal cannot be reached from the root)
+        if (!root_dead && !root_goal) enter();  // (dead: a table says the goal cannot be reached from the root)
+    }
+    // Threshold T is to run if it is within the bound; above the caller's bound the search ends as "no solution that short".
+    void enter() {
+        active = T <= bound;
+        if (!active && T <= kIdaMaxT) *out.status = DCA_IDASTAR_BOUNDED;
     }
     unsigned long long budget() const { return (unsigned long long)(max_nodes - total); }
     // Takes threshold T's control block: totals, status, and the next T or the end.
@@ -660,7 +708,7 @@ struct IdaRun {
         }
         if (ctrl.best == 0u) return;  // no child above the threshold: the whole space was searched
         T = 0xFFFFFFFFu - ctrl.best;
-        active = T <= kIdaMaxT;
+        enter();
     }
 };
 
@@ -727,12 +775,12 @@ static int ida_check_puzzle_root(const char* who, int dim, const uint8_t* root, 
     return 0;
 }
 
-static int ida_check_cube3_root(const char* who, const uint8_t* root) {
+static int ida_check_cube3_root(const char* who, const uint8_t* root, const char* what = "root") {
     uint64_t seen = 0;
     for (int i = 0; i < 54; i++) {
         const int t = root[i];
         if (t >= 54 || ((seen >> t) & 1)) {
-            set_error("bad argument: %s: root: byte %d at position %d: the 54 bytes are not the sticker ids 0..53 once each", who, t, i);
+            set_error("bad argument: %s: %s: byte %d at position %d: the 54 bytes are not the sticker ids 0..53 once each", who, what, t, i);
             return DCA_E_BADARG;
         }
         seen |= 1ull << t;
@@ -750,7 +798,7 @@ static C3Domain::State c3_root_state(const uint8_t* root) {
 // The dual search inverts a lane's words in the or-only form (c3_inverse_locs), which needs every cubie of a kind in a slot of
 // its own.  54 distinct sticker ids need not be that (a corner's sticker on an edge): such a root is no cube state — no move
 // sequence takes it to the goal — and is refused.  The moves permute the slots, so the root's property is every node's.
-static int ida_check_cube3_slots(const char* who, const uint8_t* root) {
+static int ida_check_cube3_slots(const char* who, const uint8_t* root, const char* what = "root") {
     const C3Domain::State s0 = c3_root_state(root);
     const uint64_t locs[2] = {s0.corner, s0.edge};
     for (int kind = 0; kind < 2; kind++) {
@@ -758,7 +806,8 @@ static int ida_check_cube3_slots(const char* who, const uint8_t* root) {
         uint32_t seen = 0;
         for (int q = 0; q < n; q++) seen |= 1u << (((locs[kind] >> (5 * q)) & 31u) / o);
         if (seen != (1u << n) - 1u) {
-            set_error("bad argument: %s: root: the stickers are no cube state: two %s cubies in one slot", who, kind == DCA_CUBE3_CORNERS ? "corner" : "edge");
+            set_error("bad argument: %s: %s: the stickers are no cube state: two %s cubies in one slot", who, what,
+                      kind == DCA_CUBE3_CORNERS ? "corner" : "edge");
             return DCA_E_BADARG;
         }
     }
@@ -952,15 +1001,76 @@ static IdaOut ida_out_at(const IdaOut& o, int r) {
             o.total_nodes + r};
 }
 
-// A batch of puzzle roots on one pattern set (include/dca.h "batches"): ida_search's frame with an IdaRun per root and rounds in
-// place of one root's thresholds.  A round is the next threshold of every root still active, each with the T, P, items,
-// budget, poll interval and blocks its single search would give it.  The order of the HIP calls: every root's table bytes
-// queued and one synchronise; the control blocks and the descriptors in one allocation (only where a root is active); per
-// round one memset of the round's control blocks, one upload of its descriptors, one launch, one read-back, one synchronise;
-// the free.  The host twin runs a round's roots one after the other on ida_lane, as ida_search does its one root.
+// The rounds of a batch, whatever the family: every root's IdaRun has begun (state[r] its root, run[r] its run), and a round is
+// the next threshold of every root still active, each with the T, P, items, budget, poll interval and blocks its single search
+// would give it.  Root: the family's descriptor (PzBatchRoot, C3BatchRoot); c: the host lane's context; launch(dev_desc, n,
+// blocks, dev_ctrl): the family's batch kernel on the round's n descriptors.  The order of the HIP calls: the control blocks
+// and the descriptors in one allocation; per round one memset of the round's control blocks, one upload of its descriptors,
+// one launch, one read-back, one synchronise; the free.  The host twin runs a round's roots one after the other on ida_lane,
+// as ida_search does its one root.
 // P is the single search's rule on the root's own previous count.  A shallower one for batches — the deepest P whose items
-// times the round's roots pass D::worth, fewer items a root wasting less replay — was measured and was slower at every batch
-// size (profiles/idastar_batch_probe.txt): the deep prefix is also what balances a round whose roots differ a thousandfold.
+// times the round's roots pass D::worth, fewer items a root wasting less replay — was measured on the puzzles and was slower at
+// every batch size (profiles/idastar_batch_probe.txt): the deep prefix is also what balances a round whose roots differ a
+// thousandfold.
+template <typename D, typename Root, typename Launch>
+static int ida_batch_rounds(const typename D::State* state, std::vector<IdaRun>& run, bool on_device, hipStream_t st, const char* name,
+                            const typename D::Ctx& c, Launch launch) {
+    const int n_roots = (int)run.size();
+    std::vector<Root> desc((size_t)n_roots);
+    std::vector<IdaCtrl> ctrl((size_t)n_roots);
+    std::vector<int> slot((size_t)n_roots);  // the round's j-th root
+    constexpr size_t kCtrlBytes = sizeof(IdaCtrl), kRootBytes = sizeof(Root);
+    static_assert(kCtrlBytes % 16 == 0, "the descriptors stand behind the control blocks");
+    IdaCtrl* dev_ctrl = nullptr;
+    if (on_device) DCA_HIP(hipMalloc((void**)&dev_ctrl, (size_t)n_roots * (kCtrlBytes + kRootBytes)));
+    Root* dev_desc = on_device ? (Root*)(dev_ctrl + n_roots) : nullptr;
+    const auto round = [&](int n, uint32_t blocks) -> int {
+        if (!on_device) {
+            for (int j = 0; j < n; j++) {
+                uint32_t stk[D::STACK_WORDS] = {};
+                ctrl[j] = IdaCtrl{};
+                ida_lane<D>(c, desc[j].root, &ctrl[j], stk, 1u, desc[j].T, desc[j].P, desc[j].n_items, desc[j].budget, desc[j].poll);
+            }
+            return 0;
+        }
+        DCA_HIP(hipMemsetAsync(dev_ctrl, 0, (size_t)n * kCtrlBytes, st));
+        DCA_HIP(hipMemcpyAsync(dev_desc, desc.data(), (size_t)n * kRootBytes, hipMemcpyHostToDevice, st));
+        launch((const Root*)dev_desc, n, blocks, dev_ctrl);
+        if (int rc = launch_check(name)) return rc;
+        DCA_HIP(hipMemcpyAsync(ctrl.data(), dev_ctrl, (size_t)n * kCtrlBytes, hipMemcpyDeviceToHost, st));
+        DCA_HIP(hipStreamSynchronize(st));
+        return 0;
+    };
+    int rc = 0;
+    while (rc == 0) {
+        int n = 0;
+        uint32_t blocks = 0;
+        for (int r = 0; r < n_roots; r++) {
+            if (!run[r].active) continue;
+            Root& d = desc[n];
+            d = Root{};
+            d.root = state[r];
+            d.budget = run[r].budget();
+            d.T = run[r].T;
+            d.P = ida_prefix<D>(run[r].prev);
+            d.n_items = ida_items<D>(d.P);
+            const int own = on_device ? ida_blocks(d.n_items) : 1;
+            d.poll = ida_poll(d.budget, on_device ? own * kIdaThreads : 1);
+            d.first_block = blocks;
+            blocks += (uint32_t)own;
+            slot[n++] = r;
+        }
+        if (n == 0) break;  // every root has left the batch
+        rc = round(n, blocks);
+        for (int j = 0; j < n && rc == 0; j++) run[slot[j]].step(ctrl[j]);
+    }
+    if (dev_ctrl != nullptr) (void)hipFree(dev_ctrl);  // (after an error a launch may still be writing: the free waits for it)
+    return rc;
+}
+
+// A batch of puzzle roots on one pattern set (include/dca.h "batches"): ida_search's frame with an IdaRun per root and
+// ida_batch_rounds in place of one root's thresholds.  The HIP calls in front of the rounds: every root's table bytes queued
+// and one synchronise.
 template <int DIM, bool REFLECT>
 static int ida_puzzle_batch(const uint8_t* roots, int n_roots, const PdbSet& set, int64_t max_nodes, const IdaOut& out, bool on_device,
                             hipStream_t st) {
@@ -997,62 +1107,16 @@ static int ida_puzzle_batch(const uint8_t* roots, int n_roots, const PdbSet& set
         any = any || run[r].active;
     }
     if (!any) return 0;
-    std::vector<Root> desc((size_t)n_roots);
-    std::vector<IdaCtrl> ctrl((size_t)n_roots);
-    std::vector<int> slot((size_t)n_roots);  // the round's j-th root
-    constexpr size_t kCtrlBytes = sizeof(IdaCtrl), kRootBytes = sizeof(Root);
-    static_assert(kCtrlBytes % 16 == 0, "the descriptors stand behind the control blocks");
-    IdaCtrl* dev_ctrl = nullptr;
-    if (on_device) DCA_HIP(hipMalloc((void**)&dev_ctrl, (size_t)n_roots * (kCtrlBytes + kRootBytes)));
-    Root* dev_desc = on_device ? (Root*)(dev_ctrl + n_roots) : nullptr;
-    const auto round = [&](int n, uint32_t blocks) -> int {
-        if (!on_device) {
-            const typename D::Ctx c = D::ctx(maps, args);
-            for (int j = 0; j < n; j++) {
-                uint32_t stk[D::STACK_WORDS] = {};
-                ctrl[j] = IdaCtrl{};
-                ida_lane<D>(c, desc[j].root, &ctrl[j], stk, 1u, desc[j].T, desc[j].P, desc[j].n_items, desc[j].budget, desc[j].poll);
-            }
-            return 0;
-        }
-        PzBatchArgs<DIM, REFLECT> a{};
-        a.roots = dev_desc;
-        a.n_roots = (uint32_t)n;
-        for (int q = 0; q < kIdaPuzzlePatterns; q++) a.table[q] = args.table[q];
-        a.np = args.np;
-        DCA_HIP(hipMemsetAsync(dev_ctrl, 0, (size_t)n * kCtrlBytes, st));
-        DCA_HIP(hipMemcpyAsync(dev_desc, desc.data(), (size_t)n * kRootBytes, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL((ida_puzzle_batch_kernel<DIM, REFLECT>), dim3(blocks), dim3(kIdaThreads), 0, st, a, maps, dev_ctrl);
-        if (int rc = launch_check("ida_puzzle_batch_kernel")) return rc;
-        DCA_HIP(hipMemcpyAsync(ctrl.data(), dev_ctrl, (size_t)n * kCtrlBytes, hipMemcpyDeviceToHost, st));
-        DCA_HIP(hipStreamSynchronize(st));
-        return 0;
-    };
-    int rc = 0;
-    while (rc == 0) {
-        int n = 0;
-        uint32_t blocks = 0;
-        for (int r = 0; r < n_roots; r++) {
-            if (!run[r].active) continue;
-            Root& d = desc[n];
-            d = Root{};
-            d.root = state[r];
-            d.budget = run[r].budget();
-            d.T = run[r].T;
-            d.P = ida_prefix<D>(run[r].prev);
-            d.n_items = ida_items<D>(d.P);
-            const int own = on_device ? ida_blocks(d.n_items) : 1;
-            d.poll = ida_poll(d.budget, on_device ? own * kIdaThreads : 1);
-            d.first_block = blocks;
-            blocks += (uint32_t)own;
-            slot[n++] = r;
-        }
-        if (n == 0) break;  // every root has left the batch
-        rc = round(n, blocks);
-        for (int j = 0; j < n && rc == 0; j++) run[slot[j]].step(ctrl[j]);
-    }
-    if (dev_ctrl != nullptr) (void)hipFree(dev_ctrl);  // (after an error a launch may still be writing: the free waits for it)
-    return rc;
+    const typename D::Ctx c = D::ctx(maps, args);
+    return ida_batch_rounds<D, Root>(
+        state.data(), run, on_device, st, "ida_puzzle_batch_kernel", c, [&](const Root* dev_desc, int n, uint32_t blocks, IdaCtrl* dev_ctrl) {
+            PzBatchArgs<DIM, REFLECT> a{};
+            a.roots = dev_desc;
+            a.n_roots = (uint32_t)n;
+            for (int q = 0; q < kIdaPuzzlePatterns; q++) a.table[q] = args.table[q];
+            a.np = args.np;
+            hipLaunchKernelGGL((ida_puzzle_batch_kernel<DIM, REFLECT>), dim3(blocks), dim3(kIdaThreads), 0, st, a, maps, dev_ctrl);
+        });
 }
 
 static C3IdaMoves c3_ida_moves() {
@@ -1082,15 +1146,10 @@ static int ida_cube3_search(const C3Domain::State& s0, int reads, const uint8_t*
         max_nodes, out, on_device, st);
 }
 
-// The search on the symmetric look-ups: ida_cube3 with the list in place of the set.  The list's tables are device memory
-// (on_device) or host memory; the root's h is the full maximum, and the root is dead where ANY look-up's byte is >= 0xFE.
-// dual: the search on the dual look-ups — the root's bytes are those of the list at the state and, behind them, those of the
-// second pass at the inverse state (every look-up that does not name all the cubies of its kind).
-static int ida_cube3_sym(const uint8_t* root, const C3SymList& list, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st,
-                         bool dual = false) {
-    const C3Domain::State s0 = c3_root_state(root);
-    uint64_t root_idx[kIdaMaxReads] = {};
-    const uint8_t* tables[kIdaMaxReads] = {};
+// The reads of a look-up list at a root -> their number: the root's h is the full maximum, and the root is dead where ANY
+// look-up's byte is >= 0xFE.  dual: the root's bytes are those of the list at the state and, behind them, those of the second
+// pass at the inverse state (every look-up that does not name all the cubies of its kind).
+static int c3_list_reads(const C3Domain::State& s0, const C3SymList& list, bool dual, const uint8_t** tables, uint64_t* root_idx) {
     int reads = 0;
     for (int p = 0; p < list.n; p++, reads++) {
         const C3Lookup& lk = list.lk[p];
@@ -1106,19 +1165,91 @@ static int ida_cube3_sym(const uint8_t* root, const C3SymList& list, int64_t max
             tables[reads++] = lk.table;
         }
     }
+    return reads;
+}
+
+// The search on the symmetric look-ups: ida_cube3 with the list in place of the set.  The list's tables are device memory
+// (on_device) or host memory.  dual: the search on the dual look-ups.
+static int ida_cube3_sym(const uint8_t* root, const C3SymList& list, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st,
+                         bool dual = false) {
+    const C3Domain::State s0 = c3_root_state(root);
+    uint64_t root_idx[kIdaMaxReads] = {};
+    const uint8_t* tables[kIdaMaxReads] = {};
+    const int reads = c3_list_reads(s0, list, dual, tables, root_idx);
     C3DualSet arg;
     c3_list_arg(list, arg);
     return dual ? ida_cube3_search<C3DualDomain>(s0, reads, tables, root_idx, arg, max_nodes, out, on_device, st)
                 : ida_cube3_search<C3SymDomain>(s0, reads, tables, root_idx, arg, max_nodes, out, on_device, st);
 }
 
+// the plain search's reads at a root: one byte a pattern
+static int c3_set_reads(const C3Domain::State& s0, const C3Set& set, const uint8_t** tables, uint64_t* root_idx) {
+    for (int p = 0; p < set.np; p++) {
+        root_idx[p] = set.kind[p] == DCA_CUBE3_CORNERS ? c3_index<DCA_CUBE3_CORNERS>(s0.corner, set.pat[p], set.k[p])
+                                                      : c3_index<DCA_CUBE3_EDGES>(s0.edge, set.pat[p], set.k[p]);
+        tables[p] = set.table[p];
+    }
+    return set.np;
+}
+
 static int ida_cube3(const uint8_t* root, const C3Set& set, int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
     const C3Domain::State s0 = c3_root_state(root);
     uint64_t root_idx[kPdbMaxPatterns] = {};
-    for (int p = 0; p < set.np; p++)
-        root_idx[p] = set.kind[p] == DCA_CUBE3_CORNERS ? c3_index<DCA_CUBE3_CORNERS>(s0.corner, set.pat[p], set.k[p])
-                                                      : c3_index<DCA_CUBE3_EDGES>(s0.edge, set.pat[p], set.k[p]);
-    return ida_cube3_search<C3Domain>(s0, set.np, set.table, root_idx, set, max_nodes, out, on_device, st);
+    const uint8_t* tables[kPdbMaxPatterns] = {};
+    const int reads = c3_set_reads(s0, set, tables, root_idx);
+    return ida_cube3_search<C3Domain>(s0, reads, tables, root_idx, set, max_nodes, out, on_device, st);
+}
+
+// A batch of cube3 roots on one pattern set and look-up mode (include/dca.h "bounded batches"): ida_puzzle_batch's frame.  D: the
+// mode's domain; arg: its argument as the host lane reads it (D::device_arg makes its device memory once, and only where a
+// root will search on the device); reads_of(s0, tables, idx): the mode's reads at a root, whose largest byte is h of the root
+// and of which any >= 0xFE makes it dead; bound: the roots' bounds or NULL.
+template <typename D, typename Reads>
+static int ida_cube3_batch(const uint8_t* roots, int n_roots, const typename D::Arg& arg, Reads reads_of, const int* bound, int64_t max_nodes,
+                           const IdaOut& out, bool on_device, hipStream_t st) {
+    std::vector<C3Domain::State> state((size_t)n_roots);
+    std::vector<uint8_t> v((size_t)n_roots * kIdaMaxReads);
+    std::vector<int> reads((size_t)n_roots);
+    hipError_t e = hipSuccess;
+    for (int r = 0; r < n_roots; r++) {
+        uint64_t root_idx[kIdaMaxReads] = {};
+        const uint8_t* tables[kIdaMaxReads] = {};
+        state[r] = c3_root_state(roots + (size_t)r * 54);
+        reads[r] = reads_of(state[r], tables, root_idx);
+        uint8_t* bytes = v.data() + (size_t)r * kIdaMaxReads;
+        if (!on_device)
+            for (int p = 0; p < reads[r]; p++) bytes[p] = tables[p][root_idx[p]];
+        else if (e == hipSuccess)
+            e = ida_root_bytes_queue(reads[r], tables, root_idx, st, bytes);
+    }
+    if (on_device) {
+        const hipError_t sync = hipStreamSynchronize(st);  // also after a failure: no copy into v is left pending
+        if (e == hipSuccess) e = sync;
+        if (e != hipSuccess) return hip_fail(e, "IDA*: the roots' table bytes");
+    }
+    std::vector<IdaRun> run((size_t)n_roots);
+    bool any = false;
+    for (int r = 0; r < n_roots; r++) {
+        const uint8_t* bytes = v.data() + (size_t)r * kIdaMaxReads;
+        bool dead = false;
+        uint32_t h_root = 0;
+        for (int p = 0; p < reads[r]; p++) {
+            dead = dead || bytes[p] >= kPdbInf;
+            h_root = h_root > bytes[p] ? h_root : bytes[p];
+        }
+        run[r].begin(h_root, dead, C3Domain::goal(state[r]), max_nodes, ida_out_at(out, r), bound ? (uint32_t)bound[r] : kIdaMaxT);
+        any = any || run[r].active;
+    }
+    if (!any) return 0;
+    const C3IdaMoves mt = c3_ida_moves();
+    typename D::Arg dev_arg = arg;
+    if (on_device)
+        if (int rc = D::device_arg(dev_arg)) return rc;
+    return ida_batch_rounds<D, C3BatchRoot>(
+        state.data(), run, on_device, st, "ida_cube3_batch_kernel", D::ctx((const uint8_t*)mt.w, arg),
+        [&](const C3BatchRoot* dev_desc, int n, uint32_t blocks, IdaCtrl* dev_ctrl) {
+            hipLaunchKernelGGL(ida_cube3_batch_kernel<D>, dim3(blocks), dim3(kIdaThreads), 0, st, dev_desc, (uint32_t)n, dev_arg, mt, dev_ctrl);
+        });
 }
 
 // every refusal of a puzzle search but the root's own (root: the root, or a batch's roots), and the pattern set
@@ -1244,6 +1375,46 @@ static int ida_cube3_sym_entry(const char* who, const uint8_t* root, int num_pat
     return ida_cube3_sym(root, list, max_nodes, out, on_device, st, dual);
 }
 
+// every refusal of a bounded batch of cube3 searches, a bad root by its index, then the batch: before any HIP call and any
+// output.  max_images = 0: the plain search; otherwise the symmetric one, or (dual) the dual one.
+static int ida_cube3_batch_entry(const char* who, const uint8_t* roots, int n_roots, int num_patterns, const int* kinds, const uint8_t* cubies,
+                                 const int* ks, const uint8_t* const* tables, int max_images, bool dual, const int* max_length,
+                                 int64_t max_nodes, const IdaOut& out, bool on_device, hipStream_t st) {
+    if (n_roots < 1 || n_roots > DCA_IDASTAR_MAX_BATCH) {
+        set_error("bad argument: %s: n_roots = %d is not in 1..%d", who, n_roots, DCA_IDASTAR_MAX_BATCH);
+        return DCA_E_BADARG;
+    }
+    if (roots == nullptr) {
+        set_error("bad argument: %s: roots must not be NULL", who);
+        return DCA_E_BADARG;
+    }
+    if (int rc = ida_check_out(who, max_nodes, out)) return rc;
+    const bool plain = max_images == 0 && !dual;
+    C3Set set{};
+    C3SymList list;
+    if (int rc = c3_fill_sym_entry(who, num_patterns, kinds, cubies, ks, tables, plain ? 1 : max_images, set, list)) return rc;
+    for (int r = 0; r < n_roots; r++) {
+        char what[32];
+        snprintf(what, sizeof(what), "roots[%d]", r);
+        if (max_length != nullptr && max_length[r] < 0) {
+            set_error("bad argument: %s: max_length[%d] = %d is negative", who, r, max_length[r]);
+            return DCA_E_BADARG;
+        }
+        if (int rc = ida_check_cube3_root(who, roots + (size_t)r * 54, what)) return rc;
+        if (dual)
+            if (int rc = ida_check_cube3_slots(who, roots + (size_t)r * 54, what)) return rc;
+    }
+    if (plain)
+        return ida_cube3_batch<C3Domain>(
+            roots, n_roots, set, [&](const C3Domain::State& s0, const uint8_t** t, uint64_t* idx) { return c3_set_reads(s0, set, t, idx); }, max_length,
+            max_nodes, out, on_device, st);
+    C3DualSet arg;
+    c3_list_arg(list, arg);
+    const auto reads_of = [&](const C3Domain::State& s0, const uint8_t** t, uint64_t* idx) { return c3_list_reads(s0, list, dual, t, idx); };
+    return dual ? ida_cube3_batch<C3DualDomain>(roots, n_roots, arg, reads_of, max_length, max_nodes, out, on_device, st)
+                : ida_cube3_batch<C3SymDomain>(roots, n_roots, arg, reads_of, max_length, max_nodes, out, on_device, st);
+}
+
 }  // namespace dca
 
 using namespace dca;
@@ -1305,6 +1476,24 @@ int dca_idastar_cube3_dual(const uint8_t* root, int num_patterns, const int* kin
                            int64_t* total_nodes, void* stream) {
     const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
     return ida_cube3_sym_entry(__func__, root, num_patterns, kinds, cubies, ks, tables, max_images, max_nodes, out, true, (hipStream_t)stream, true);
+}
+
+int dca_idastar_cube3_batch(const uint8_t* roots, int n_roots, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
+                            const uint8_t* const* tables, int max_images, int dual, const int* max_length, int64_t max_nodes, int* status,
+                            int* length, uint8_t* moves, int moves_cap, int* num_thresholds, int* thresholds, int64_t* nodes_per_threshold,
+                            int thresholds_cap, int64_t* total_nodes, void* stream) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    return ida_cube3_batch_entry(__func__, roots, n_roots, num_patterns, kinds, cubies, ks, tables, max_images, dual != 0, max_length, max_nodes,
+                                 out, true, (hipStream_t)stream);
+}
+
+int dca_idastar_host_cube3_batch(const uint8_t* roots, int n_roots, int num_patterns, const int* kinds, const uint8_t* cubies, const int* ks,
+                                 const uint8_t* const* tables, int max_images, int dual, const int* max_length, int64_t max_nodes,
+                                 int* status, int* length, uint8_t* moves, int moves_cap, int* num_thresholds, int* thresholds,
+                                 int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes) {
+    const IdaOut out{status, length, moves, moves_cap, num_thresholds, thresholds, nodes_per_threshold, thresholds_cap, total_nodes};
+    return ida_cube3_batch_entry(__func__, roots, n_roots, num_patterns, kinds, cubies, ks, tables, max_images, dual != 0, max_length, max_nodes,
+                                 out, false, nullptr);
 }
 
 int dca_idastar_host(int env, int dim, const uint8_t* root, int num_patterns, const int* kinds, const uint8_t* ids, const int* ks,

@@ -100,6 +100,19 @@ class IDAStar:
             max_nodes = default_max_nodes(self.env_name)
         return _lib.idastar_npuzzle_batch(self.dim, roots, self.pdb.partition, self.pdb.tables, max_nodes, reflect=self.pdb.reflect)
 
+    def solve_bounded(self, roots, max_length, max_nodes: int = None) -> List[Dict[str, Any]]:
+        """A bounded batch of 1 .. IDASTAR_MAX_BATCH SHALLOW cube3 roots, one launch per round (include/dca.h "Bounded batches") ->
+        per root what solve() gives for it alone, except that a root with no solution of at most max_length moves (an int, or
+        one per root) ends with status "bounded" after the thresholds up to it.  max_nodes is per root.  This is what
+        search_methods/refine.py searches a solution's windows with; a shipped state belongs to solve().  ValueError on the
+        sliding puzzles, which have solve_batch."""
+        if self.env != _lib.ENV_CUBE3:
+            raise ValueError("IDA*: a bounded batch is searched on cube3 only; the sliding puzzles have solve_batch")
+        if max_nodes is None:
+            max_nodes = default_max_nodes(self.env_name)
+        return _lib.idastar_cube3_batch(roots, self.pdb.patterns, self.pdb.tables, max_nodes, max_length=max_length, sym=self.pdb.sym,
+                                        dual=self.pdb.dual)
+
 
 def refused_root(err: Exception) -> Dict[str, Any]:
     """The result the CLI records for a root the library refuses (wrong parity, no permutation): unsolved, nothing searched."""
@@ -161,7 +174,9 @@ def build_parser() -> ArgumentParser:
                              "(one launch per round runs the next threshold of every state of the group still searching; 1 .. %d).  "
                              "Each state's result is what its single search gives; --max_nodes is per state; `times` holds the group's "
                              "wall seconds divided by the group's size.  A group with a state the library refuses is run again state by "
-                             "state.  The default, 1, searches state by state; cube3 takes no other value" % _lib.IDASTAR_MAX_BATCH)
+                             "state.  The default, 1, searches state by state; cube3 takes no other value (a shipped cube3 state fills the chip "
+                             "by itself; batches of shallow cube3 roots are what search_methods/refine.py searches a solution's "
+                             "windows with)" % _lib.IDASTAR_MAX_BATCH)
     parser.add_argument('--verbose', action='store_true', default=False, help="print every threshold's node count")
     parser.add_argument('--debug', action='store_true', default=False, help="do not copy the output to results_dir/output.txt")
     return parser

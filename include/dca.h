@@ -553,6 +553,34 @@ int dca_idastar_cube3_dual(const uint8_t* root /*host [54]*/, int num_patterns, 
                            int* status, int* length, uint8_t* moves /*host [moves_cap]*/, int moves_cap, int* num_thresholds,
                            int* thresholds /*host [thresholds_cap]*/, int64_t* nodes_per_threshold /*host [thresholds_cap]*/,
                            int thresholds_cap, int64_t* total_nodes, void* stream);
+/* Bounded batches: many cube3 roots on one pattern set and look-up mode, searched in the rounds of dca_idastar_npuzzle_batch —
+ * one launch runs the next threshold of every root still searching, root r on the blocks its single search would get and with
+ * its own control block.  For SHALLOW roots with a bound on the length, such as the windows of a found solution
+ * (search_methods/refine.py); a shipped state fills the chip by itself and gains nothing here.  roots: n_roots cubes of 54
+ * sticker ids.  max_images = 0 and dual = 0: the search of dca_idastar_cube3; max_images in 1..48: that of
+ * dca_idastar_cube3_sym, or, where dual != 0, of dca_idastar_cube3_dual (dual != 0 with max_images = 0 is refused, as
+ * max_images).  Every output is an array, root r's at index r, as dca_idastar_npuzzle_batch lays them out.
+ * The contract: root r's status, length, thresholds and completed counts are those of the matching single entry point called on
+ * that root alone with the same max_nodes (a move list that solves the root at that length; the last threshold's count
+ * varies, as it does there).  max_length[r] = B changes one thing: a root whose next threshold would exceed B — h(root)
+ * included, in which case nothing is launched for it — stops with status DCA_IDASTAR_BOUNDED, "no solution of at most B
+ * moves": with an admissible set the thresholds run are the single search's thresholds <= B, with their counts, and no
+ * threshold above B is among them.  max_length = NULL, or B >= DCA_IDASTAR_MAX_MOVES: no bound.  max_nodes is per root and
+ * the budget bounds are the single search's, per root; one root's budget, bound or solution does not end another's search.
+ * Per round the call does one memset, one upload, one launch and one read-back and SYNCHRONISES the stream once; the look-up
+ * list's device copy is made (or found) once per call, the control blocks and descriptors are allocated once per call.
+ * DCA_E_BADARG before any HIP call and with no output written: what the matching single entry point refuses, n_roots outside
+ * 1..DCA_IDASTAR_MAX_BATCH, a negative max_length[i], and a bad root, which the message names by its index ("roots[i]: ...",
+ * the dual search's "no cube state" included): the whole call is refused. */
+#define DCA_IDASTAR_BOUNDED 3
+int dca_idastar_cube3_batch(const uint8_t* roots /*host [n_roots, 54]*/, int n_roots, int num_patterns,
+                            const int* kinds /*host [num_patterns]*/, const uint8_t* cubies /*host*/, const int* ks /*host [num_patterns]*/,
+                            const uint8_t* const* tables /*host [num_patterns] of device pointers*/, int max_images /*0: plain*/, int dual,
+                            const int* max_length /*host [n_roots] or NULL*/, int64_t max_nodes /*per root*/, int* status /*[n_roots]*/,
+                            int* length /*[n_roots]*/, uint8_t* moves /*[n_roots, moves_cap]*/, int moves_cap,
+                            int* num_thresholds /*[n_roots]*/, int* thresholds /*[n_roots, thresholds_cap]*/,
+                            int64_t* nodes_per_threshold /*[n_roots, thresholds_cap]*/, int thresholds_cap,
+                            int64_t* total_nodes /*[n_roots]*/, void* stream);
 
 /* state hash (a9). The reference's hash VALUES are process-randomised SipHash (cube3.py:17-21)
  * or unpinned boost::hash_range (parallel_weighted_astar.cpp:104-111); what is pinned is key

@@ -100,6 +100,14 @@ int dca_idastar_host_dual(const uint8_t* root, int num_patterns, const int* kind
                           const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/, int max_images, int64_t max_nodes,
                           int* status, int* length, uint8_t* moves, int moves_cap, int* num_thresholds, int* thresholds,
                           int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes);
+/* Host-only: the bounded batch of dca_idastar_cube3_batch on the CPU from HOST tables: the same driver, rounds and bounds, a
+ * round's roots run one after the other on the sequential search of dca_idastar_host, dca_idastar_host_sym or
+ * dca_idastar_host_dual.  Same arguments but the stream, same refusals, same outputs. */
+int dca_idastar_host_cube3_batch(const uint8_t* roots /*host [n_roots, 54]*/, int n_roots, int num_patterns, const int* kinds,
+                                 const uint8_t* cubies, const int* ks, const uint8_t* const* tables /*host [num_patterns] of HOST pointers*/,
+                                 int max_images /*0: plain*/, int dual, const int* max_length /*host [n_roots] or NULL*/,
+                                 int64_t max_nodes, int* status, int* length, uint8_t* moves, int moves_cap, int* num_thresholds,
+                                 int* thresholds, int64_t* nodes_per_threshold, int thresholds_cap, int64_t* total_nodes);
 /* Host-only: what dca_cube3_pdb_eval_dual computes, in a plain loop on the CPU through the row load and the row value the kernel
  * compiles.  states, tables and out are HOST memory; the refusals are those of dca_cube3_pdb_eval_dual. */
 int dca_cube3_pdb_eval_dual_host(const uint8_t* states /*host [n, ld]*/, int64_t n, int64_t ld, int row_kind, int num_patterns,
