@@ -2599,6 +2599,8 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
     uint8_t* lst = smem + TL::LDS_BYTES;  // child rows of the tile, laid out exactly like their HBM destination
     __shared__ uint32_t l_pid[TP], l_g[TP], l_mv[TP];
     __shared__ uint32_t l_qn, l_qcc[kThreads], l_qrep[kThreads], l_qres[kThreads];
+    __shared__ float l_h[ENV == DCA_ENV_CUBE3 ? TP * EV::A : 1];  // cube3: the children's heuristic and solved flag on their way
+    __shared__ uint8_t l_ok[ENV == DCA_ENV_CUBE3 ? TP * EV::A : 1];  // from the lane that built the child to the lane that stores them
     __shared__ uint32_t l_ohq;  // one-hot rows: next 1 KiB piece (one wave-wide 16-byte store) nobody has claimed yet
     // batch geometry: every workgroup derives it from the state the previous iteration left (S[iters & 1]) and the
     // pop that k_rank just finished; workgroup 0 also records it for the rest of the iteration (close_pop)
@@ -2776,13 +2778,47 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
     // synchronises the workgroup inside a round)
     if (threadIdx.x == 0) l_qn = 0;
     for (uint32_t cc0 = 0; cc0 < nchild; cc0 += kThreads) {
-        const uint32_t cc = cc0 + threadIdx.x;
-        const bool cvalid = cc < nchild;
+        uint32_t cc = cc0 + threadIdx.x;
+        bool cvalid = cc < nchild;
+        uint32_t cw[ENV == DCA_ENV_CUBE3 ? 14 : 1], r3 = 0, a3 = 0;  // cube3: the child's row as dwords, its parent and move
+        if constexpr (ENV == DCA_ENV_CUBE3) {
+            // cube3 builds its rows in registers from constant move maps (cube3_child_words, dca_tile.h), so the move must be
+            // uniform where the code runs: lane t holds parent r = t & 15 and the move a = 3 * wave + m, m = (t >> 4) & 3 — three
+            // moves a wave, m == 3 idle (48 children in each of the four waves).  A bijection on the tile's children: whatever
+            // is indexed by the child is indexed by cc as before, and every id and every array's layout stays what it was.
+            static_assert(TP == 16 && EV::A == 12 && EV::D == 54 && TP * EV::A <= kThreads, "cube3: 16 parents x 12 moves, one round");
+            const uint32_t m = (threadIdx.x >> 4) & 3u;
+            const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+            const uint32_t r = r3 = threadIdx.x & 15u;
+            a3 = 3u * wave + m;
+            cc = r * EV::A + a3;
+            cvalid = m < 3u && r < np;
+            // the parent's row, once per lane (the 16 lanes of a group share the address): bytes 54 and 55 are 0
+            uint32_t pw[14];
+            __builtin_memcpy(pw, lpar + r * EV::D, 52);
+            pw[13] = *reinterpret_cast<const uint16_t*>(lpar + r * EV::D + 52);
+            auto build3 = [&](auto a0) {
+                constexpr int A0 = decltype(a0)::value;
+                if (m == 0u)
+                    cube3_child_words<A0>(pw, cw);
+                else if (m == 1u)
+                    cube3_child_words<A0 + 1>(pw, cw);
+                else
+                    cube3_child_words<A0 + 2>(pw, cw);  // (the idle lanes too: their row is never used)
+            };
+            switch (wave) {
+                case 0: build3(std::integral_constant<int, 0>{}); break;
+                case 1: build3(std::integral_constant<int, 3>{}); break;
+                case 2: build3(std::integral_constant<int, 6>{}); break;
+                default: build3(std::integral_constant<int, 9>{}); break;
+            }
+        }
         uint64_t h = 0;
         uint64_t roww[(EV::D + 7) / 8];  // the child's row, 8 bytes a word (compared against representatives' rows)
         bool known = false;  // a duplicate by its parent's node fields alone (known_duplicate, dca_common.h): never probed
         if (cvalid) {
         uint32_t r = cc / EV::A, a = cc - r * EV::A;
+        if constexpr (ENV == DCA_ENV_CUBE3) r = r3, a = a3;
         // sum_i s_i * (7 i + 3) in 32 bits: the whole sum is at most D * 255 * (7 (D - 1) + 3) < 2^32 for every row length
         // (D = 54: 5 150 070); widened where heur_from takes it.  Four bytes per instruction, from the assembled words: a 4 x u8
         // dot product against the low bytes of the four weights, and — where a weight passes 255 (i >= 37) — another against
@@ -2797,12 +2833,16 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
 #pragma unroll
         for (int k = 0; k < EV::D; k += 8) {
             uint64_t w = 0;
+            if constexpr (ENV == DCA_ENV_CUBE3) {
+                w = (uint64_t)cw[k >> 2] | ((uint64_t)cw[(k >> 2) + 1] << 32);
+            } else {
 #pragma unroll
-            for (int j = 0; j < 8; j++) {
-                if (k + j < EV::D) {
-                    uint32_t b = t.child_byte(r, a, k + j);
-                    w |= (uint64_t)b << (8 * j);
-                    if constexpr (ENV == DCA_ENV_NPUZZLE) manh += manhattan_term(DIM, (uint32_t)(k + j), b);
+                for (int j = 0; j < 8; j++) {
+                    if (k + j < EV::D) {
+                        uint32_t b = t.child_byte(r, a, k + j);
+                        w |= (uint64_t)b << (8 * j);
+                        if constexpr (ENV == DCA_ENV_NPUZZLE) manh += manhattan_term(DIM, (uint32_t)(k + j), b);
+                    }
                 }
             }
             h = hash_word(h, w);
@@ -2837,11 +2877,19 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
         if (a == 0) E.pop_g[r0 + r] = gp;  // the parents' path costs in pop order: what the dedup / push kernels read
         // (the chain marks child_multi are cleared by k_commit after it has read them, not here: another workgroup of this
         // launch may set this child's mark before or after this point)
+        if constexpr (ENV == DCA_ENV_CUBE3) {
+            // cube3: the 16 lanes of a group hold children 12 elements apart, and stores issued from here would be many small
+            // write requests into the same lines.  What only this lane knows goes through LDS; every node field is stored
+            // behind the barrier below with lane t on child t (measured against storing from here: profiles/expand_moves_ab.txt)
+            l_ok[cc] = ok ? 1 : 0;
+            if (heur_id >= 0) l_h[cc] = heur_from(heur_id, (uint64_t)(sum + (sum_hi << 8)), h, manh);
+        } else {
         E.g[id] = (int32_t)(gp + 1u);  // path cost + unit transition cost (astar.py:125-126 / cpp:219)
         E.parent[id] = pid;
         E.move[id] = (uint8_t)a;
         E.solved[id] = ok ? 1 : 0;
         if (heur_id >= 0) E.child_h[j] = heur_from(heur_id, (uint64_t)(sum + (sum_hi << 8)), h, manh);
+        }
         }
         {
             // ---- find-or-insert the CLOSED slot of this round's children (rows taken from LDS)
@@ -2855,6 +2903,18 @@ __global__ __launch_bounds__(kThreads) void k_expand(const Eng* __restrict__ eng
             bool active = cvalid && !known, inserted = false, paused = false;
             uint32_t slot = (uint32_t)h & E.tab_mask, v0 = known ? 0u : GINF, rep_id = 0, probes = 0, qi = 0;
             __syncthreads();  // the round's rows are staged (lst) — and l_qn is zero
+            if constexpr (ENV == DCA_ENV_CUBE3) {
+                // the node fields, lane t on child t: consecutive lanes, consecutive elements (the same values, the same places)
+                const uint32_t c2 = threadIdx.x;
+                if (c2 < nchild) {
+                    const uint32_t r2 = c2 / EV::A, a2 = c2 - r2 * EV::A, j2 = j0 + c2, id2 = base + j2;
+                    E.g[id2] = (int32_t)(l_g[r2] + 1u);
+                    E.parent[id2] = l_pid[r2];
+                    E.move[id2] = (uint8_t)a2;
+                    E.solved[id2] = l_ok[c2];
+                    if (heur_id >= 0) E.child_h[j2] = l_h[c2];
+                }
+            }
             for (;;) {
                 if (active && !paused) {
                     for (;;) {

@@ -1,6 +1,8 @@
 // dca_tile.h — LDS parent-tile helpers shared by the stand-alone expansion kernels (dca_env.hip) and the
 // engine's fused pop->expand kernel (dca_engine.hip).
 #pragma once
+#include <utility>
+
 #include "dca_common.h"
 
 namespace dca {
@@ -99,6 +101,95 @@ struct Tile {
         return b;
     }
 };
+
+// ---- cube3 children from constant move maps.  With the move known at compile time nothing of a child's row is looked up at
+// run time: a move permutes 20 of the 54 stickers, so 7-12 of the row's 14 dwords change, each into bytes of one to four
+// parent dwords — a byte permute (v_perm_b32) per source dword after the first pair; the other dwords are copies.
+
+// Byte b of the result is byte (sel >> 8 b) & 0xFF of the eight bytes {hi, lo} (0-3: lo, 4-7: hi), 0 where that selector byte
+// is 0x0C: v_perm_b32 on the device, the same in plain C++ on the host and wherever it is evaluated at compile time.
+constexpr __host__ __device__ inline uint32_t perm_bytes(uint32_t hi, uint32_t lo, uint32_t sel) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (!__builtin_is_constant_evaluated()) return __builtin_amdgcn_perm(hi, lo, sel);
+#endif
+    uint32_t out = 0;
+    for (int b = 0; b < 4; b++) {
+        const uint32_t s = (sel >> (8 * b)) & 0xFFu;
+        const uint32_t v = s < 4u ? (lo >> (8 * s)) & 0xFFu : s < 8u ? (hi >> (8 * (s - 4u))) & 0xFFu : 0u;
+        out |= v << (8 * b);
+    }
+    return out;
+}
+
+// How dword w of move a's child is made: the n distinct parent dwords its bytes come from (in order of first use) and the
+// selectors that put them together — sel[0] takes src[0] as `lo` and src[1] (if any) as `hi`, sel[k - 1] for k >= 2 takes
+// the bytes so far as `lo` and src[k] as `hi`.  Bytes past the row are 0 (the convention of gather_word).
+struct Cube3WordPlan {
+    bool copy;  // no byte of the dword moves
+    int n, src[4];
+    uint32_t sel[3];
+};
+constexpr Cube3WordPlan cube3_word_plan(int a, int w) {
+    constexpr int D = 54;
+    Cube3WordPlan p{true, 0, {0, 0, 0, 0}, {0, 0, 0}};
+    int which[4] = {-1, -1, -1, -1}, byte[4] = {0, 0, 0, 0};  // per byte of the dword: index into src[], byte of that dword
+    for (int b = 0; b < 4; b++) {
+        const int i = 4 * w + b;
+        if (i >= D) continue;
+        const int s = kCube3Perm.p[a][i];
+        if (s != i) p.copy = false;
+        int k = 0;
+        while (k < p.n && p.src[k] != s / 4) k++;
+        if (k == p.n) p.src[p.n++] = s / 4;
+        which[b] = k;
+        byte[b] = s % 4;
+    }
+    for (int b = 0; b < 4; b++) {
+        p.sel[0] |= (which[b] == 0 ? (uint32_t)byte[b] : which[b] == 1 ? 4u + (uint32_t)byte[b] : 0x0Cu) << (8 * b);
+        for (int k = 2; k < 4; k++) p.sel[k - 1] |= (which[b] == k ? 4u + (uint32_t)byte[b] : (uint32_t)b) << (8 * b);
+    }
+    return p;
+}
+
+template <int A, int W>
+constexpr __host__ __device__ inline uint32_t cube3_child_word(const uint32_t (&pw)[14]) {
+    constexpr Cube3WordPlan p = cube3_word_plan(A, W);
+    if constexpr (p.copy) {
+        return pw[W];
+    } else {
+        uint32_t acc = perm_bytes(pw[p.src[p.n > 1 ? 1 : 0]], pw[p.src[0]], p.sel[0]);
+        if constexpr (p.n > 2) acc = perm_bytes(pw[p.src[2]], acc, p.sel[1]);
+        if constexpr (p.n > 3) acc = perm_bytes(pw[p.src[3]], acc, p.sel[2]);
+        return acc;
+    }
+}
+template <int A, int... W>
+constexpr __host__ __device__ inline void cube3_child_words_seq(const uint32_t (&pw)[14], uint32_t (&cw)[14],
+                                                                std::integer_sequence<int, W...>) {
+    ((cw[W] = cube3_child_word<A, W>(pw)), ...);
+}
+// cw = the row (14 dwords, bytes 54 and 55 zero) of the child that move A makes of the parent whose row is pw
+template <int A>
+constexpr __host__ __device__ inline void cube3_child_words(const uint32_t (&pw)[14], uint32_t (&cw)[14]) {
+    static_assert(A >= 0 && A < 12, "cube3 has 12 moves");
+    cube3_child_words_seq<A>(pw, cw, std::make_integer_sequence<int, 14>{});
+}
+// the builder against the table it was generated from: the parent whose byte i is i becomes kCube3Perm.p[A], byte for byte
+template <int A>
+constexpr bool cube3_child_words_match() {
+    uint32_t pw[14] = {}, cw[14] = {};
+    for (int i = 0; i < 54; i++) pw[i >> 2] |= (uint32_t)i << (8 * (i & 3));
+    cube3_child_words<A>(pw, cw);
+    for (int i = 0; i < 56; i++)
+        if (((cw[i >> 2] >> (8 * (i & 3))) & 0xFFu) != (i < 54 ? (uint32_t)kCube3Perm.p[A][i] : 0u)) return false;
+    return true;
+}
+template <int... A>
+constexpr bool cube3_child_words_match_all(std::integer_sequence<int, A...>) {
+    return (cube3_child_words_match<A>() && ...);
+}
+static_assert(cube3_child_words_match_all(std::make_integer_sequence<int, 12>{}),
+              "cube3_child_words<A> must apply kCube3Perm.p[A] for every move A");
 
 // device copy of the gather map (constant-initialised from the same constexpr builder)
 static __constant__ Cube3Perm d_cube3_perm = make_cube3_perm();
